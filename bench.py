@@ -13,6 +13,10 @@ synchronised (one fp64 all-reduce per BN layer and direction).
 Prints ONE JSON line (rank 0): value = global images per second; roofline = achieved algorithmic TFLOP/s of the dominant
 kernel family (the MFMA implicit-GEMM convolution engine) measured live with hipEvents on the launch stream;
 cpu_baseline = the CPU oracle (restatement of the reference, oracle/restate.py) timed on the host cores at a reduced batch.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs below). Weights, real baskets, latents and
+labels all come from fixed seeds, and with this flag the last timed step starts again from the seeded weights and optimizer state, so two
+builds of the library run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
@@ -243,6 +247,47 @@ def run_extra(name, device, steps=None, warmup=None):
             "last_step_losses": {"d_loss": round(d_l, 5), "g_loss": round(g_l, 5)}}
 
 
+DUMP_MAX_ELEMS = 2 << 20      # per dumped array (8 MB of float32)
+
+
+def snapshot_state(w, G, D):
+    """--dump-outputs: everything a training step reads besides its real baskets, copied before the first step -- the three networks (parameters and
+    buffers), both optimizers and the host and device generators the latents and labels are drawn from. All of it follows from the fixed seeds alone."""
+    return {"nets": [{k: v.clone() for k, v in m.state_dict().items()} for m in (G, D, w.Gen_ema)],
+            "opts": [o.state_dict() for o in (w.g_optimizer, w.d_optimizer)],
+            "rng": (torch.get_rng_state(), torch.cuda.get_rng_state())}
+
+
+def restore_state(w, G, D, snap):
+    for m, sd in zip((G, D, w.Gen_ema), snap["nets"]):
+        m.load_state_dict(sd, strict=True)
+    for o, sd in zip((w.g_optimizer, w.d_optimizer), snap["opts"]):
+        o.load_state_dict(sd)
+    torch.set_rng_state(snap["rng"][0])
+    torch.cuda.set_rng_state(snap["rng"][1])
+
+
+def dump_outputs(w, last, out_dir):
+    """--dump-outputs: what the last timed step handed back, as out_dir/<name>.npy in float32: the two losses step() returned and the generator images and
+    discriminator logits of its generator update (w.last_g). An array of more than DUMP_MAX_ELEMS elements is cut to that many of its elements at fixed
+    positions (seeded draw, sorted): the same positions in every run of the same shapes, so two dumps compare element for element.
+
+    Why main() rewinds to snapshot_state() in front of that step: a step is not bit-reproducible (its batch-norm and bias-gradient sums are atomic),
+    Adam at beta1 = 0 turns a gradient element at noise level into a move of +-lr, and further steps of GAN training amplify that: free-running, two
+    runs of one build were 3 % of the images' rms apart after 15 steps (MI355X, default workload), and the updated parameters differ in single elements
+    by up to 2 lr after one step, which is why they are not dumped. From the seeded state, pairs of runs of --steps 10 --warmup 5 gave bit-identical images,
+    d_loss (4.9) and g_loss (1.1) within 1e-5 and logits at most 2e-4 apart (range 1.5; they follow two noisy discriminator updates); the images also
+    equal those of a --steps 1 --warmup 0 run bit for bit. Step time with the flag: 127.5 / 127.8 ms next to 128.0 / 128.2 ms without, same machine, alternating."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("d_loss", last[0]), ("g_loss", last[1]), ("fake_images", w.last_g[0]), ("fake_adv_output", w.last_g[1])):
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def synth_batches(n, batch, img_size, classes, device, seed):
     """uint8-grid 'real' images in [-1,1] and labels, generated on the CPU with a seeded generator."""
     g = torch.Generator().manual_seed(seed)
@@ -426,6 +471,10 @@ def main():
     ap.add_argument("--strong", action="store_true", help="strong scaling: --batch is the GLOBAL batch, every rank takes batch / world of it (what the reference does: "
                     "src/loader.py:162 divides the configured batch over the ranks); default is weak scaling (--batch per GPU)")
     ap.add_argument("--strict", action="store_true", help="exit non-zero when an extra workload / leg fails (the line is still printed)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0: losses, generator images, discriminator logits) as DIR/<name>.npy in float32. That "
+                         "step starts from the seeded weights, optimizer state and generator state again, so two builds run with the same arguments compare "
+                         "output for output")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_baseline_child:
@@ -549,6 +598,9 @@ def main():
     torch.manual_seed(1234 + rank)  # per-rank sampling streams (reference src/loader.py:99)
     n_d = wl["n_d"]
     pool = generator_real_pool(G, min(32, n_d * (args.warmup + args.steps + 2)), args.batch, wl["z_dim"], wl["classes"], device, 1234 + rank)
+    # --dump-outputs: the LAST timed step starts from this state again (restore_state in the timed loop: ~2 GB of device copies, once), so that what
+    # it computes depends on the seeds alone and not on the rounding noise the steps before it amplified (dump_outputs). Every rank rewinds.
+    snap = snapshot_state(w, G, D) if args.dump_outputs else None
 
     def barrier():
         torch.cuda.synchronize()
@@ -579,6 +631,8 @@ def main():
     ev0.record()
     last = None
     for i in range(args.steps):
+        if snap is not None and i == args.steps - 1:
+            restore_state(w, G, D, snap)
         last = w.step(args.warmup + i, baskets(pool, args.warmup + i, n_d))
         e = torch.cuda.Event(enable_timing=True)
         e.record()
@@ -586,6 +640,8 @@ def main():
         host_done.append(time.perf_counter() - t0)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:          # (outside the timed region, before the profiled steps below overwrite w.last_g)
+        dump_outputs(w, last, args.dump_outputs)
     gpu_done = [ev0.elapsed_time(e) for e in ev_steps]
     host_lead = {"host_issue_ms_per_step": round(1e3 * host_done[-1] / args.steps, 3),
                  "gpu_minus_host_ms_per_step_end": [round(g - 1e3 * h, 2) for g, h in zip(gpu_done, host_done)][:32],

@@ -116,6 +116,25 @@ def test_synthetic_inception_weights_match_oracle_generator():
     assert all(torch.equal(a[k], b[k]) for k in a)
 
 
+def test_bench_dump_outputs_is_float32_capped_and_repeatable(tmp_path):
+    """bench.py --dump-outputs: every array float32, small ones whole, large ones cut to DUMP_MAX_ELEMS elements at the same positions in every call."""
+    import types
+    import numpy as np
+    import bench
+    img = torch.randn(3, 1024, 1024).bfloat16()          # 3 Mi elements: above the cap
+    w = types.SimpleNamespace(last_g=(img, torch.randn(4)))
+    last = (torch.tensor(0.5), torch.tensor(-0.25))
+    for d in ("a", "b"):
+        bench.dump_outputs(w, last, str(tmp_path / d))
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["d_loss", "fake_adv_output", "fake_images", "g_loss"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    assert got["fake_adv_output"].shape == (4,) and float(got["d_loss"]) == 0.5 and float(got["g_loss"]) == -0.25
+    assert got["fake_images"].shape == (bench.DUMP_MAX_ELEMS,) and np.isin(got["fake_images"], img.float().numpy()).all()
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / (k + ".npy"))) for k, v in got.items())
+
+
 def test_loss_schedule_helpers():
     """reference src/utils/losses.py:364-366 (adjust_k) and src/utils/ops.py:106-133 (LeCamEMA)."""
     from studiogan_amd import losses as SL, ops

@@ -494,7 +494,9 @@ def test_attention_flash_single_pass_deferred_rescale(sg, shape):
 def test_head_losses_embedding(sg):
     from studiogan_amd import functional as F, _lib as L
     d = dev()
-    # losses
+    # losses. Seeded here: the scalar losses are judged relative to their own size, and with whatever generator state the tests before this one
+    # leave behind the mean of 19 logits can cancel to ~1e-3 (fp32 summation noise then reads as 2e-5)
+    torch.manual_seed(4)
     r, f = torch.randn(19), torch.randn(19)
     for kind, name in [(0, "hinge"), (1, "wasserstein"), (2, "vanilla")]:
         rr, fr = r.double().requires_grad_(True), f.double().requires_grad_(True)
