@@ -400,6 +400,22 @@ int sg_attn_probs_fwd(const void* theta, const void* phi, void* P, float* lse, i
 int sg_attn_ds_bwd(const void* theta, const void* phi, const void* g, const void* dO, const float* lse, void* dS,
                    int B, int HW, int HW4, int Dp, int Cg, sg_stream_t s);
 
+/* ---- projection front end of the self-attention block as one launch per direction (csrc/attn_proj.hip), bf16 only.
+ * x [B][H][W][ldx] (C channels used); w_theta / w_phi [Dp][C], w_g [Cg][C]: forward images of the three 1x1 layers (Dp includes the zero rows of a
+ * padded image). H, W powers of two >= 2.
+ *   sg_attn_proj_fwd:      theta [B][HW][Dp] = conv1x1(relu?(x)), phi [B][HW/4][Dp] and g [B][HW/4][Cg] = 2x2 max-pool of the other two projections
+ *                          (each rounded to bf16 before the maximum; first maximum in (dy, dx) row-major order wins), idx_phi / idx_g: the argmax
+ *                          planes (uint8, 2 dy + dx) in sg_maxpool2_fwd's layout. x is read once; full-resolution phi / g are never written.
+ *   sg_attn_proj_bwd_data: dx [B][H][W][C] = res + wd_theta^T-image . dtheta + wd_phi . unpool(dphi) + wd_g . unpool(dg), one fp32 sum rounded once;
+ *                          wd_*: the layers' data-gradient images [C][Dp] / [C][Cg]; res ([B][H][W][C], may be NULL): the gradient x already carries.
+ *                          No ReLU mask: only for blocks that read x as it is.
+ * sg_attn_proj_ok returns 1 for the shapes the kernels are built for: (Dp, Cg) = (16, 48) with C <= 96 or (24, 96) with C <= 192, C % 8 == 0. */
+int sg_attn_proj_ok(int B, int H, int W, int C, int ldx, int Dp, int Cg);
+int sg_attn_proj_fwd(const void* x, int ldx, const void* w_theta, const void* w_phi, const void* w_g, void* theta, void* phi, void* g,
+                     uint8_t* idx_phi, uint8_t* idx_g, int B, int H, int W, int C, int Dp, int Cg, int relu, sg_stream_t s);
+int sg_attn_proj_bwd_data(const void* dtheta, const void* dphi, const void* dg, const uint8_t* idx_phi, const uint8_t* idx_g, const void* wd_theta,
+                          const void* wd_phi, const void* wd_g, const void* res, void* dx, int B, int H, int W, int C, int Dp, int Cg, sg_stream_t s);
+
 /* BigGAN-deep skips (reference models/big_resnet_deep_legacy.py:53-56,74-77,236-238): channel slice (+ nearest x up, up in {1,2})
  * y [N][Hs*up][Ws*up][C] from x [N][Hs][Ws][ldx], its adjoint (dx gets all ldx channels, zeros beyond C), and a pitched channel copy */
 int sg_slice_up_fwd(int dtype, const void* x, void* y, int N, int Hs, int Ws, int ldx, int C, int up, sg_stream_t s);

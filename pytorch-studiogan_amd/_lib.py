@@ -178,6 +178,9 @@ _PROTOS = {
     "sg_attn_bwd_fused": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "sg_attn_probs_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "sg_attn_ds_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "sg_attn_proj_ok": [_i, _i, _i, _i, _i, _i, _i],
+    "sg_attn_proj_fwd": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "sg_attn_proj_bwd_data": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "sg_slice_up_fwd": [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "sg_slice_up_bwd": [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "sg_copy_channels": [_i, _vp, _i, _vp, _i, _ll, _i, _vp],

@@ -1,7 +1,7 @@
 """self-attention core (csrc/attn.hip; reference src/utils/ops.py:83-103)."""
 from ._base import *  # noqa: F401,F403  (shared helpers, switches, raw launch wrappers, torch / _lib / comm)
 from .layout import ConvertFn
-from .conv import ConvCfg, ConvDgradFn
+from .conv import ConvCfg, ConvDgradFn, ConvFn, _conv_wgrad
 
 # ---------------------------------------------------------------------------------------------------------
 # self-attention core (reference src/utils/ops.py:83-103)
@@ -280,6 +280,88 @@ class AttnPooledFn(torch.autograd.Function):
         return dtheta, dphi, dg
 
 
+def attn_proj_on():
+    """SG_ATTN_PROJ=0 (read per call): the projections and poolings of SelfAttention as their five separate launches (A/B runs, the reference of the tests)"""
+    return os.environ.get("SG_ATTN_PROJ", "1") != "0"
+
+
+def attn_proj_ok(x, rts):
+    """does csrc/attn_proj.hip take this block? x: the NHWC input, rts: the bank records of conv1x1_theta / _phi / _g"""
+    rt_t, rt_p, rt_g = rts
+    if x.dtype != torch.bfloat16 or x.dim() != 4 or rt_t.rows_pad != rt_p.rows_pad or any(r.RS != 1 or r.trans or r.cin_pad != x.shape[3] for r in rts):
+        return False
+    B, H, W, Cc = x.shape
+    return L.lib().sg_attn_proj_ok(B, H, W, Cc, Cc, rt_t.rows_pad, rt_g.rows_pad) == 1
+
+
+class AttnProjFn(torch.autograd.Function):
+    """theta = conv1x1(x), phi = maxpool2(conv1x1(x)), g = maxpool2(conv1x1(x)) of SelfAttention (reference src/utils/ops.py:83-91) in ONE launch that reads x
+    once (csrc/attn_proj.hip), and their data gradients -- plus whatever gradient x already carries (GradLink chain) -- in ONE launch that writes dx once:
+    full-resolution phi / g and their three-quarters-zero gradients never reach HBM on the forward / data-gradient side. The weight gradients are the three
+    launches of ConvFn (they read the un-pooled gradients, which are only materialised when a weight gradient is wanted). A create_graph backward
+    (gradient penalties) re-evaluates the block from ConvFn / MaxPool2Fn on the saved input and differentiates that."""
+
+    @staticmethod
+    def forward(ctx, x, w_theta, w_phi, w_g, rts, slot, link=None):
+        x = _c(x)
+        rt_t, rt_p, rt_g = rts
+        bank = rt_t.bank()
+        B, H, W, Cc = x.shape
+        Dp, Cg = rt_t.rows_pad, rt_g.rows_pad
+        ctx.link = link
+        if link is not None and link.chain:
+            link.pending += 1
+        for _ in rts:
+            _tick()
+        HW4 = (H // 2) * (W // 2)
+        theta = torch.empty((B, H, W, Dp), dtype=x.dtype, device=x.device)
+        phi = torch.empty((B, HW4, Dp), dtype=x.dtype, device=x.device)
+        g = torch.empty((B, HW4, Cg), dtype=x.dtype, device=x.device)
+        iphi = torch.empty((B, HW4, Dp), dtype=torch.uint8, device=x.device)
+        ig = torch.empty((B, HW4, Cg), dtype=torch.uint8, device=x.device)
+        L.call("sg_attn_proj_fwd", L.ptr(x), Cc, bank.w_fwd(slot, rt_t), bank.w_fwd(slot, rt_p), bank.w_fwd(slot, rt_g), L.ptr(theta), L.ptr(phi), L.ptr(g),
+               L.ptr(iphi), L.ptr(ig), B, H, W, Cc, Dp, Cg, 0, L.stream())
+        ctx.save_for_backward(x, iphi, ig)
+        ctx.rts, ctx.slot = rts, slot
+        ctx.weights = (w_theta, w_phi, w_g)      # the master parameters: only handed on to ConvFn so the second-order graph reaches them
+        return theta, phi, g
+
+    @staticmethod
+    def backward(ctx, dtheta, dphi, dg):
+        x, iphi, ig = ctx.saved_tensors
+        rts, slot = ctx.rts, ctx.slot
+        B, H, W, Cc = x.shape
+        cfg = ConvCfg(1, 1)
+        if torch.is_grad_enabled():
+            # create_graph=True: today's composite on the saved input (which carries its graph), differentiated with a graph of its own; the link is not used
+            if not ctx.needs_input_grad[0]:
+                return (None,) * 7
+            with torch.enable_grad():
+                outs = (ConvFn.apply(x, ctx.weights[0], None, None, rts[0], slot, cfg, None),
+                        MaxPool2Fn.apply(ConvFn.apply(x, ctx.weights[1], None, None, rts[1], slot, cfg, None)),
+                        MaxPool2Fn.apply(ConvFn.apply(x, ctx.weights[2], None, None, rts[2], slot, cfg, None)))
+                (dx,) = torch.autograd.grad(outs, [x], [dtheta, dphi, dg], create_graph=True)
+            return (dx,) + (None,) * 6
+        bank = rts[0].bank()
+        Dp, Cg = rts[0].rows_pad, rts[2].rows_pad
+        dtheta, dphi, dg = _c(dtheta), _c(dphi), _c(dg)
+        dx = None
+        skip_dx = ctx.link.take() if ctx.link is not None else None     # the residual path's gradient w.r.t. this same input (GradLink)
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            L.call("sg_attn_proj_bwd_data", L.ptr(dtheta), L.ptr(dphi), L.ptr(dg), L.ptr(iphi), L.ptr(ig), bank.w_dgrad(slot, rts[0]), bank.w_dgrad(slot, rts[1]),
+                   bank.w_dgrad(slot, rts[2]), L.ptr(skip_dx), L.ptr(dx), B, H, W, Cc, Dp, Cg, L.stream())
+        elif skip_dx is not None:
+            raise RuntimeError("GradLink: a residual gradient was handed over but the attention block's input needs no gradient")
+        if ctx.link is not None and ctx.link.chain:
+            ctx.link.pending -= 1
+        for k, (dy, idx) in enumerate(((dtheta, None), (dphi, iphi), (dg, ig))):
+            if ctx.needs_input_grad[1 + k]:
+                full = dy if idx is None else _maxpool2_bwd(dy, idx, (B, H, W, dy.shape[-1]))
+                _conv_wgrad(x, full, rts[k], slot, cfg)
+        return (dx,) + (None,) * 6
+
+
 class AttnOutFn(torch.autograd.Function):
     """y = x + sigma * conv1x1(o)   (reference src/utils/ops.py:102-103), sigma read from device memory."""
 
@@ -323,4 +405,4 @@ class AttnOutFn(torch.autograd.Function):
         return dx, do, None, None, None, None, None
 
 
-__all__ = ['AttnCoreFn', 'AttnOutFn', 'AttnPooledFn', 'BmmFn', 'MaxPool2BwdFn', 'MaxPool2Fn', 'ScalePtrFn', 'SoftmaxRowsBwdFn', 'SoftmaxRowsFn', '_attn_reference_graph', '_maxpool2_bwd']
+__all__ = ['AttnCoreFn', 'AttnOutFn', 'AttnPooledFn', 'AttnProjFn', 'attn_proj_ok', 'attn_proj_on', 'BmmFn', 'MaxPool2BwdFn', 'MaxPool2Fn', 'ScalePtrFn', 'SoftmaxRowsBwdFn', 'SoftmaxRowsFn', '_attn_reference_graph', '_maxpool2_bwd']

@@ -326,12 +326,19 @@ class SelfAttention(nn.Module):
     def forward_nhwc(self, x, slot=None):
         # x has four readers (theta, phi, g, the residual): their gradients are summed inside the three data-gradient launches
         link = F.GradLink(chain=True) if (F._GRAD_LINK[0] and torch.is_grad_enabled() and x.requires_grad) else None
-        theta = self.conv1x1_theta.forward_nhwc(x, slot, link=link)
-        phi = self.conv1x1_phi.forward_nhwc(x, slot, link=link)
-        g = self.conv1x1_g.forward_nhwc(x, slot, link=link)
-        o = F.AttnCoreFn.apply(theta, phi, g)
         rt = self.conv1x1_attn._sg_rt
         slot = slot if slot is not None else rt.bank().current
+        convs = (self.conv1x1_theta, self.conv1x1_phi, self.conv1x1_g)
+        rts = tuple(m._sg_rt for m in convs)
+        if F.attn_proj_on() and all(m.bias is None for m in convs) and F.attn_proj_ok(x, rts):
+            # the three projections and both poolings in one launch over the shared input (csrc/attn_proj.hip)
+            theta, phi_p, g_p = F.AttnProjFn.apply(x, convs[0].master_weight, convs[1].master_weight, convs[2].master_weight, rts, slot, link)
+            o = F.AttnPooledFn.apply(theta, phi_p, g_p)
+        else:
+            theta = self.conv1x1_theta.forward_nhwc(x, slot, link=link)
+            phi = self.conv1x1_phi.forward_nhwc(x, slot, link=link)
+            g = self.conv1x1_g.forward_nhwc(x, slot, link=link)
+            o = F.AttnCoreFn.apply(theta, phi, g)
         return F.AttnOutFn.apply(x, o, self.conv1x1_attn.master_weight, self.sigma, rt, slot, link)
 
     def forward(self, x):
