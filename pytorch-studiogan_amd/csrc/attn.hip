@@ -613,19 +613,17 @@ extern "C" int sg_attn_fwd_flash_ok(int B, int HW, int HW4, int Dp, int Cg) {
 extern "C" int sg_attn_fwd_fused(const void* theta, const void* phi, const void* g, void* P, float* lse, void* O, float* O32, int B, int HW, int HW4, int Dp, int Cg, sg_stream_t s) {
   SG_CHECK(theta && phi && g && lse && O, "sg_attn_fwd_fused: null");
   SG_CHECK(!(P && O32), "sg_attn_fwd_fused: the fp32 copy of O belongs to the path that does not store P");
-  static const bool two_pass = [] { const char* e = getenv("SG_ATTN_FLASH"); return e && e[0] == '0'; }();    // A/B switch: the first fused forward
-  const bool flash = !P && !(two_pass && !O32);
-  SG_CHECK((flash ? sg_attn_fwd_flash_ok(B, HW, HW4, Dp, Cg) : sg_attn_fwd_fused_ok(B, HW, HW4, Dp, Cg)) == 1, "sg_attn_fwd_fused: unsupported shape");
+  SG_CHECK((P ? sg_attn_fwd_fused_ok(B, HW, HW4, Dp, Cg) : sg_attn_fwd_flash_ok(B, HW, HW4, Dp, Cg)) == 1, "sg_attn_fwd_fused: unsupported shape");
   const int ncg = (Cg + 31) / 32;
   const int lds = HW4 * 64 + ncg * 16384;
   SgProfScope prof((hipStream_t)s, (double)B * HW * ((P ? (double)HW4 * 2.0 : 0.0) + (Dp + Cg) * 2.0 + 4.0) + (double)B * HW4 * (Dp + Cg) * 2.0, 5);
   const dim3 grid(HW / 128, B), blk(256);
   hipStream_t st = (hipStream_t)s;
-#define ATF_LAUNCH(N, SP)                                                                                                                 \
+#define ATF_LAUNCH(N)                                                                                                                     \
   {                                                                                                                                        \
     static bool done = false;                                                                                                              \
-    if (!done) { SG_CHECK(hipFuncSetAttribute((const void*)k_attn_fwd_fused<N, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess, "sg_attn_fwd_fused: LDS attribute"); done = true; } \
-    hipLaunchKernelGGL((k_attn_fwd_fused<N, SP>), grid, blk, lds, st, (const bf16_t*)theta, (const bf16_t*)phi, (const bf16_t*)g, (bf16_t*)P, lse, (bf16_t*)O, HW, HW4, Dp, Cg); \
+    if (!done) { SG_CHECK(hipFuncSetAttribute((const void*)k_attn_fwd_fused<N, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess, "sg_attn_fwd_fused: LDS attribute"); done = true; } \
+    hipLaunchKernelGGL((k_attn_fwd_fused<N, true>), grid, blk, lds, st, (const bf16_t*)theta, (const bf16_t*)phi, (const bf16_t*)g, (bf16_t*)P, lse, (bf16_t*)O, HW, HW4, Dp, Cg); \
   }
 #define ATL_LAUNCH(N)                                                                                                                     \
   {                                                                                                                                        \
@@ -633,8 +631,7 @@ extern "C" int sg_attn_fwd_fused(const void* theta, const void* phi, const void*
     if (!done) { SG_CHECK(hipFuncSetAttribute((const void*)k_attn_fwd_flash<N>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess, "sg_attn_fwd_fused: LDS attribute"); done = true; } \
     hipLaunchKernelGGL((k_attn_fwd_flash<N>), grid, blk, (1 + N) * 16384, st, (const bf16_t*)theta, (const bf16_t*)phi, (const bf16_t*)g, lse, (bf16_t*)O, O32, HW, HW4, Dp, Cg); \
   }
-  if (P) { if (ncg == 1) ATF_LAUNCH(1, true) else if (ncg == 2) ATF_LAUNCH(2, true) else if (ncg == 3) ATF_LAUNCH(3, true) else ATF_LAUNCH(4, true) }
-  else if (!flash) { if (ncg == 1) ATF_LAUNCH(1, false) else if (ncg == 2) ATF_LAUNCH(2, false) else if (ncg == 3) ATF_LAUNCH(3, false) else ATF_LAUNCH(4, false) }
+  if (P) { if (ncg == 1) ATF_LAUNCH(1) else if (ncg == 2) ATF_LAUNCH(2) else if (ncg == 3) ATF_LAUNCH(3) else ATF_LAUNCH(4) }
   else { if (ncg == 1) ATL_LAUNCH(1) else if (ncg == 2) ATL_LAUNCH(2) else if (ncg == 3) ATL_LAUNCH(3) else ATL_LAUNCH(4) }
 #undef ATL_LAUNCH
 #undef ATF_LAUNCH

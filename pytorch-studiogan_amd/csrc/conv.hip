@@ -1,6 +1,7 @@
 // conv.hip -- convolution forward / data-gradient / weight-gradient as implicit GEMM on the MFMA engine
 // (gemm_core.h). Replaces nn.Conv2d + autograd's convolution_backward on the StudioGAN hot path
 // (reference src/utils/ops.py:165-173,195-204; call sites models/big_resnet.py:28-42,177-242).
+#include <type_traits>
 #include "conv_common.h"
 #include "conv_v2.h"
 
@@ -37,44 +38,33 @@ static void conv_fwd_launch(const sg_conv_fwd_desc* d, const Epilogue<T>& e, int
 }
 
 // second-generation kernel (conv_v2.h) for the hot bf16 shapes; returns false when the problem is not eligible
-template <typename T> static bool conv_fwd_v2_try(const sg_conv_fwd_desc*, const Epilogue<T>&, int, int, int, int, hipStream_t) { return false; }
-template <> bool conv_fwd_v2_try<bf16_t>(const sg_conv_fwd_desc* d, const Epilogue<bf16_t>& e, int I, int J, int K, int pflags, hipStream_t st) {
+static bool conv_fwd_v2_try(const ConvFwdProblem& pb, hipStream_t st) {
+  const sg_conv_fwd_desc* d = pb.d;
+  const int I = pb.I, J = pb.J, K = pb.K, pflags = pb.pflags;
   // SG_CONV_V2=0 disables the kernel, =force skips the "enough tiles to fill the chip" heuristic (used by the tests)
-  const char* mode = getenv("SG_CONV_V2");
-  const bool disabled = mode && mode[0] == '0';
-  const bool force = mode && mode[0] == 'f';
-  if (disabled || (pflags & SG_PIX_TRANSPOSED)) return false;
+  const char mode = env_mode("SG_CONV_V2");
+  const bool force = mode == 'f';
+  if (mode == '0' || (pflags & SG_PIX_TRANSPOSED)) return false;
   // stride 2 (round 3: InceptionV3's reduction layers ran on the generic engine): plain row order, no upsample-on-load
-  if (d->stride != 1 && (d->stride != 2 || (pflags & (SG_PIX_UPSAMPLE | SG_PIX_QUAD)) || getenv("SG_CONV_V2_STRIDE2_OFF"))) return false;
+  if (d->stride != 1 && (d->stride != 2 || (pflags & (SG_PIX_UPSAMPLE | SG_PIX_QUAD)))) return false;
   if (d->C % 8 || d->ldx % 8 || d->R * d->S > 25 || J < 256) return false;
   // descriptor extents: offsets with bit 31 (activations) / bit 30 (weights) set must be out of range
-  const long long xbytes = (((long long)d->N * d->Hs * d->Ws - 1) * d->ldx + d->C) * 2, wbytes = (long long)I * K * 2;
-  if (xbytes >= (1ll << 31) || wbytes >= (1ll << 30)) return false;
+  if (pb.xbytes >= (1ll << 31) || pb.wbytes >= (1ll << 30)) return false;
   if (!aligned16(d->x) || !aligned16(d->w)) return false;
-  // the kernel's only epilogue: bf16 rows, 16-byte stores; its ReLU-mask OR residual tile (bf16) is pre-staged with 16-byte loads
-  if ((e.flags & (SG_EPI_ATOMIC | SG_EPI_OUT_F32)) || (e.ldo & 7) || !aligned16(e.out)) return false;
-  // (mask AND residual together: sg_conv_epilogue condenses the mask tile to register bits, then stages the residual tile)
-  if (e.mask && ((e.ldm & 7) || !aligned16(e.mask))) return false;
-  if (e.res && ((e.flags & SG_EPI_RES_F32) || (e.ldr & 7) || !aligned16(e.res))) return false;
+  if (!epi_bf16_rows_ok(pb.e)) return false;
   const int tj = (J + 255) / 256;
-  const int cands[3] = {192, 128, 96};   // (a 256-wide cout tile puts part of its 128 accumulator registers in scratch with hipcc 7.2: left out)
-  int best = 0, best_tiles = 0;
-  for (int c = 0; c < 3; c++) {
-    if (I % cands[c]) continue;
-    const int tiles = (I / cands[c]) * tj;
-    if (tiles >= 512) { best = cands[c]; best_tiles = tiles; break; }
-    if (tiles > best_tiles) { best = cands[c]; best_tiles = tiles; }
-  }
+  int best_tiles = 0;
+  int best = cout_tile_search(I, tj, best_tiles);
   if (!best && I % 8 == 0 && I >= 32) {
     // no candidate divides the cout count (InceptionV3: 32 / 48 / 64 / 160 / 224 / 320 / 448 couts): take the one that pads least -- the kernel
     // zero-fills weight rows >= I and its epilogue stores only the 16-byte chunks that exist. Up to 50 % padding still beats the generic
     // engine these layers ran on (17 % of the FID leg at ~150 us per launch, profiles/r02_fid_leg_kerneltrace.txt).
     int best_pad = 0;
     for (int c = 0; c < 3; c++) {
-      const int padded = ((I + cands[c] - 1) / cands[c]) * cands[c];
+      const int padded = ((I + kCoutTiles[c] - 1) / kCoutTiles[c]) * kCoutTiles[c];
       if (2 * padded > 3 * I) continue;
-      const int tiles = (padded / cands[c]) * tj;
-      if (!best || padded < best_pad) { best = cands[c]; best_pad = padded; best_tiles = tiles; }
+      const int tiles = (padded / kCoutTiles[c]) * tj;
+      if (!best || padded < best_pad) { best = kCoutTiles[c]; best_pad = padded; best_tiles = tiles; }
     }
   }
   // tile-count floor: below it the chip is too empty for this kernel's one workgroup per CU. SG_CONV_V2_MIN_TILES=<n> moves it (A/B switch: 128-cout
@@ -85,12 +75,12 @@ template <> bool conv_fwd_v2_try<bf16_t>(const sg_conv_fwd_desc* d, const Epilog
   ConvV2Params p;
   p.x = (const bf16_t*)d->x; p.w = (const bf16_t*)d->w;
   p.N = d->N; p.Hs = d->Hs; p.Ws = d->Ws; p.C = d->C; p.ldx = d->ldx;
-  const int up = (pflags & SG_PIX_UPSAMPLE) ? 2 : 1;
-  p.Hin = d->Hs * up; p.Win = d->Ws * up; p.Ho = d->Ho; p.Wo = d->Wo;
+  p.Hin = d->Hs * (pb.up ? 2 : 1); p.Win = d->Ws * (pb.up ? 2 : 1); p.Ho = d->Ho; p.Wo = d->Wo;
   p.R = d->R; p.S = d->S; p.pad_h = d->pad_h; p.pad_w = d->pad_w; p.flags = pflags; p.stride = d->stride;
   p.I = I; p.J = J; p.K = K; p.cpt = d->C / 8; p.ntap = d->R * d->S;
-  p.wshift = ilog2_exact(d->Wo); p.hshift = ilog2_exact(d->Ho);
-  p.xbytes = (unsigned)xbytes; p.wbytes = (unsigned)wbytes;
+  p.wshift = pb.wshift; p.hshift = pb.hshift;
+  p.xbytes = (unsigned)pb.xbytes; p.wbytes = (unsigned)pb.wbytes;
+  const Epilogue<bf16_t>& e = pb.e;
   int rc = 0;
   // piece placement (conv_v2.h SCHED): the 96-wide tiles spread their DMA pieces over the MFMA sub-steps (SCHED 1), the 192/128-wide
   // ones issue them in front and prefetch fragments across sub-steps (SCHED 7); SCHED 2..6 are the ablation variants of a
@@ -103,23 +93,6 @@ template <> bool conv_fwd_v2_try<bf16_t>(const sg_conv_fwd_desc* d, const Epilog
     else rc = sg_launch_conv_v2<96, 8, 1, 256, 1>(p, e, st);
   }
   return rc == 0;
-}
-
-template <typename T> static bool conv_fwd_v3_try(const sg_conv_fwd_desc*, const Epilogue<T>&, int, int, int, int, hipStream_t) { return false; }
-template <> bool conv_fwd_v3_try<bf16_t>(const sg_conv_fwd_desc* d, const Epilogue<bf16_t>& e, int I, int J, int K, int pflags, hipStream_t st) {
-  return sg_conv_fwd_v3_try(d, e, I, J, K, pflags, st);      // conv_v3.hip
-}
-template <typename T> static bool conv_fwd_v4_try(const sg_conv_fwd_desc*, const Epilogue<T>&, int, int, int, int, hipStream_t) { return false; }
-template <> bool conv_fwd_v4_try<bf16_t>(const sg_conv_fwd_desc* d, const Epilogue<bf16_t>& e, int I, int J, int K, int pflags, hipStream_t st) {
-  return sg_conv_fwd_v4_try(d, e, I, J, K, pflags, st);      // conv_v4.hip
-}
-template <typename T> static bool conv_fwd_rs_try(const sg_conv_fwd_desc*, const Epilogue<T>&, int, int, int, int, hipStream_t) { return false; }
-template <> bool conv_fwd_rs_try<bf16_t>(const sg_conv_fwd_desc* d, const Epilogue<bf16_t>& e, int I, int J, int K, int pflags, hipStream_t st) {
-  return sg_conv_fwd_rs_try(d, e, I, J, K, pflags, st);      // conv_rs.hip
-}
-template <typename T> static bool conv_fwd_sk_try(const sg_conv_fwd_desc*, const Epilogue<T>&, int, int, int, int, hipStream_t) { return false; }
-template <> bool conv_fwd_sk_try<bf16_t>(const sg_conv_fwd_desc* d, const Epilogue<bf16_t>& e, int I, int J, int K, int pflags, hipStream_t st) {
-  return sg_conv_fwd_sk_try(d, e, I, J, K, pflags, st);      // conv_sk.hip
 }
 
 template <typename T> static int conv_fwd_t(const sg_conv_fwd_desc* d, hipStream_t st) {
@@ -138,20 +111,23 @@ template <typename T> static int conv_fwd_t(const sg_conv_fwd_desc* d, hipStream
   }
   const bool w_vec = (K % ET<T>::VEC == 0) && aligned16(d->w);
   const bool x_vec = (d->C % ET<T>::VEC == 0) && (d->ldx % ET<T>::VEC == 0) && aligned16(d->x);
-  Epilogue<T> e;
-  e.out = d->out; e.out_bstride = 0; e.ldo = d->ldo; e.bias = d->bias;
-  e.res = d->res; e.res_bstride = 0; e.ldr = d->ldr; e.beta = d->beta;
-  e.mask = (const T*)d->mask; e.mask_bstride = 0; e.ldm = d->ldm; e.split_stride = 0;
-  e.alpha = d->alpha; e.alpha_ptr = d->alpha_ptr; e.flags = d->epi_flags; e.I = I; e.J = J;
+  const Epilogue<T> e = make_epilogue<T>(d, I, J);
   const int prof = sg_prof_begin(st, 2.0 * (double)I * (double)J * (double)K, 0);
   int eng = SG_ENG_CONV_GEMM;
-  if (w_vec && x_vec && conv_fwd_sk_try<T>(d, e, I, J, K, pflags, st)) eng = SG_ENG_CONV_SK;
-  else if (w_vec && x_vec && conv_fwd_rs_try<T>(d, e, I, J, K, pflags, st)) eng = SG_ENG_CONV_RS;
-  else if (w_vec && x_vec && conv_fwd_v4_try<T>(d, e, I, J, K, pflags, st)) eng = SG_ENG_CONV_V4;
-  else if (w_vec && x_vec && conv_fwd_v3_try<T>(d, e, I, J, K, pflags, st)) eng = SG_ENG_CONV_V3;
-  else if (w_vec && x_vec && conv_fwd_v2_try<T>(d, e, I, J, K, pflags, st)) eng = SG_ENG_CONV_V2;
-  else if (w_vec && x_vec) conv_fwd_launch<T, true>(d, e, I, J, K, pflags, st);   // all-vector kernels: no gather code in the k-loop
-  else conv_fwd_launch<T, false>(d, e, I, J, K, pflags, st);
+  if constexpr (std::is_same_v<T, bf16_t>) {      // the bf16 kernels, most specific first; each declines what it does not serve
+    if (w_vec && x_vec) {
+      const ConvFwdProblem pb = conv_fwd_problem(d, e, I, J, K, pflags);
+      if (sg_conv_fwd_sk_try(pb, st)) eng = SG_ENG_CONV_SK;
+      else if (sg_conv_fwd_rs_try(pb, st)) eng = SG_ENG_CONV_RS;
+      else if (sg_conv_fwd_v4_try(pb, st)) eng = SG_ENG_CONV_V4;
+      else if (sg_conv_fwd_v3_try(pb, st)) eng = SG_ENG_CONV_V3;
+      else if (conv_fwd_v2_try(pb, st)) eng = SG_ENG_CONV_V2;
+    }
+  }
+  if (eng == SG_ENG_CONV_GEMM) {
+    if (w_vec && x_vec) conv_fwd_launch<T, true>(d, e, I, J, K, pflags, st);   // all-vector kernels: no gather code in the k-loop
+    else conv_fwd_launch<T, false>(d, e, I, J, K, pflags, st);
+  }
   {
     // algorithmic HBM bytes: input, filter, result (pooled size when pooling), ReLU-mask / residual operands once each
     const double es = sizeof(T), jout = (d->epi_flags & SG_EPI_POOL) ? (double)J / 4.0 : (double)J;
@@ -173,14 +149,10 @@ static int conv_fwd_skip(const sg_conv_skip_desc* sk, hipStream_t st, bool dry) 
   const int J = (int)Jll;
   int pflags = d->pix_flags;
   if (d->epi_flags & SG_EPI_POOL) { if ((d->Ho & 1) || (d->Wo & 1)) return 0; pflags |= SG_PIX_QUAD; } else pflags &= ~SG_PIX_QUAD;
-  Epilogue<bf16_t> e;
-  e.out = d->out; e.out_bstride = 0; e.ldo = d->ldo; e.bias = d->bias;
-  e.res = d->res; e.res_bstride = 0; e.ldr = d->ldr; e.beta = d->beta;
-  e.mask = (const bf16_t*)d->mask; e.mask_bstride = 0; e.ldm = d->ldm; e.split_stride = 0;
-  e.alpha = d->alpha; e.alpha_ptr = d->alpha_ptr; e.flags = d->epi_flags; e.I = I; e.J = J;
-  if (dry) return sg_conv_fwd_v4_skip_try(d, sk, e, I, J, K, pflags, st, true) ? 1 : 0;
+  const ConvFwdProblem pb = conv_fwd_problem(d, make_epilogue<bf16_t>(d, I, J), I, J, K, pflags);
+  if (dry) return sg_conv_fwd_v4_skip_try(pb, sk, st, true) ? 1 : 0;
   const int prof = sg_prof_begin(st, 2.0 * (double)I * (double)J * ((double)K + (double)sk->C2), 0);
-  const bool ok = sg_conv_fwd_v4_skip_try(d, sk, e, I, J, K, pflags, st, false);
+  const bool ok = sg_conv_fwd_v4_skip_try(pb, sk, st, false);
   {
     const double jout = (d->epi_flags & SG_EPI_POOL) ? (double)J / 4.0 : (double)J;
     const double x2 = (double)d->N * (sk->x2_up ? (d->Ho / 2) * (d->Wo / 2) : d->Ho * d->Wo) * sk->C2;

@@ -170,21 +170,20 @@ extern "C" int sg_quad_pack_batch(int dtype, const sg_quad_item* items_dev, cons
 // ---- forward / data gradient ---------------------------------------------------------------------------------------------------------
 static bool convq_plan(const sg_convq_desc* d, ConvQParams& p, Epilogue<bf16_t>& e, int& NB) {
   if (d->dtype != SG_DTYPE_BF16 || (d->form != SG_Q_POOL && d->form != SG_Q_UP)) return false;
-  const char* mode = getenv("SG_CONV_Q");
-  if (mode && mode[0] == '0') return false;
+  if (env_mode("SG_CONV_Q") == '0') return false;
   if (d->C < 32 || d->C % 32 || d->ldx % 8 || !aligned16(d->x) || !aligned16(d->wq)) return false;
   const int wlog = ilog2_exact(d->Wl), hlog = ilog2_exact(d->Hl);
   if (wlog < 2 || hlog < 1) return false;
   const long long J = (long long)d->N * d->Hl * d->Wl;
   const long long npix_x = d->form == SG_Q_POOL ? 4 * J : J;
   if (4 * J >= (1ll << 29)) return false;
-  const long long xbytes = ((npix_x - 1) * d->ldx + d->C) * 2, wbytes = (long long)d->Cout * 16 * d->C * 2;
+  const long long xbytes = bf16_extent(npix_x, d->ldx, d->C), wbytes = (long long)d->Cout * 16 * d->C * 2;
   if (xbytes >= (1ll << 31) || wbytes >= (1ll << 31)) return false;
   if ((d->epi_flags & ~SG_EPI_RELU) || (d->pix_flags & ~SG_PIX_RELU)) return false;
-  if ((d->ldo & 7) || !aligned16(d->out)) return false;
-  if (d->mask && ((d->ldm & 7) || !aligned16(d->mask))) return false;
-  if (d->res && ((d->ldr & 7) || !aligned16(d->res))) return false;
-  if (d->Cout % 96 == 0) NB = 3; else if (d->Cout % 64 == 0) NB = 2; else return false;
+  e = make_epilogue<bf16_t>(d, d->Cout, (int)J);
+  if (!epi_bf16_rows_ok(e)) return false;
+  NB = cout_blocks(d->Cout);
+  if (!NB) return false;
   p.x = (const bf16_t*)d->x; p.w = (const bf16_t*)d->wq;
   p.form = d->form; p.Wl = d->Wl; p.wlog = wlog; p.hlog = hlog;
   p.C = d->C; p.ldx = d->ldx; p.I = d->Cout; p.J = (int)J; p.K = 16 * d->C; p.nslice = d->C / 32;
@@ -208,17 +207,13 @@ static bool convq_plan(const sg_convq_desc* d, ConvQParams& p, Epilogue<bf16_t>&
     if (d->form != SG_Q_POOL || !d->w2q || (!c8 && (d->C2 < 32 || d->C2 % 32)) || d->ldx2 % 8 || !aligned16(d->x2) || !aligned16(d->w2q)) return false;
     if (d->bias2 && !d->bias) return false;
     const int c2w = c8 ? 32 : d->C2;
-    const long long x2bytes = ((4 * J - 1) * d->ldx2 + d->C2) * 2, w2bytes = (long long)d->Cout * c2w * 2;
+    const long long x2bytes = bf16_extent(4 * J, d->ldx2, d->C2), w2bytes = (long long)d->Cout * c2w * 2;
     if (x2bytes >= (1ll << 31) || w2bytes >= (1ll << 31)) return false;
     p.x2 = (const bf16_t*)d->x2; p.w2 = (const bf16_t*)d->w2q; p.bias2 = d->bias2;
     p.C2 = c2w; p.ldx2 = d->ldx2; p.nslice2 = c2w / 32; p.x2bytes = (unsigned)x2bytes; p.w2bytes = (unsigned)w2bytes;
     p.c2x8 = c8 ? 1 : 0; p.skip_norelu = d->x2_norelu ? 1 : 0;
   }
   p.stats = d->stats;
-  e.out = d->out; e.out_bstride = 0; e.ldo = d->ldo; e.bias = d->bias;
-  e.res = d->res; e.res_bstride = 0; e.ldr = d->ldr; e.beta = d->beta;
-  e.mask = (const bf16_t*)d->mask; e.mask_bstride = 0; e.ldm = d->ldm; e.split_stride = 0;
-  e.alpha = d->alpha; e.alpha_ptr = d->alpha_ptr; e.flags = d->epi_flags; e.I = d->Cout; e.J = (int)J;
   return true;
 }
 extern "C" int sg_conv2d_q_ok(const sg_convq_desc* d) {
@@ -266,15 +261,15 @@ extern "C" int sg_conv2d_q(const sg_convq_desc* d, sg_stream_t stream) {
 struct QPlan { bool ok; int NB, S, nci, nco, splits, nchunk; long long n, stride; };
 static QPlan wgradq_plan(const sg_convq_wgrad_desc* d) {
   QPlan s; s.ok = false; s.NB = s.S = s.nci = s.nco = s.splits = s.nchunk = 0; s.n = s.stride = 0;
-  const char* mode = getenv("SG_WGRAD_Q");
-  if (mode && mode[0] == '0') return s;
+  if (env_mode("SG_WGRAD_Q") == '0') return s;
   if (d->dtype != SG_DTYPE_BF16 || (d->form != SG_Q_POOL && d->form != SG_Q_UP)) return s;
   if (ilog2_exact(d->Wl) < 2 || ilog2_exact(d->Hl) < 0) return s;
   if (d->Wl == 4 && (d->Hl != 4 || d->N % 4)) return s;
   if (d->Wl < 64 && d->Wl > 4 && d->Hl % (64 / d->Wl)) return s;      // a chunk = 64 / W whole image rows
   if (d->C % 32 || d->ldx % 8 || d->ldg % 8 || !aligned16(d->x) || !aligned16(d->dy)) return s;
   if (d->x_flags & ~SG_PIX_RELU) return s;
-  if (d->Cout % 96 == 0) s.NB = 3; else if (d->Cout % 64 == 0) s.NB = 2; else return s;
+  s.NB = cout_blocks(d->Cout);
+  if (!s.NB) return s;
   const long long K = (long long)d->N * d->Hl * d->Wl;
   if (K % 64 || 4 * K >= (1ll << 29)) return s;
   const long long xpix = d->form == SG_Q_POOL ? 4 * K : K, gpix = d->form == SG_Q_POOL ? K : 4 * K;
@@ -364,8 +359,8 @@ extern "C" int sg_conv2d_q_wgrad(const sg_convq_wgrad_desc* d, sg_stream_t strea
   p.N = d->N; p.H = d->Hl; p.W = d->Wl; p.wlog = ilog2_exact(d->Wl); p.C = d->C; p.Cout = d->Cout;
   p.nci = s.nci; p.nco = s.nco; p.nchunk = s.nchunk; p.splits = s.splits;
   const long long xpix = d->form == SG_Q_POOL ? 4 * K : K, gpix = d->form == SG_Q_POOL ? K : 4 * K;
-  p.xbytes = (unsigned)(((xpix - 1) * d->ldx + d->C) * 2);
-  p.gbytes = (unsigned)(((gpix - 1) * d->ldg + d->Cout) * 2);
+  p.xbytes = (unsigned)bf16_extent(xpix, d->ldx, d->C);
+  p.gbytes = (unsigned)bf16_extent(gpix, d->ldg, d->Cout);
   p.out = d->work; p.split_stride = s.stride;
   p.bias_off = d->dbias ? s.n : -1;
   p.alpha = d->alpha; p.alpha_ptr = d->alpha_ptr;
@@ -373,8 +368,7 @@ extern "C" int sg_conv2d_q_wgrad(const sg_convq_wgrad_desc* d, sg_stream_t strea
   sg_prof_set_executed(prof, 2.0 * (double)d->Cout * (double)K * 16.0 * (double)d->C);
   // the lean kernel (wgrad_ql.h; round 5, same box: the ten quad layers of C3 6.29 -> 5.00 ms, profiles/r05_variant_ab_layer_tables_b.txt).
   // SG_WGRAD_Q_LEAN=0 (read per call) selects the round-4 kernel it replaced: the bit-identity reference of tests/test_quad_gpu.py
-  const char* lean = getenv("SG_WGRAD_Q_LEAN");
-  const int rc = (lean && lean[0] == '0') ? sg_launch_wgrad_q(p, s.NB, s.S, st) : sg_launch_wgrad_ql(p, s.NB, s.S, st);
+  const int rc = env_mode("SG_WGRAD_Q_LEAN") == '0' ? sg_launch_wgrad_q(p, s.NB, s.S, st) : sg_launch_wgrad_ql(p, s.NB, s.S, st);
   if (rc == 0) {
     const bool pl = d->form == SG_Q_POOL;
     const int cb = d->C > 64 ? (d->C + 63) / 64 : 1;

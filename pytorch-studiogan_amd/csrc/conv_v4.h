@@ -450,6 +450,7 @@ static inline int sg_launch_conv_v4_skip(const ConvV4Params& p, const Epilogue<b
 template <int NB, int TJW>
 static inline int sg_launch_conv_v4(const ConvV4Params& p, const Epilogue<bf16_t>& e, hipStream_t st) {
   const bool up = (p.flags & SG_PIX_UPSAMPLE) != 0, relu = (p.flags & SG_PIX_RELU) != 0;
+#ifdef SG_ABLATION   // measurement builds only: wrong results by construction, so the product library has neither these instantiations nor the switch
   if constexpr (NB == 3 && TJW == 2) {
     if (!up && !relu) {          // ablation instantiations (see the kernel): SG_V4_ABLATE = bit mask, plain 96-cout tiles only
       static int abl = -1;
@@ -468,6 +469,7 @@ static inline int sg_launch_conv_v4(const ConvV4Params& p, const Epilogue<bf16_t
       }
     }
   }
+#endif
   if (relu) return up ? sg_launch_conv_v4r<NB, true, true, TJW>(p, e, st) : sg_launch_conv_v4r<NB, true, false, TJW>(p, e, st);
   return up ? sg_launch_conv_v4r<NB, false, true, TJW>(p, e, st) : sg_launch_conv_v4r<NB, false, false, TJW>(p, e, st);
 }

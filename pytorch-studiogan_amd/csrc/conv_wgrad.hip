@@ -1,33 +1,40 @@
 // conv_wgrad.hip -- convolution weight gradient (sg_conv2d_wgrad, sg_conv2d_wgrad_plan): wgrad_v2.h for the hot bf16 shapes,
 // gemm_core.h's ConvPixMC x ConvPixMC contraction otherwise; deterministic two-stage split-K.
 // Replaces autograd's convolution_backward (weight part) on the StudioGAN hot path (reference src/utils/ops.py:165-173,195-204).
+#include <type_traits>
 #include "conv_common.h"
 #include "wgrad_v2.h"
 #include "wgrad_sk.h"
 #include "wgrad_v3.h"
 #include "wgrad_v3l.h"
 
+// what every bf16 weight-gradient kernel asks first: stride 1, ds_read_b64_tr_b16 fragments allowed, plain (not transposed) operands, and
+// buffer-descriptor DMA -- bit 31 of a byte offset must be out of range
+static bool wgrad_bf16_ok(const sg_conv_wgrad_desc* d) {
+  if (d->dtype != SG_DTYPE_BF16 || d->stride != 1 || d->no_tr) return false;
+  if ((d->x_flags | d->g_flags) & SG_PIX_TRANSPOSED) return false;
+  return (long long)d->N * d->xHs * d->xWs * d->ldx * 2 < (1ll << 31) && (long long)d->N * d->gHs * d->gWs * d->ldg * 2 < (1ll << 31);
+}
+// descriptor extents of the stored x and dy
+static inline unsigned wgrad_xbytes(const sg_conv_wgrad_desc* d) { return (unsigned)bf16_extent((long long)d->N * d->xHs * d->xWs, d->ldx, d->C); }
+static inline unsigned wgrad_gbytes(const sg_conv_wgrad_desc* d) { return (unsigned)bf16_extent((long long)d->N * d->gHs * d->gWs, d->ldg, d->Cout); }
+
 // ---- thin layers: streaming kernel (wgrad_sk.h). SG_WGRAD_SK=0 disables it. -----------------------------------------------------
 struct SkPlan { bool ok, taps; int NI, NJ, swap, nw; long long n; };
 static SkPlan wgrad_sk_plan(const sg_conv_wgrad_desc* d) {
   SkPlan s; s.ok = false; s.taps = false; s.NI = s.NJ = s.swap = s.nw = 0; s.n = 0;
-  const char* mode = getenv("SG_WGRAD_SK");
-  if (mode && mode[0] == '0') return s;
-  if (d->dtype != SG_DTYPE_BF16 || d->stride != 1 || d->no_tr) return s;
-  if ((d->x_flags | d->g_flags) & SG_PIX_TRANSPOSED) return s;
-  const int wsh = ilog2_exact(d->Wo), hsh = ilog2_exact(d->Ho);
-  if (wsh < 0 || hsh < 0) return s;
+  if (env_mode("SG_WGRAD_SK") == '0' || !wgrad_bf16_ok(d)) return s;
+  if (ilog2_exact(d->Wo) < 0 || ilog2_exact(d->Ho) < 0) return s;
   if (d->C % 8 || d->ldx % 8 || d->Cout % 8 || d->ldg % 8 || !aligned16(d->x) || !aligned16(d->dy)) return s;
   const long long K = (long long)d->N * d->Ho * d->Wo;
   if (K % 32 || K / 32 >= (1ll << 30)) return s;
-  if ((long long)d->N * d->xHs * d->xWs * d->ldx * 2 >= (1ll << 31) || (long long)d->N * d->gHs * d->gWs * d->ldg * 2 >= (1ll << 31)) return s;
   const bool xup = d->x_flags & SG_PIX_UPSAMPLE, gup = d->g_flags & SG_PIX_UPSAMPLE, xrelu = d->x_flags & SG_PIX_RELU;
   if (d->R == 1 && d->S == 1 && d->pad_h == 0 && d->pad_w == 0) {
     if (d->C > 192 || d->Cout > 96) return s;
     const int ni = (d->C + 31) / 32, nj = (d->Cout + 31) / 32;
     if (ni == 4 || ni == 5) return s;                       // (no layer of the networks has 97..160 input channels on a thin 1x1)
     s.ok = true; s.NI = ni; s.NJ = nj; s.n = (long long)d->C * d->Cout;
-  } else if (d->R == 3 && d->S == 3 && d->pad_h == 1 && d->pad_w == 1 && !xup && !gup && !xrelu && d->Wo >= 32) {
+  } else if (is_3x3_s1_p1(d) && !xup && !gup && !xrelu && d->Wo >= 32) {
     if (d->C == 8 && d->Cout <= 96) { s.ok = true; s.taps = true; s.NI = 3; s.NJ = (d->Cout + 31) / 32; s.n = 72ll * d->Cout; }
     else if (d->Cout == 8 && d->C <= 96) { s.ok = true; s.taps = true; s.swap = 1; s.NI = 3; s.NJ = (d->C + 31) / 32; s.n = 72ll * d->C; }
   }
@@ -37,8 +44,7 @@ static SkPlan wgrad_sk_plan(const sg_conv_wgrad_desc* d) {
 static int wgrad_sk_launch(const sg_conv_wgrad_desc* d, const SkPlan& s, hipStream_t st) {
   WgradSkParams p;
   const long long K = (long long)d->N * d->Ho * d->Wo;
-  const unsigned xbytes = (unsigned)((((long long)d->N * d->xHs * d->xWs - 1) * d->ldx + d->C) * 2);
-  const unsigned gbytes = (unsigned)((((long long)d->N * d->gHs * d->gWs - 1) * d->ldg + d->Cout) * 2);
+  const unsigned xbytes = wgrad_xbytes(d), gbytes = wgrad_gbytes(d);
   p.H = d->Ho; p.W = d->Wo; p.wshift = ilog2_exact(d->Wo); p.hshift = ilog2_exact(d->Ho);
   p.nchunk = (int)(K / 32);
   p.arelu = (d->x_flags & SG_PIX_RELU) ? 1 : 0;
@@ -61,20 +67,19 @@ static int wgrad_sk_launch(const sg_conv_wgrad_desc* d, const SkPlan& s, hipStre
 struct V3Plan { bool ok; int NB, nci, nco, splits, nchunk; long long n, stride; };   // stride: floats per partial = n (+ Cout when the bias gradient rides along)
 static V3Plan wgrad_v3_plan(const sg_conv_wgrad_desc* d) {
   V3Plan s; s.ok = false; s.NB = s.nci = s.nco = s.splits = s.nchunk = 0; s.n = 0; s.stride = 0;
-  const char* mode = getenv("SG_WGRAD_V3");
-  if (mode && mode[0] == '0') return s;
-  const bool force = mode && mode[0] == 'f';                            // test hook: no lower bound on the problem size
-  if (d->dtype != SG_DTYPE_BF16 || d->stride != 1 || d->no_tr || d->R != 3 || d->S != 3 || d->pad_h != 1 || d->pad_w != 1) return s;
-  if ((d->x_flags | d->g_flags) & SG_PIX_TRANSPOSED) return s;
+  const char mode = env_mode("SG_WGRAD_V3");
+  if (mode == '0') return s;
+  const bool force = mode == 'f';                                       // test hook: no lower bound on the problem size
+  if (!wgrad_bf16_ok(d) || !is_3x3_s1_p1(d)) return s;
   if (d->Wo != 4 && d->Wo != 8 && d->Wo != 16 && d->Wo != 32 && d->Wo % 64) return s;
   if (d->Wo == 4) {     // (round 4) 4 x 4 images: a chunk is four whole images, plain operands only
     if (d->Ho != 4 || d->N % 4 || ((d->x_flags | d->g_flags) & SG_PIX_UPSAMPLE)) return s;
   } else if (d->Wo < 64 && d->Ho % (64 / d->Wo)) return s;              // a chunk = 64 / W whole image rows
   if (d->C % 32 || d->ldx % 8 || d->ldg % 8 || !aligned16(d->x) || !aligned16(d->dy)) return s;
-  if (d->Cout % 96 == 0) s.NB = 3; else if (d->Cout % 64 == 0) s.NB = 2; else return s;
+  s.NB = cout_blocks(d->Cout);
+  if (!s.NB) return s;
   const long long K = (long long)d->N * d->Ho * d->Wo;
   if (K % 64 || (!force && K < (d->Wo == 4 ? 4096 : 16384)) || K >= (1ll << 31)) return s;      // (4 x 4 layers: 16 pixels per image, batch 256 = 4096)
-  if ((long long)d->N * d->xHs * d->xWs * d->ldx * 2 >= (1ll << 31) || (long long)d->N * d->gHs * d->gWs * d->ldg * 2 >= (1ll << 31)) return s;
   s.nci = d->C / 32; s.nco = d->Cout / (32 * s.NB); s.nchunk = (int)(K / 64);
   s.n = 9ll * d->C * d->Cout;
   s.stride = s.n + (d->dbias ? d->Cout : 0);
@@ -94,36 +99,47 @@ static int wgrad_v3_launch(const sg_conv_wgrad_desc* d, const V3Plan& s, hipStre
   p.gHs = d->gHs; p.gWs = d->gWs; p.ldg = d->ldg; p.g_up = (d->g_flags & SG_PIX_UPSAMPLE) ? 1 : 0;
   p.N = d->N; p.H = d->Ho; p.W = d->Wo; p.C = d->C; p.Cout = d->Cout;
   p.nci = s.nci; p.nco = s.nco; p.nchunk = s.nchunk; p.splits = s.splits;
-  p.xbytes = (unsigned)((((long long)d->N * d->xHs * d->xWs - 1) * d->ldx + d->C) * 2);
-  p.gbytes = (unsigned)((((long long)d->N * d->gHs * d->gWs - 1) * d->ldg + d->Cout) * 2);
+  p.xbytes = wgrad_xbytes(d); p.gbytes = wgrad_gbytes(d);
   p.out = d->work; p.split_stride = s.stride;
   p.bias_off = d->dbias ? s.n : -1; p.bias_scale = p.g_up ? 0.25f : 1.f;
   p.alpha = d->alpha; p.alpha_ptr = d->alpha_ptr;
   // the lean kernel (wgrad_v3l.h; round 5, same box: the wgrad_v3 layers of C3 -8..-12 %, profiles/r05_variant_ab_layer_tables_b.txt); it hands problems whose
   // operands are read through a 2x upsampling to wgrad_v3.h's kernel. SG_WGRAD_V3_LEAN=0 (read per call): that kernel everywhere (the bit-identity reference of
   // tests/test_conv_v2_gpu.py)
-  if (const char* m = getenv("SG_WGRAD_V3_LEAN")) { if (m[0] == '0') return sg_launch_wgrad_v3(p, s.NB, st); }
+  if (env_mode("SG_WGRAD_V3_LEAN") == '0') return sg_launch_wgrad_v3(p, s.NB, st);
   return sg_launch_wgrad_v3l(p, s.NB, st);
 }
 
-// tile configuration and split-K plan of the weight gradient (shared by the launcher and sg_conv2d_wgrad_plan)
+// ---- tile kernel (wgrad_v2.h). SG_CONV_V2=0 disables it, =force takes narrow problems too. ---------------------------------------------
 static bool wgrad_v2_ok(const sg_conv_wgrad_desc* d) {
-  const char* mode = getenv("SG_CONV_V2");
-  if (mode && mode[0] == '0') return false;
-  const bool force = mode && mode[0] == 'f';
-  if (d->dtype != SG_DTYPE_BF16 || d->stride != 1 || d->no_tr) return false;
-  if ((d->x_flags | d->g_flags) & SG_PIX_TRANSPOSED) return false;
+  const char mode = env_mode("SG_CONV_V2");
+  if (mode == '0' || !wgrad_bf16_ok(d)) return false;
   if (ilog2_exact(d->Ho) < 0 || ilog2_exact(d->Wo) < 0) return false;
   if (d->C % 8 || d->ldx % 8 || d->Cout % 8 || d->ldg % 8 || !aligned16(d->x) || !aligned16(d->dy)) return false;
   const long long K = (long long)d->N * d->Ho * d->Wo;
   const int I = d->R * d->S * d->C;
-  // buffer-descriptor DMA: bit 31 of a byte offset must be out of range
-  if ((long long)d->N * d->xHs * d->xWs * d->ldx * 2 >= (1ll << 31) || (long long)d->N * d->gHs * d->gWs * d->ldg * 2 >= (1ll << 31)) return false;
-  if (!force && (I < 64 || d->Cout < 64 || K < 4096)) return false;   // narrow I (1x1 convs, the 8-channel RGB stem) wastes part of the
-                                                                       // 256-row tile but still beats the generic kernel 3-4x
+  if (mode != 'f' && (I < 64 || d->Cout < 64 || K < 4096)) return false;   // narrow I (1x1 convs, the 8-channel RGB stem) wastes part of the
+                                                                           // 256-row tile but still beats the generic kernel 3-4x
   return true;
 }
+static int wgrad_v2_launch(const sg_conv_wgrad_desc* d, const Epilogue<bf16_t>& e, int I, int J, int K, int splits, hipStream_t st) {
+  WgradV2Params p;
+  p.x = (const bf16_t*)d->x; p.dy = (const bf16_t*)d->dy;
+  p.xHs = d->xHs; p.xWs = d->xWs; p.C = d->C; p.ldx = d->ldx;
+  p.x_up = (d->x_flags & SG_PIX_UPSAMPLE) ? 1 : 0; p.x_relu = (d->x_flags & SG_PIX_RELU) ? 1 : 0;
+  p.Hin = d->xHs * (p.x_up ? 2 : 1); p.Win = d->xWs * (p.x_up ? 2 : 1);
+  p.gHs = d->gHs; p.gWs = d->gWs; p.Cout = d->Cout; p.ldg = d->ldg; p.g_up = (d->g_flags & SG_PIX_UPSAMPLE) ? 1 : 0;
+  p.Ho = d->Ho; p.Wo = d->Wo; p.wshift = ilog2_exact(d->Wo); p.hshift = ilog2_exact(d->Ho);
+  p.R = d->R; p.S = d->S; p.pad_h = d->pad_h; p.pad_w = d->pad_w;
+  p.I = I; p.J = J; p.K = K;
+  p.xbytes = wgrad_xbytes(d); p.gbytes = wgrad_gbytes(d);
+  int klen = K;
+  if (splits > 1) { klen = (K + splits - 1) / splits; klen = ((klen + 63) / 64) * 64; splits = (K + klen - 1) / klen; }
+  p.klen = klen;
+  return sg_launch_wgrad_v2(p, e, splits, st);
+}
 
+// tile configuration and split-K plan of the tile kernel and of the generic engine
 static void wgrad_plan(int I, int J, int K, int bk, int want_splits, int& BI, int& BJ, int& splits, bool v2 = false) {
   if (v2) { BI = 256; BJ = sg_wgrad_v2_bj(I, J, K); bk = 64; }
   else if (I <= 32) { BI = 32; BJ = 256; }
@@ -144,24 +160,47 @@ static void wgrad_plan(int I, int J, int K, int bk, int want_splits, int& BI, in
   }
 }
 
+// ---- THE engine choice: the two query entry points and the launcher all ask here, so they cannot disagree ------------------------------------
+// The partial tiles are `splits` rows of `stride` floats in the workspace, the first n of each the gradient (the halo kernel appends Cout bias sums when
+// d->dbias is set); work_floats = what the deterministic two-stage reduction needs, 0 = one writer, no workspace. The streaming and the halo kernel exist
+// in the workspace form only: a launch (launching = true) whose descriptor brings less than the planned workspace falls through to the next engine.
+enum WgradEngine { WG_SK, WG_V3, WG_V2, WG_GEMM };
+struct WgradChoice {
+  WgradEngine engine;
+  int splits; long long n, stride, work_floats;
+  bool fuses_bias;
+  SkPlan sk; V3Plan v3; int BI, BJ;      // the chosen family's own fields
+};
+static WgradChoice wgrad_choose(const sg_conv_wgrad_desc* d, bool launching) {
+  WgradChoice c = {};
+  const auto have = [&](long long floats) { return !launching || (d->work && d->work_floats >= floats); };
+  c.sk = wgrad_sk_plan(d);
+  if (c.sk.ok && have((long long)c.sk.nw * c.sk.n)) {
+    c.engine = WG_SK; c.splits = c.sk.nw; c.n = c.stride = c.sk.n; c.work_floats = (long long)c.sk.nw * c.sk.n;
+    return c;
+  }
+  c.v3 = wgrad_v3_plan(d);
+  if (c.v3.ok && have((long long)c.v3.splits * c.v3.stride)) {
+    c.engine = WG_V3; c.splits = c.v3.splits; c.n = c.v3.n; c.stride = c.v3.stride; c.work_floats = (long long)c.v3.splits * c.v3.stride;
+    c.fuses_bias = d->dbias != nullptr;
+    return c;
+  }
+  const int I = d->R * d->S * d->C, J = d->Cout, K = (int)((long long)d->N * d->Ho * d->Wo);
+  const bool v2 = wgrad_v2_ok(d);
+  wgrad_plan(I, J, K, d->dtype == SG_DTYPE_BF16 ? ET<bf16_t>::BK : ET<float>::BK, d->splits, c.BI, c.BJ, c.splits, v2);
+  c.engine = v2 ? WG_V2 : WG_GEMM; c.n = c.stride = (long long)I * J; c.work_floats = c.splits > 1 ? c.splits * c.n : 0;
+  return c;
+}
+
 extern "C" int sg_conv2d_wgrad_fuses_bias(const sg_conv_wgrad_desc* d) {
-  if (!d || !d->dbias) return 0;
-  if (wgrad_sk_plan(d).ok) return 0;
-  return wgrad_v3_plan(d).ok ? 1 : 0;            // (the launcher also needs the workspace sg_conv2d_wgrad_plan asks for: the caller provides it)
+  return (d && wgrad_choose(d, false).fuses_bias) ? 1 : 0;     // (the launcher also needs the workspace sg_conv2d_wgrad_plan asks for: the caller provides it)
 }
 
 extern "C" int sg_conv2d_wgrad_plan(const sg_conv_wgrad_desc* d, int* splits, long long* work_floats) {
   SG_CHECK(d && splits && work_floats, "sg_conv2d_wgrad_plan: null");
-  const int I = d->R * d->S * d->C, J = d->Cout;
-  const long long K = (long long)d->N * d->Ho * d->Wo;
-  const SkPlan sk = wgrad_sk_plan(d);
-  if (sk.ok) { *splits = sk.nw; *work_floats = (long long)sk.nw * sk.n; return 0; }
-  const V3Plan v3 = wgrad_v3_plan(d);
-  if (v3.ok) { *splits = v3.splits; *work_floats = (long long)v3.splits * v3.stride; return 0; }
-  int BI, BJ, sp;
-  wgrad_plan(I, J, (int)K, d->dtype == SG_DTYPE_BF16 ? 32 : 16, d->splits, BI, BJ, sp, wgrad_v2_ok(d));
-  *splits = sp;
-  *work_floats = sp > 1 ? (long long)sp * I * J : 0;
+  const WgradChoice c = wgrad_choose(d, false);
+  *splits = c.splits;
+  *work_floats = c.work_floats;
   return 0;
 }
 
@@ -234,10 +273,7 @@ __global__ __launch_bounds__(256) void k_splitk_reduce_v4(const float* partial, 
   }
 }
 static void splitk_reduce_launch(const float* partial, float* out, int splits, long long n, long long stride, float* out2, long long n2, hipStream_t st) {
-  if (stride == 0) stride = n;
-  static int mode = -1;
-  if (mode < 0) { const char* e = getenv("SG_REDUCE_V4"); mode = (e && e[0] == '0') ? 0 : 1; }
-  const bool v4 = mode && (n % 4 == 0) && (n2 % 4 == 0) && (stride % 4 == 0) && ((((uintptr_t)partial | (uintptr_t)out | (uintptr_t)out2) & 15) == 0);
+  const bool v4 = (n % 4 == 0) && (n2 % 4 == 0) && (stride % 4 == 0) && ((((uintptr_t)partial | (uintptr_t)out | (uintptr_t)out2) & 15) == 0);
   if (v4) {
     long long blocks = ((n + n2) / 4 + 63) / 64; if (blocks > 8192) blocks = 8192; if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(k_splitk_reduce_v4, dim3((int)blocks), dim3(256), 0, st, partial, out, splits, n, stride, out2, n2);
@@ -272,25 +308,6 @@ static void conv_wgrad_launch(const sg_conv_wgrad_desc* d, const Epilogue<T>& e,
   else sg_launch_gemm<T, LM, LM, 128, 128, 2, 2, TR>(lp, lq, e, I, J, K, splits, 1, st);
 }
 
-template <typename T> static bool wgrad_v2_launch(const sg_conv_wgrad_desc*, const Epilogue<T>&, int, int, int, int, hipStream_t) { return false; }
-template <> bool wgrad_v2_launch<bf16_t>(const sg_conv_wgrad_desc* d, const Epilogue<bf16_t>& e, int I, int J, int K, int splits, hipStream_t st) {
-  WgradV2Params p;
-  p.x = (const bf16_t*)d->x; p.dy = (const bf16_t*)d->dy;
-  p.xHs = d->xHs; p.xWs = d->xWs; p.C = d->C; p.ldx = d->ldx;
-  p.x_up = (d->x_flags & SG_PIX_UPSAMPLE) ? 1 : 0; p.x_relu = (d->x_flags & SG_PIX_RELU) ? 1 : 0;
-  p.Hin = d->xHs * (p.x_up ? 2 : 1); p.Win = d->xWs * (p.x_up ? 2 : 1);
-  p.gHs = d->gHs; p.gWs = d->gWs; p.Cout = d->Cout; p.ldg = d->ldg; p.g_up = (d->g_flags & SG_PIX_UPSAMPLE) ? 1 : 0;
-  p.Ho = d->Ho; p.Wo = d->Wo; p.wshift = ilog2_exact(d->Wo); p.hshift = ilog2_exact(d->Ho);
-  p.R = d->R; p.S = d->S; p.pad_h = d->pad_h; p.pad_w = d->pad_w;
-  p.I = I; p.J = J; p.K = K;
-  p.xbytes = (unsigned)((((long long)d->N * d->xHs * d->xWs - 1) * d->ldx + d->C) * 2);
-  p.gbytes = (unsigned)((((long long)d->N * d->gHs * d->gWs - 1) * d->ldg + d->Cout) * 2);
-  int klen = K;
-  if (splits > 1) { klen = (K + splits - 1) / splits; klen = ((klen + 63) / 64) * 64; splits = (K + klen - 1) / klen; }
-  p.klen = klen;
-  return sg_launch_wgrad_v2(p, e, splits, st) == 0;
-}
-
 // algorithmic HBM bytes of a weight gradient: x and dy once (stored sizes), the fp32 gradient read and written
 template <typename T> static double wgrad_alg_bytes(const sg_conv_wgrad_desc* d) {
   return sizeof(T) * ((double)d->N * d->xHs * d->xWs * d->C + (double)d->N * d->gHs * d->gWs * d->Cout) + 8.0 * (double)d->R * d->S * d->C * d->Cout;
@@ -303,51 +320,37 @@ template <typename T, bool TR> static int conv_wgrad_t(const sg_conv_wgrad_desc*
   SG_CHECK((long long)d->N * d->xHs * d->xWs * d->ldx < (1ll << 31) && (long long)d->N * d->gHs * d->gWs * d->ldg < (1ll << 31),
            "sg_conv2d_wgrad: tensor too large for 32-bit element offsets");
   const int K = (int)Kll;
-  {
-    const SkPlan sk = wgrad_sk_plan(d);
-    if (sk.ok && d->work && d->work_floats >= (long long)sk.nw * sk.n) {
-      const int prof = sg_prof_begin(st, 2.0 * (double)I * (double)J * (double)K, 1);
-      if (wgrad_sk_launch(d, sk, st) != 0) { sg_set_error("sg_conv2d_wgrad: streaming kernel launch failed"); return -2; }
-      splitk_reduce_launch((const float*)d->work, d->dw, sk.nw, sk.n, 0, nullptr, 0, st);
-      sg_prof_tag(prof, SG_ENG_WGRAD_SK, wgrad_alg_bytes<T>(d));
-      sg_prof_end(st, prof);
-      SG_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  {
-    const V3Plan v3 = wgrad_v3_plan(d);
-    if (v3.ok && d->work && d->work_floats >= (long long)v3.splits * v3.stride) {
-      const int prof = sg_prof_begin(st, 2.0 * (double)I * (double)J * (double)K, 1);
-      if (wgrad_v3_launch(d, v3, st) != 0) { sg_set_error("sg_conv2d_wgrad: halo kernel launch failed"); return -2; }
-      splitk_reduce_launch((const float*)d->work, d->dw, v3.splits, v3.n, v3.stride, d->dbias, (long long)(d->dbias ? d->Cout : 0), st);
-      sg_prof_tag(prof, SG_ENG_WGRAD_V3, wgrad_alg_bytes<T>(d));
-      sg_prof_end(st, prof);
-      SG_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  int BI, BJ, splits;
-  const bool v2 = wgrad_v2_ok(d);
-  wgrad_plan(I, J, K, ET<T>::BK, d->splits, BI, BJ, splits, v2);
-  const long long n = (long long)I * J;
-  const bool two_stage = splits > 1 && d->work && d->work_floats >= (long long)splits * n;
-  Epilogue<T> e;
-  e.out = d->dw; e.out_bstride = 0; e.ldo = I; e.bias = nullptr; e.res = nullptr; e.res_bstride = 0; e.ldr = 0; e.beta = 0.f;
-  e.mask = nullptr; e.mask_bstride = 0; e.ldm = 0; e.alpha = d->alpha; e.alpha_ptr = d->alpha_ptr; e.split_stride = 0;
-  e.flags = SG_EPI_OUT_F32; e.I = I; e.J = J;
-  if (splits == 1) { e.res = d->dw; e.ldr = I; e.beta = 1.f; e.flags |= SG_EPI_RES_F32; }   // single writer: dw += tile, no atomics
-  else if (two_stage) { e.out = d->work; e.split_stride = n; }                                 // partial tiles, reduced below
-  else e.flags |= SG_EPI_ATOMIC;                                                               // no workspace: fp32 atomics
+  const WgradChoice c = wgrad_choose(d, true);
   const int prof = sg_prof_begin(st, 2.0 * (double)I * (double)J * (double)K, 1);
-  const bool fast = (d->C % ET<T>::VEC == 0) && (d->ldx % ET<T>::VEC == 0) && aligned16(d->x) &&
-                    (d->Cout % ET<T>::VEC == 0) && (d->ldg % ET<T>::VEC == 0) && aligned16(d->dy);
   int eng = SG_ENG_WGRAD_GEMM;
-  if (v2 && wgrad_v2_launch<T>(d, e, I, J, K, splits, st)) eng = SG_ENG_WGRAD_V2;
-  else if (fast) conv_wgrad_launch<T, TR, true>(d, e, I, J, K, BI, BJ, splits, st);
-  else conv_wgrad_launch<T, TR, false>(d, e, I, J, K, BI, BJ, splits, st);
+  bool two_stage = true;
+  if (c.engine == WG_SK) {
+    if (wgrad_sk_launch(d, c.sk, st) != 0) { sg_set_error("sg_conv2d_wgrad: streaming kernel launch failed"); return -2; }
+    eng = SG_ENG_WGRAD_SK;
+  } else if (c.engine == WG_V3) {
+    if (wgrad_v3_launch(d, c.v3, st) != 0) { sg_set_error("sg_conv2d_wgrad: halo kernel launch failed"); return -2; }
+    eng = SG_ENG_WGRAD_V3;
+  } else {
+    two_stage = c.work_floats > 0 && d->work && d->work_floats >= c.work_floats;
+    Epilogue<T> e;
+    e.out = d->dw; e.out_bstride = 0; e.ldo = I; e.bias = nullptr; e.res = nullptr; e.res_bstride = 0; e.ldr = 0; e.beta = 0.f;
+    e.mask = nullptr; e.mask_bstride = 0; e.ldm = 0; e.alpha = d->alpha; e.alpha_ptr = d->alpha_ptr; e.split_stride = 0;
+    e.flags = SG_EPI_OUT_F32; e.I = I; e.J = J;
+    if (c.splits == 1) { e.res = d->dw; e.ldr = I; e.beta = 1.f; e.flags |= SG_EPI_RES_F32; }   // single writer: dw += tile, no atomics
+    else if (two_stage) { e.out = d->work; e.split_stride = c.n; }                                // partial tiles, reduced below
+    else e.flags |= SG_EPI_ATOMIC;                                                                // no workspace: fp32 atomics
+    if constexpr (std::is_same_v<T, bf16_t>) {
+      if (c.engine == WG_V2 && wgrad_v2_launch(d, e, I, J, K, c.splits, st) == 0) eng = SG_ENG_WGRAD_V2;
+    }
+    if (eng == SG_ENG_WGRAD_GEMM) {
+      const bool fast = (d->C % ET<T>::VEC == 0) && (d->ldx % ET<T>::VEC == 0) && aligned16(d->x) &&
+                        (d->Cout % ET<T>::VEC == 0) && (d->ldg % ET<T>::VEC == 0) && aligned16(d->dy);
+      if (fast) conv_wgrad_launch<T, TR, true>(d, e, I, J, K, c.BI, c.BJ, c.splits, st);
+      else conv_wgrad_launch<T, TR, false>(d, e, I, J, K, c.BI, c.BJ, c.splits, st);
+    }
+  }
   if (two_stage) {
-    splitk_reduce_launch((const float*)d->work, d->dw, splits, n, 0, nullptr, 0, st);
+    splitk_reduce_launch((const float*)d->work, d->dw, c.splits, c.n, c.stride, c.fuses_bias ? d->dbias : nullptr, c.fuses_bias ? d->Cout : 0, st);
   }
   sg_prof_tag(prof, eng, wgrad_alg_bytes<T>(d));
   sg_prof_end(st, prof);

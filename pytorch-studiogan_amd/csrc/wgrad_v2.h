@@ -274,9 +274,5 @@ static inline int sg_wgrad_v2_bj(int I, int J, int K) {
 static inline int sg_launch_wgrad_v2(const WgradV2Params& p, const Epilogue<bf16_t>& e, int splits, hipStream_t st) {
   if (sg_wgrad_v2_bj(p.I, p.J, p.K) == 256)
     return p.x_relu ? sg_launch_wgrad_v2r<true, 256>(p, e, splits, st) : sg_launch_wgrad_v2r<false, 256>(p, e, splits, st);
-  // SG_WGRAD_NBUF=2: the two-buffer loop (A/B switch); default three buffers
-  static int nbuf = -1;
-  if (nbuf < 0) { const char* e3 = getenv("SG_WGRAD_NBUF"); nbuf = (e3 && e3[0] == '2') ? 2 : 3; }
-  if (nbuf == 3) return p.x_relu ? sg_launch_wgrad_v2r<true, 128, 3>(p, e, splits, st) : sg_launch_wgrad_v2r<false, 128, 3>(p, e, splits, st);
-  return p.x_relu ? sg_launch_wgrad_v2r<true, 128>(p, e, splits, st) : sg_launch_wgrad_v2r<false, 128>(p, e, splits, st);
+  return p.x_relu ? sg_launch_wgrad_v2r<true, 128, 3>(p, e, splits, st) : sg_launch_wgrad_v2r<false, 128, 3>(p, e, splits, st);   // three LDS buffers
 }

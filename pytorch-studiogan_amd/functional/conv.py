@@ -14,6 +14,23 @@ class ConvCfg:
         self.in_relu, self.in_upsample, self.out_pool = in_relu, in_upsample, out_pool
         self.stats = stats      # a batch norm reads the result next: take its statistics in the epilogue where the kernel can
 
+    def out_hw(self, Hs, Ws):
+        """size of the convolution's result (before pooling) over a stored Hs x Ws input"""
+        up = 2 if self.in_upsample else 1
+        return (Hs * up + 2 * self.pad_h - self.R) // self.stride + 1, (Ws * up + 2 * self.pad_w - self.S) // self.stride + 1
+
+    def pix_flags(self):
+        """how the forward and weight-gradient launches read the stored input"""
+        return (L.PIX_RELU if self.in_relu else 0) | (L.PIX_UPSAMPLE if self.in_upsample else 0)
+
+    def epi_flags(self):
+        return L.EPI_POOL if self.out_pool else 0
+
+    @property
+    def scale(self):
+        """2x2 average pooling = the kernels' pooling sum x 1/4 (alpha of the forward launch and of both gradients)"""
+        return 0.25 if self.out_pool else 1.0
+
 
 class GradLink:
     """Carries the gradient a residual block's INPUT receives through the skip path from the block tail's backward (ConvSkipFn) to the
@@ -67,10 +84,8 @@ def _conv_fwd(x, rt, slot, cfg, bias, res=None, stats=False):
                          stats=stats and _BN_FUSED_STATS[0] and rt.rows_pad == rt.rows)
         if y is not None:
             return y
-    pf = (L.PIX_RELU if cfg.in_relu else 0) | (L.PIX_UPSAMPLE if cfg.in_upsample else 0)
-    ef = L.EPI_POOL if cfg.out_pool else 0
-    return conv2d_raw(x, bank.w_fwd(slot, rt), Cin, rt.rows_pad, cfg.R, cfg.S, cfg.stride, cfg.pad_h, cfg.pad_w, pf, ef, bias=bias, res=res,
-                      alpha=0.25 if cfg.out_pool else 1.0)
+    return conv2d_raw(x, bank.w_fwd(slot, rt), Cin, rt.rows_pad, cfg.R, cfg.S, cfg.stride, cfg.pad_h, cfg.pad_w, cfg.pix_flags(), cfg.epi_flags(),
+                      bias=bias, res=res, alpha=cfg.scale)
 
 
 def _conv_wgrad(x, dy, rt, slot, cfg, dbias=None):
@@ -80,13 +95,9 @@ def _conv_wgrad(x, dy, rt, slot, cfg, dbias=None):
     form = _quad_form(rt, cfg, x)
     if form is not None and conv2d_q_wgrad_raw(x, dy, bank.dwt(slot, rt), form, Cin, rt.rows_pad, L.PIX_RELU if cfg.in_relu else 0, dbias=dbias):
         return dbias is not None
-    up = 2 if cfg.in_upsample else 1
-    Ho = (Hs * up + 2 * cfg.pad_h - cfg.R) // cfg.stride + 1
-    Wo = (Ws * up + 2 * cfg.pad_w - cfg.S) // cfg.stride + 1
-    pool = cfg.out_pool
-    xf = (L.PIX_RELU if cfg.in_relu else 0) | (L.PIX_UPSAMPLE if cfg.in_upsample else 0)
-    return conv2d_wgrad_raw(x, dy, bank.dwt(slot, rt), Cin, rt.rows_pad, cfg.R, cfg.S, Ho, Wo, cfg.stride, cfg.pad_h, cfg.pad_w, xf,
-                            L.PIX_UPSAMPLE if pool else 0, alpha=0.25 if pool else 1.0, dbias=dbias)
+    Ho, Wo = cfg.out_hw(Hs, Ws)
+    return conv2d_wgrad_raw(x, dy, bank.dwt(slot, rt), Cin, rt.rows_pad, cfg.R, cfg.S, Ho, Wo, cfg.stride, cfg.pad_h, cfg.pad_w, cfg.pix_flags(),
+                            L.PIX_UPSAMPLE if cfg.out_pool else 0, alpha=cfg.scale, dbias=dbias)
 
 
 def _conv_dgrad(dy, x, rt, slot, cfg, res=None):
@@ -112,7 +123,7 @@ def _conv_dgrad(dy, x, rt, slot, cfg, res=None):
     # dy has rows_pad channels and the dgrad image is [cin_pad][R][S][rows_pad] (zero outside the real weights): the padded
     # channels ride along so the 16-byte loaders apply; dx comes out with cin_pad channels like x
     return conv2d_raw(dy, bank.w_dgrad(slot, rt), rt.rows_pad, Cin, cfg.R, cfg.S, 1, cfg.R - 1 - cfg.pad_h, cfg.S - 1 - cfg.pad_w, pf, ef,
-                      mask=x if cfg.in_relu else None, res=res, alpha=0.25 if pool else 1.0, ldx=dy.shape[3])
+                      mask=x if cfg.in_relu else None, res=res, alpha=cfg.scale, ldx=dy.shape[3])
 
 
 class ConvDgradFn(torch.autograd.Function):
@@ -140,18 +151,15 @@ class ConvDgradFn(torch.autograd.Function):
             L.call("sg_relu_mask", L.dt(t), L.ptr(t), L.ptr(x), L.ptr(m), t.numel(), L.stream())
             t = m
         N, Hs, Ws, Cin = x.shape
-        up = 2 if cfg.in_upsample else 1
-        Ho = (Hs * up + 2 * cfg.pad_h - cfg.R) // cfg.stride + 1
-        Wo = (Ws * up + 2 * cfg.pad_w - cfg.S) // cfg.stride + 1
-        pool = cfg.out_pool
+        Ho, Wo = cfg.out_hw(Hs, Ws)
         g_dy = None
         if ctx.needs_input_grad[0]:
             # (rows_pad: the zero rows of a padded weight image -- theta / phi of SelfAttention, the RGB layer -- ride along as in the first-order launches)
             g_dy = conv2d_raw(t, bank.w_fwd(slot, rt), Cin, rt.rows_pad, cfg.R, cfg.S, cfg.stride, cfg.pad_h, cfg.pad_w,
-                              L.PIX_UPSAMPLE if cfg.in_upsample else 0, L.EPI_POOL if pool else 0, alpha=0.25 if pool else 1.0)
+                              L.PIX_UPSAMPLE if cfg.in_upsample else 0, cfg.epi_flags(), alpha=cfg.scale)
         if ctx.needs_input_grad[2]:
             conv2d_wgrad_raw(t, dy, bank.dwt(slot, rt), Cin, rt.rows_pad, cfg.R, cfg.S, Ho, Wo, cfg.stride, cfg.pad_h, cfg.pad_w,
-                             L.PIX_UPSAMPLE if cfg.in_upsample else 0, L.PIX_UPSAMPLE if pool else 0, alpha=0.25 if pool else 1.0)
+                             L.PIX_UPSAMPLE if cfg.in_upsample else 0, L.PIX_UPSAMPLE if cfg.out_pool else 0, alpha=cfg.scale)
         return g_dy, None, None, None, None, None
 
 
@@ -201,13 +209,6 @@ class ConvFn(torch.autograd.Function):
             dx = ConvDgradFn.apply(dy, x, ctx.weight, rt, slot, cfg) if ctx.needs_input_grad[0] else None
             return dx, None, None, (dy if ctx.has_res else None), None, None, None, None
         dy = _c(dy)
-        N, Hs, Ws, Cin = x.shape
-        up = 2 if cfg.in_upsample else 1
-        Hin, Win = Hs * up, Ws * up
-        Ho = (Hin + 2 * cfg.pad_h - cfg.R) // cfg.stride + 1
-        Wo = (Win + 2 * cfg.pad_w - cfg.S) // cfg.stride + 1
-        pool = cfg.out_pool
-        scale = 0.25 if pool else 1.0
         dx = None
         skip_dx = ctx.link.take() if ctx.link is not None else None     # the skip path's gradient w.r.t. this same input (GradLink)
         if ctx.needs_input_grad[0]:
@@ -247,10 +248,8 @@ class ConvSkipFn(torch.autograd.Function):
         _tick()
         # (cfg0.in_relu may differ from cfg2.in_relu: the first discriminator block's skip reads the image itself, big_resnet.py:177-192)
         assert cfg2.R == 3 and cfg0.R == 1 and cfg2.out_pool == cfg0.out_pool and not cfg2.in_upsample and (cfg0.in_relu == cfg2.in_relu or not cfg0.in_relu)
-        pf = L.PIX_RELU if cfg2.in_relu else 0
+        pf, ef, al = cfg2.pix_flags(), cfg2.epi_flags(), cfg2.scale      # (cfg2.in_upsample is False: pf is the ReLU flag alone)
         same_relu = cfg0.in_relu == cfg2.in_relu
-        ef = L.EPI_POOL if cfg2.out_pool else 0
-        al = 0.25 if cfg2.out_pool else 1.0
         y = None
         plain = rt2.rows_pad == rt2.rows and rt0.rows_pad == rt0.rows and b2 is not None and b0 is not None
         # measured (tools/skip_bench.py, profiles/r03_skip_bench_c.txt): the fused launch wins from 16 x 16 outputs up (0.01-0.30 ms per block
@@ -268,8 +267,7 @@ class ConvSkipFn(torch.autograd.Function):
                              x2=x, w2q_ptr=bank.w_quad(slot, rt0, 5 if rt0.cin_pad == 8 else 4), bias2=b0, x2_norelu=not same_relu)
         if y is None:
             hh = _conv_fwd(h, rt2, slot, cfg2, b2)
-            pf0 = (L.PIX_RELU if cfg0.in_relu else 0) | (L.PIX_UPSAMPLE if cfg0.in_upsample else 0)
-            y = conv2d_raw(x, bank.w_fwd(slot, rt0), x.shape[3], rt0.rows_pad, 1, 1, 1, 0, 0, pf0, ef, bias=b0, res=hh, alpha=al)
+            y = conv2d_raw(x, bank.w_fwd(slot, rt0), x.shape[3], rt0.rows_pad, 1, 1, 1, 0, 0, cfg0.pix_flags(), ef, bias=b0, res=hh, alpha=al)
         ctx.save_for_backward(h, x)
         ctx.rt2, ctx.rt0, ctx.slot, ctx.cfg2, ctx.cfg0 = rt2, rt0, slot, cfg2, cfg0
         ctx.w2, ctx.b2, ctx.w0, ctx.b0 = w2, b2, w0, b0
@@ -297,15 +295,10 @@ class ConvSkipFn(torch.autograd.Function):
             shared_db = zeros_small(rt2.rows, torch.float32, dy.device)
         for inp, rt, cfg, w_i, b_i, wp, bp in ((h, rt2, cfg2, 2, 3, ctx.w2, ctx.b2), (x, rt0, cfg0, 4, 5, ctx.w0, ctx.b0)):
             k = 0 if inp is h else 1
-            N, Hs, Ws, Cin = inp.shape
-            up = 2 if cfg.in_upsample else 1
-            Ho, Wo = Hs * up, Ws * up      # 3x3 pad 1 / 1x1 pad 0, stride 1
-            pool = cfg.out_pool
             outs.append(_conv_dgrad(dy, inp, rt, slot, cfg) if ctx.needs_input_grad[k] else None)
             want_db = bp is not None and ctx.needs_input_grad[b_i]
             db_done = False
             if ctx.needs_input_grad[w_i]:
-                xf = (L.PIX_RELU if cfg.in_relu else 0) | (L.PIX_UPSAMPLE if cfg.in_upsample else 0)
                 g = ensure_grad(bp) if (want_db and rt.rows_pad == rt.rows) else None
                 if k == 0 and shared_db is not None:
                     g = shared_db
