@@ -8,10 +8,16 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
-from util import check
+from util import check, engine_launches, one_launch
 from test_kernels_gpu import rnd, nhwc, nchw, _conv_ref
 
 pytestmark = pytest.mark.gpu
+
+
+def _wgrad_tile_engine(Cin, Cout, R, K):
+    """the weight-gradient engine of a bf16 power-of-two-image problem that neither the streaming nor the halo kernel takes, no switch set: the tile kernel from
+    64 filter-row elements, 64 couts and 4096 pixels on (csrc/conv_wgrad.hip wgrad_v2_ok), the generic engine below"""
+    return "wgrad_v2" if R * R * Cin >= 64 and Cout >= 64 and K >= 4096 else "wgrad_gemm"
 
 CASES = [
     # N, Cin, Cout, H, R, relu, up, pool
@@ -27,7 +33,8 @@ CASES = [
     (2, 48, 96, 16, 3, True, True, False),
     (2, 64, 64, 16, 3, False, False, False),      # cout count no tile divides (64 on the 96-wide tile: weight rows >= 64 zero-filled, tail chunks not stored)
     (3, 96, 160, 17, 1, False, False, False),     # InceptionV3-like: 17 x 17 images (not a power of two), 160 couts on the 192-wide tile
-    (2, 64, 320, 8, 3, True, False, False),       # 320 couts: two tiles of 192, the second one 2/3 full
+    (2, 64, 320, 8, 3, True, False, False),       # 320 couts at J = 128: fewer than the 256 pixels conv_v2 asks for, the forced arm runs the generic engine too
+    (8, 64, 320, 8, 3, True, False, False),       # 320 couts: two tiles of 192, the second one 2/3 full (J = 512)
 ]
 
 
@@ -49,11 +56,12 @@ def test_conv_v2_matches_reference_and_v1(sg, case):
     pf = (L.PIX_RELU if relu else 0) | (L.PIX_UPSAMPLE if up else 0)
     ef = L.EPI_POOL if pool else 0
     outs = {}
+    v2 = "v2" if N * Ho * Ho >= 256 else "gemm"
     for mode in ("force", "0"):
         os.environ["SG_CONV_V2"] = mode
-        y = F.conv2d_raw(xd, wd.data_ptr(), Cin, Cout, R, R, 1, pad, pad, pf, ef, bias=bias.to(d), res=nhwc(res).to(d),
-                         alpha=0.25 if pool else 1.0)
-        torch.cuda.synchronize()
+        with one_launch(v2 if mode == "force" else "gemm", f"conv v2={mode} {case}"):
+            y = F.conv2d_raw(xd, wd.data_ptr(), Cin, Cout, R, R, 1, pad, pad, pf, ef, bias=bias.to(d), res=nhwc(res).to(d),
+                             alpha=0.25 if pool else 1.0)
         outs[mode] = y.float().cpu()
     os.environ.pop("SG_CONV_V2", None)
     check(f"conv v2 {case}", nchw(outs["force"]), yref, 4e-3)
@@ -67,9 +75,9 @@ def test_conv_v2_matches_reference_and_v1(sg, case):
     wdg = w.flip(2, 3).permute(1, 2, 3, 0).contiguous().to(d)
     if Cin % 96 == 0 or Cin % 128 == 0:
         os.environ["SG_CONV_V2"] = "force"
-        dx = F.conv2d_raw(nhwc(gy).to(d), wdg.data_ptr(), Cout, Cin, R, R, 1, R - 1 - pad, R - 1 - pad, L.PIX_UPSAMPLE if pool else 0,
-                          L.EPI_POOL if up else 0, mask=xd if relu else None, alpha=0.25 if pool else 1.0)
-        torch.cuda.synchronize()
+        with one_launch(v2, f"conv v2 dgrad {case}"):
+            dx = F.conv2d_raw(nhwc(gy).to(d), wdg.data_ptr(), Cout, Cin, R, R, 1, R - 1 - pad, R - 1 - pad, L.PIX_UPSAMPLE if pool else 0,
+                              L.EPI_POOL if up else 0, mask=xd if relu else None, alpha=0.25 if pool else 1.0)
         os.environ.pop("SG_CONV_V2", None)
         check(f"conv v2 dgrad {case}", nchw(dx.float().cpu()), xr.grad, 4e-3)
 
@@ -83,7 +91,7 @@ V3_CASES = [
     (2, 128, 96, 8, False, True, True),         # upsample + pooling
     (8, 64, 96, 8, False, False, False),        # 8x8 images: a tile spans four images
     (5, 64, 96, 8, True, False, False),         # J = 320: partial last tile
-    (3, 72, 96, 16, False, False, False),       # C = 72
+    (3, 72, 96, 16, False, False, False),       # C = 72: conv_v3 takes whole 32-channel half slices only (C = 96 and C = 160 in this table), so both arms run conv_v2
     (5, 64, 128, 16, True, False, False),       # 128-wide cout tile
     (8, 96, 96, 128, True, False, True),        # the 512-pixel tile configuration (J = 131072), as D's first block
     (2, 384, 192, 8, True, False, False),       # six slices through the three-weight-buffer loop (cross-tap fragment prefetch)
@@ -91,7 +99,8 @@ V3_CASES = [
     (1, 192, 384, 16, False, True, False),      # two cout tiles, upsample on load, three weight buffers
     (16, 64, 96, 4, True, False, False),        # 4x4 images (D's last blocks): a 256-pixel tile spans 16 images
     (8, 128, 96, 4, False, True, False),        # 4x4 source, upsampled to 8x8
-    (2, 96, 8, 32, False, False, False),        # narrow cout tile (G's RGB layer: 3 couts padded to 8), cout-tail guard of the epilogue
+    (2, 96, 8, 32, False, False, False),        # narrow cout tile (G's RGB layer: 3 couts padded to 8), cout-tail guard of the epilogue; its data gradient has 8
+                                                # input channels, fewer than the 64 of a slice: conv_v2
 ]
 
 
@@ -116,10 +125,12 @@ def test_conv_v3_matches_reference_and_v2(sg, case):
     ef = L.EPI_POOL if pool else 0
     outs = {}
     os.environ["SG_CONV_V4"] = "0"                     # (conv_v4.h would take some of these shapes first)
+    # conv_v2 asks for >= 256 output pixels and >= 32 couts: below, the comparison arm is the generic engine
+    eng = {"v3": "v3" if Cin % 32 == 0 else "v2", "v2": "v2" if N * Ho * Ho >= 256 and Cout >= 32 else "gemm"}
     for name, v3, v2 in (("v3", "force", "force"), ("v2", "0", "force")):
         os.environ["SG_CONV_V3"], os.environ["SG_CONV_V2"] = v3, v2
-        y = F.conv2d_raw(xd, wd.data_ptr(), Cin, Cout, 3, 3, 1, 1, 1, pf, ef, bias=bias.to(d), res=nhwc(res).to(d), alpha=0.25 if pool else 1.0)
-        torch.cuda.synchronize()
+        with one_launch(eng[name], f"conv {name} arm {case}"):
+            y = F.conv2d_raw(xd, wd.data_ptr(), Cin, Cout, 3, 3, 1, 1, 1, pf, ef, bias=bias.to(d), res=nhwc(res).to(d), alpha=0.25 if pool else 1.0)
         outs[name] = y.float().cpu()
     check(f"conv v3 {case}", nchw(outs["v3"])[sel], yref, 4e-3)
     check(f"conv v3 vs v2 {case}", outs["v3"], outs["v2"], 4e-3)
@@ -131,9 +142,9 @@ def test_conv_v3_matches_reference_and_v2(sg, case):
         y2.backward(gy[sel].double())
         wdg = w.flip(2, 3).permute(1, 2, 3, 0).contiguous().to(d)
         os.environ["SG_CONV_V3"], os.environ["SG_CONV_V2"] = "force", "force"
-        dx = F.conv2d_raw(nhwc(gy).to(d), wdg.data_ptr(), Cout, Cin, 3, 3, 1, 1, 1, L.PIX_UPSAMPLE if pool else 0,
-                          L.EPI_POOL if up else 0, mask=xd if relu else None, alpha=0.25 if pool else 1.0)
-        torch.cuda.synchronize()
+        with one_launch("v3" if Cout >= 64 else "v2", f"conv v3 dgrad {case}"):
+            dx = F.conv2d_raw(nhwc(gy).to(d), wdg.data_ptr(), Cout, Cin, 3, 3, 1, 1, 1, L.PIX_UPSAMPLE if pool else 0,
+                              L.EPI_POOL if up else 0, mask=xd if relu else None, alpha=0.25 if pool else 1.0)
         check(f"conv v3 dgrad {case}", nchw(dx.float().cpu())[sel], xr.grad, 4e-3)
     os.environ.pop("SG_CONV_V3", None)
     os.environ.pop("SG_CONV_V2", None)
@@ -149,7 +160,8 @@ V4_CASES = [
     (8, 32, 64, 8, False, False, False),        # 8x8 images: a tile spans four images; one slice
     (5, 64, 96, 8, True, False, False),         # J = 320: partial last tile
     (4, 96, 96, 128, True, False, True),        # W = 128: the tile is one pair of image rows (D's first block, pooled)
-    (4, 96, 96, 128, False, False, False),      # W = 128 raster
+    (4, 96, 96, 128, False, False, False),      # W = 128 raster; the data gradient (no bias, mask or residual; 4 x 16 strips of 8 rows = 64) goes to conv_rs96
+    (3, 96, 96, 128, False, False, False),      # ... 3 x 16 = 48 strips, fewer than conv_rs96 asks for: the W = 128 raster data gradient on conv_v4
     (2, 192, 96, 64, True, True, False),        # 192 -> 96 up @128^2 (G's last block)
     (16, 64, 96, 4, True, False, False),        # 4x4 images: a 256-pixel tile spans 16 images
     (2, 384, 192, 8, True, False, False),       # twelve slices (a deep layer through the same loop)
@@ -178,8 +190,9 @@ def test_conv_v4_matches_reference_and_v3(sg, case, monkeypatch):
     os.environ["SG_CONV_V3"], os.environ["SG_CONV_V2"] = "force", "force"
     for name, v4 in (("v4", "all"), ("v3", "0")):
         os.environ["SG_CONV_V4"] = v4
-        y = F.conv2d_raw(xd, wd.data_ptr(), Cin, Cout, 3, 3, 1, 1, 1, pf, ef, bias=bias.to(d), res=nhwc(res).to(d), alpha=0.25 if pool else 1.0)
-        torch.cuda.synchronize()
+        # (conv_v3 has no slice narrower than 64 channels: the 32-channel case is compared with conv_v2)
+        with one_launch("v4" if name == "v4" else "v3" if Cin >= 64 else "v2", f"conv {name} arm {case}"):
+            y = F.conv2d_raw(xd, wd.data_ptr(), Cin, Cout, 3, 3, 1, 1, 1, pf, ef, bias=bias.to(d), res=nhwc(res).to(d), alpha=0.25 if pool else 1.0)
         outs[name] = y.float().cpu()
     check(f"conv v4 {case}", nchw(outs["v4"])[sel], yref, 4e-3)
     check(f"conv v4 vs v3 {case}", outs["v4"], outs["v3"], 6e-3)       # two bf16-rounded results, each within 4e-3 of fp64
@@ -191,9 +204,11 @@ def test_conv_v4_matches_reference_and_v3(sg, case, monkeypatch):
         y2.backward(gy[sel].double())
         wdg = w.flip(2, 3).permute(1, 2, 3, 0).contiguous().to(d)
         os.environ["SG_CONV_V4"] = "all"
-        dx = F.conv2d_raw(nhwc(gy).to(d), wdg.data_ptr(), Cout, Cin, 3, 3, 1, 1, 1, L.PIX_UPSAMPLE if pool else 0,
-                          L.EPI_POOL if up else 0, mask=xd if relu else None, alpha=0.25 if pool else 1.0)
-        torch.cuda.synchronize()
+        # a plain 96 -> 96 problem on 128-pixel rows with >= 64 eight-row strips belongs to the row-streaming kernel, which stands in front of conv_v4
+        rs96 = Cin == 96 and Cout == 96 and H == 128 and not (relu or up or pool) and N * 16 >= 64
+        with one_launch("rs" if rs96 else "v4", f"conv v4 dgrad {case}"):
+            dx = F.conv2d_raw(nhwc(gy).to(d), wdg.data_ptr(), Cout, Cin, 3, 3, 1, 1, 1, L.PIX_UPSAMPLE if pool else 0,
+                              L.EPI_POOL if up else 0, mask=xd if relu else None, alpha=0.25 if pool else 1.0)
         check(f"conv v4 dgrad {case}", nchw(dx.float().cpu())[sel], xr.grad, 4e-3)
     os.environ.pop("SG_CONV_V3", None)
     os.environ.pop("SG_CONV_V2", None)
@@ -243,8 +258,9 @@ def test_conv_sk_matches_reference_and_v2(sg, case):
         outs = {}
         for name, sk in (("sk", "force"), ("old", "0")):
             os.environ["SG_CONV_SK"] = sk
-            y = F.conv2d_raw(xd, wd.data_ptr(), Cin, Cout, R, R, 1, pad, pad, pf, ef, alpha=al, **kw)
-            torch.cuda.synchronize()
+            # (without the streaming kernel these test-sized problems have too few tiles for any tile kernel: the generic engine)
+            with one_launch("sk" if name == "sk" else "gemm", f"conv sk={sk} {what} {case}"):
+                y = F.conv2d_raw(xd, wd.data_ptr(), Cin, Cout, R, R, 1, pad, pad, pf, ef, alpha=al, **kw)
             outs[name] = y.float().cpu()
         os.environ.pop("SG_CONV_SK", None)
         yref = _conv_ref(x, w, 1, pad, relu, up, pool, bias if what != "mask" else None, res if what == "res" else None)
@@ -260,15 +276,16 @@ def test_conv_sk_full_size_stem_and_skip(sg):
     from studiogan_amd import functional as F, _lib as L
     d = torch.device("cuda:0")
     dt = torch.bfloat16
-    for (N, Cin, Cout, H, R, pool) in ((32, 8, 96, 128, 3, False), (32, 96, 192, 64, 1, True), (7, 96, 48, 64, 1, False)):
+    # last column: the engine without the streaming kernel (48 couts pad to no conv_v2 tile: generic engine)
+    for (N, Cin, Cout, H, R, pool, old) in ((32, 8, 96, 128, 3, False, "v2"), (32, 96, 192, 64, 1, True, "v2"), (7, 96, 48, 64, 1, False, "gemm")):
         x = rnd((N, H, H, Cin), dt, 51).to(d)
         w = rnd((Cout, R, R, Cin), dt, 52, 0.1).to(d)
         bias = rnd((Cout,), torch.float32, 53).to(d)
         outs = {}
         for name, sk in (("sk", "force"), ("old", "0")):
             os.environ["SG_CONV_SK"] = sk
-            y = F.conv2d_raw(x, w.data_ptr(), Cin, Cout, R, R, 1, R // 2, R // 2, 0, L.EPI_POOL if pool else 0, bias=bias, alpha=0.25 if pool else 1.0)
-            torch.cuda.synchronize()
+            with one_launch("sk" if name == "sk" else old, f"conv sk={sk} full size {(N, Cin, Cout, H, R, pool)}"):
+                y = F.conv2d_raw(x, w.data_ptr(), Cin, Cout, R, R, 1, R // 2, R // 2, 0, L.EPI_POOL if pool else 0, bias=bias, alpha=0.25 if pool else 1.0)
             outs[name] = y.float().cpu()
         os.environ.pop("SG_CONV_SK", None)
         check(f"conv sk full size {(N, Cin, Cout, H, R, pool)}", outs["sk"], outs["old"], 4e-3)
@@ -311,8 +328,8 @@ def test_wgrad_v2_matches_reference_and_v1(sg, case):
         os.environ["SG_CONV_V2"] = mode
         for splits in (0, 3):
             dw = torch.zeros((Cout, R, R, Cin), dtype=torch.float32, device=d)
-            F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, R, R, Ho, Ho, 1, pad, pad, xf, gf, alpha=0.25 if pool else 1.0, splits=splits)
-            torch.cuda.synchronize()
+            with one_launch("wgrad_v2" if mode == "force" else "wgrad_gemm", f"wgrad v2={mode} splits={splits} {case}"):
+                F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, R, R, Ho, Ho, 1, pad, pad, xf, gf, alpha=0.25 if pool else 1.0, splits=splits)
             outs[(mode, splits)] = dw.cpu()
             check(f"wgrad {mode} splits={splits} {case}", dw.cpu().permute(0, 3, 1, 2), wr.grad, 2e-3)
     os.environ.pop("SG_CONV_V2", None)
@@ -359,13 +376,14 @@ def test_wgrad_sk_matches_reference_and_tile_kernels(sg, case):
     for mode in ("1", "0"):
         os.environ["SG_WGRAD_SK"] = mode
         dw = torch.zeros((Cout, R, R, Cin), dtype=torch.float32, device=d)
-        F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, R, R, Ho, Ho, 1, pad, pad, xf, gf, alpha=0.25 if pool else 1.0)
-        torch.cuda.synchronize()
+        eng = "wgrad_sk" if mode == "1" else _wgrad_tile_engine(Cin, Cout, R, N * Ho * Ho)
+        with one_launch(eng, f"wgrad sk={mode} {case}"):
+            F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, R, R, Ho, Ho, 1, pad, pad, xf, gf, alpha=0.25 if pool else 1.0)
         outs[mode] = dw.cpu().clone()
         check(f"wgrad sk={mode} {case}", dw.cpu().permute(0, 3, 1, 2), wr.grad, 2e-3)
         # accumulation into dw (acml_steps > 1, shared weights) and the device-side scale (attention gate): dw += 0.7 * dW
-        F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, R, R, Ho, Ho, 1, pad, pad, xf, gf, alpha=0.25 if pool else 1.0, alpha_ptr=sig)
-        torch.cuda.synchronize()
+        with one_launch(eng, f"wgrad sk={mode} accumulate {case}"):
+            F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, R, R, Ho, Ho, 1, pad, pad, xf, gf, alpha=0.25 if pool else 1.0, alpha_ptr=sig)
         check(f"wgrad sk={mode} accumulate {case}", dw.cpu().permute(0, 3, 1, 2), 1.7 * wr.grad, 2e-3)
     os.environ.pop("SG_WGRAD_SK", None)
     check(f"wgrad sk vs tile kernels {case}", outs["1"], outs["0"], 1e-4)
@@ -384,8 +402,8 @@ def test_wgrad_sk_full_size_layers(sg):
         for mode in ("1", "0"):
             os.environ["SG_WGRAD_SK"] = mode
             dw = torch.zeros((Cout, R, R, Cin), dtype=torch.float32, device=d)
-            F.conv2d_wgrad_raw(x, gy, dw.data_ptr(), Cin, Cout, R, R, H, H, 1, R // 2, R // 2)
-            torch.cuda.synchronize()
+            with one_launch("wgrad_sk" if mode == "1" else _wgrad_tile_engine(Cin, Cout, R, N * H * H), f"wgrad sk={mode} full size {(N, Cin, Cout, H, R)}"):
+                F.conv2d_wgrad_raw(x, gy, dw.data_ptr(), Cin, Cout, R, R, H, H, 1, R // 2, R // 2)
             outs[mode] = dw.cpu()
         os.environ.pop("SG_WGRAD_SK", None)
         check(f"wgrad sk full size {(N, Cin, Cout, H, R)}", outs["1"], outs["0"], 2e-3)
@@ -429,20 +447,21 @@ def test_wgrad_v3_matches_reference_and_v2(sg, case):
     outs = {}
     for mode in ("force", "0"):
         os.environ["SG_WGRAD_V3"] = mode
+        eng = "wgrad_v3" if mode == "force" else _wgrad_tile_engine(Cin, Cout, R, N * Ho * Ho)
         for splits in (0, 3):
             dw = torch.zeros((Cout, R, R, Cin), dtype=torch.float32, device=d)
-            F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, R, R, Ho, Ho, 1, pad, pad, xf, gf, alpha=0.25 if pool else 1.0, splits=splits)
-            torch.cuda.synchronize()
+            with one_launch(eng, f"wgrad v3={mode} splits={splits} {case}"):
+                F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, R, R, Ho, Ho, 1, pad, pad, xf, gf, alpha=0.25 if pool else 1.0, splits=splits)
             outs[(mode, splits)] = dw.cpu().clone()
             check(f"wgrad v3={mode} splits={splits} {case}", dw.cpu().permute(0, 3, 1, 2), wr.grad, 2e-3)
-        F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, R, R, Ho, Ho, 1, pad, pad, xf, gf, alpha=0.25 if pool else 1.0, alpha_ptr=sig, splits=3)
-        torch.cuda.synchronize()
+        with one_launch(eng, f"wgrad v3={mode} accumulate {case}"):
+            F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, R, R, Ho, Ho, 1, pad, pad, xf, gf, alpha=0.25 if pool else 1.0, alpha_ptr=sig, splits=3)
         check(f"wgrad v3={mode} accumulate {case}", dw.cpu().permute(0, 3, 1, 2), 1.7 * wr.grad, 2e-3)
         # bias gradient riding along (column sums of the STORED dy -- the pooled one is read four times and scaled back), accumulating
         db = torch.full((Cout,), 0.5, dtype=torch.float32, device=d)
         dw2 = torch.zeros((Cout, R, R, Cin), dtype=torch.float32, device=d)
-        fused = F.conv2d_wgrad_raw(xd, gyd, dw2.data_ptr(), Cin, Cout, R, R, Ho, Ho, 1, pad, pad, xf, gf, alpha=0.25 if pool else 1.0, dbias=db)
-        torch.cuda.synchronize()
+        with one_launch(eng, f"wgrad v3={mode} with bias gradient {case}"):
+            fused = F.conv2d_wgrad_raw(xd, gyd, dw2.data_ptr(), Cin, Cout, R, R, Ho, Ho, 1, pad, pad, xf, gf, alpha=0.25 if pool else 1.0, dbias=db)
         assert fused == (mode == "force")
         if fused:
             check(f"wgrad v3 fused bias gradient {case}", db.cpu().double(), 0.5 + gy.double().sum((0, 2, 3)), 2e-3)
@@ -471,8 +490,8 @@ def test_wgrad_v3_full_size_layers(sg):
         for mode in ("1", "0"):
             os.environ["SG_WGRAD_V3"] = mode
             dw = torch.zeros((Cout, 3, 3, Cin), dtype=torch.float32, device=d)
-            F.conv2d_wgrad_raw(x, gy, dw.data_ptr(), Cin, Cout, 3, 3, H, H, 1, 1, 1, xf, gf)
-            torch.cuda.synchronize()
+            with one_launch("wgrad_v3" if mode == "1" else "wgrad_v2", f"wgrad v3={mode} full size {(N, Cin, Cout, H, xf, gf)}"):
+                F.conv2d_wgrad_raw(x, gy, dw.data_ptr(), Cin, Cout, 3, 3, H, H, 1, 1, 1, xf, gf)
             outs[mode] = dw.cpu()
         os.environ.pop("SG_WGRAD_V3", None)
         check(f"wgrad v3 full size {(N, Cin, Cout, H, xf, gf)}", outs["1"], outs["0"], 2e-3)
@@ -498,8 +517,8 @@ def test_wgrad_v3_lean_matches_round4_kernel(sg, case, monkeypatch):
         monkeypatch.setenv("SG_WGRAD_V3_LEAN", lean)
         dw = torch.zeros((Cout, 3, 3, Cin), dtype=torch.float32, device=d)
         db = torch.zeros((Cout,), dtype=torch.float32, device=d)
-        fused = F.conv2d_wgrad_raw(x, gy, dw.data_ptr(), Cin, Cout, 3, 3, Ho, Ho, 1, 1, 1, xf, gf, alpha=0.5, dbias=db)
-        torch.cuda.synchronize()
+        with one_launch("wgrad_v3", f"wgrad v3 lean={lean} {case}"):
+            fused = F.conv2d_wgrad_raw(x, gy, dw.data_ptr(), Cin, Cout, 3, 3, Ho, Ho, 1, 1, 1, xf, gf, alpha=0.5, dbias=db)
         assert fused
         outs[lean] = (dw.cpu(), db.cpu())
     assert torch.equal(outs["0"][0], outs["1"][0]), case
@@ -540,11 +559,13 @@ def test_conv_fused_skip_matches_reference_and_two_launches(sg, case):
     pf = L.PIX_RELU if relu else 0
     ef = L.EPI_POOL if pool else 0
     al = 0.25 if pool else 1.0
-    y = F.conv2d_skip_raw(hd, wd.data_ptr(), C, Cout, xd, w0d.data_ptr(), C2, up2, pf, ef, bias=b.to(d), bias2=b0.to(d), alpha=al)
+    with one_launch("v4_skip", f"fused skip {case}"):
+        y = F.conv2d_skip_raw(hd, wd.data_ptr(), C, Cout, xd, w0d.data_ptr(), C2, up2, pf, ef, bias=b.to(d), bias2=b0.to(d), alpha=al)
     assert y is not None, "the fused kernel must take this shape"
-    hh = F.conv2d_raw(hd, wd.data_ptr(), C, Cout, 3, 3, 1, 1, 1, pf, ef, bias=b.to(d), alpha=al)
-    y2 = F.conv2d_raw(xd, w0d.data_ptr(), C2, Cout, 1, 1, 1, 0, 0, pf | (L.PIX_UPSAMPLE if up2 else 0), ef, bias=b0.to(d), res=hh, alpha=al)
-    torch.cuda.synchronize()
+    with engine_launches() as two:        # the two launches it replaces, each on the engine it gets by default: two launches, neither of them the fused kernel
+        hh = F.conv2d_raw(hd, wd.data_ptr(), C, Cout, 3, 3, 1, 1, 1, pf, ef, bias=b.to(d), alpha=al)
+        y2 = F.conv2d_raw(xd, w0d.data_ptr(), C2, Cout, 1, 1, 1, 0, 0, pf | (L.PIX_UPSAMPLE if up2 else 0), ef, bias=b0.to(d), res=hh, alpha=al)
+    assert sum(two.values()) == 2 and two["v4_skip"] == 0 and two["other"] == 0, two
     check(f"fused skip {case}", nchw(y.float().cpu()), yref, 4e-3)
     check(f"two launches {case}", nchw(y2.float().cpu()), yref, 6e-3)
     check(f"fused vs two launches {case}", y.float().cpu(), y2.float().cpu(), 1e-2)   # two bf16 results, the unfused one rounded twice
@@ -581,9 +602,10 @@ def test_conv_epilogue_mask_and_residual(sg, case, monkeypatch):
     pf = L.PIX_UPSAMPLE if up else 0
     ef = L.EPI_POOL if pool else 0
     wd = w.permute(0, 2, 3, 1).contiguous().to(d)
-    y = F.conv2d_raw(nhwc(x).to(d), wd.data_ptr(), Cin, Cout, R, R, 1, pad, pad, pf, ef,
-                     mask=nhwc(m).to(d), res=nhwc(res).to(d), alpha=0.25 if pool else 1.0)
-    torch.cuda.synchronize()
+    eng = next((e for e in ("v4", "v3", "v2") if env.get("SG_CONV_" + e.upper()) == "force"), "gemm")
+    with one_launch(eng, f"mask + residual {case[:7]}"):
+        y = F.conv2d_raw(nhwc(x).to(d), wd.data_ptr(), Cin, Cout, R, R, 1, pad, pad, pf, ef,
+                         mask=nhwc(m).to(d), res=nhwc(res).to(d), alpha=0.25 if pool else 1.0)
     check(f"mask + residual {case[:7]}", nchw(y.float().cpu()), yref, 4e-3)
 
 
@@ -591,9 +613,13 @@ STRIDE2_CASES = [
     # N, Cin, Cout, H, R, pad      -- stride-2 convolutions on the conv_v2 tile kernels (InceptionV3's reduction layers)
     (4, 96, 96, 35, 3, 0),          # Mixed_6a.branch3x3dbl_3: 35 -> 17, valid
     (2, 288, 384, 35, 3, 0),        # Mixed_6a.branch3x3
+    # the next three have fewer than the 256 output pixels conv_v2 asks for (192, 128, 128): both arms run the generic engine; their siblings below have >= 256
     (3, 192, 320, 17, 3, 0),        # Mixed_7a.branch3x3_2: 17 -> 8, cout count no tile divides
     (2, 64, 128, 16, 3, 1),         # padded, even size (DCGAN-style 4x4 s2 has its own transposed path; this is the plain strided form)
     (2, 64, 96, 16, 1, 0),          # 1x1 stride 2
+    (5, 192, 320, 17, 3, 0),        # Mixed_7a.branch3x3_2 on conv_v2: J = 320, a partial second tile, 320 couts on two 192-wide tiles
+    (4, 64, 128, 16, 3, 1),         # padded, even size: J = 256
+    (6, 64, 96, 16, 1, 0),          # 1x1 stride 2: J = 384
 ]
 
 
@@ -611,8 +637,9 @@ def test_conv_v2_stride2_matches_reference_and_generic(sg, case, monkeypatch):
     outs = {}
     for mode in ("force", "0"):
         monkeypatch.setenv("SG_CONV_V2", mode)
-        y = F.conv2d_raw(xd, wd.data_ptr(), Cin, Cout, R, R, 2, pad, pad, 0, 0, bias=bias.to(d))
-        torch.cuda.synchronize()
+        Ho = (H + 2 * pad - R) // 2 + 1
+        with one_launch("v2" if mode == "force" and N * Ho * Ho >= 256 else "gemm", f"conv v2={mode} stride 2 {case}"):
+            y = F.conv2d_raw(xd, wd.data_ptr(), Cin, Cout, R, R, 2, pad, pad, 0, 0, bias=bias.to(d))
         outs[mode] = y.float().cpu()
     assert tuple(nchw(outs["force"]).shape) == tuple(yref.shape)
     check(f"conv v2 stride 2 {case}", nchw(outs["force"]), yref, 4e-3)
@@ -653,13 +680,14 @@ def test_conv_rs_matches_reference_and_halo_kernel(sg, case, monkeypatch):
     pf = L.PIX_RELU if relu_in else 0
     ef = L.EPI_RELU if relu_out else 0
     outs = {}
+    monkeypatch.setenv("SG_CONV_V3", "force")       # (at these batch sizes the halo kernel takes the problem only when forced; the row-streaming kernel stands in front of it)
     for mode in ("force", "0"):
         monkeypatch.setenv("SG_CONV_RS", mode)
         if sh:
             monkeypatch.setenv("SG_CONV_RS_SH", str(sh))
         before = L.lib().sg_conv_rs_launches()
-        y = F.conv2d_raw(xd, wd.data_ptr(), Cin, Cout, 3, 3, 1, 1, 1, pf, ef, bias=None if bias is None else bias.to(d), alpha=alpha)
-        torch.cuda.synchronize()
+        with one_launch("rs" if mode == "force" else "v3", f"conv rs={mode} {case}"):
+            y = F.conv2d_raw(xd, wd.data_ptr(), Cin, Cout, 3, 3, 1, 1, 1, pf, ef, bias=None if bias is None else bias.to(d), alpha=alpha)
         assert L.lib().sg_conv_rs_launches() - before == (1 if mode == "force" else 0), "the wrong engine took the problem"
         outs[mode] = y.float().cpu()
     check(f"conv rs {case}", nchw(outs["force"]), yref, 4e-3)
@@ -693,13 +721,14 @@ def test_conv_rs96_matches_reference_and_halo_kernel(sg, case, monkeypatch):
     pf = L.PIX_RELU if relu_in else 0
     ef = (L.EPI_POOL if pool else 0) | (L.EPI_RELU if relu_out else 0)
     outs = {}
+    monkeypatch.setenv("SG_CONV_V3", "force")       # (the halo kernel as the comparison arm at these batch sizes, as above)
     for mode in ("force", "0"):
         monkeypatch.setenv("SG_CONV_RS96", mode)
         if sh:
             monkeypatch.setenv("SG_CONV_RS_SH", str(sh))
         before = L.lib().sg_conv_rs_launches()
-        y = F.conv2d_raw(xd, wd.data_ptr(), Cc, Cc, 3, 3, 1, 1, 1, pf, ef, bias=None if bias is None else bias.to(d), alpha=0.25 if pool else 1.0)
-        torch.cuda.synchronize()
+        with one_launch("rs" if mode == "force" else "v3", f"conv rs96={mode} {case}"):
+            y = F.conv2d_raw(xd, wd.data_ptr(), Cc, Cc, 3, 3, 1, 1, 1, pf, ef, bias=None if bias is None else bias.to(d), alpha=0.25 if pool else 1.0)
         assert L.lib().sg_conv_rs_launches() - before == (1 if mode == "force" else 0), "the wrong engine took the problem"
         outs[mode] = y.float().cpu()
     check(f"conv rs96 {case}", nchw(outs["force"]), yref, 4e-3)

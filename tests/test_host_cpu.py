@@ -54,6 +54,25 @@ def test_abi_symbols_match_header():
     assert lib.sg_version() >= 1
 
 
+def test_engine_names_match_enum():
+    """tests/util.py engine_launches reports launches per SG_ENG_* id: its names follow the enum of csrc/common.h one for one, and
+    bench.py's table of the same ids has the same length, so a new engine cannot shift the ids unnoticed."""
+    import bench
+    from util import ENGINE_NAMES
+    src = open(os.path.join(ROOT, "pytorch-studiogan_amd", "csrc", "common.h")).read()
+    m = re.search(r"enum\s*\{\s*(SG_ENG_OTHER\s*=\s*0[^}]*)\}", src)
+    assert m, "SG_ENG_* enum not found in csrc/common.h"
+    ids = [t.split("=")[0].strip() for t in m.group(1).split(",") if t.strip()]
+    assert ids[-1] == "SG_ENG_COUNT" and all("=" not in t for t in m.group(1).split(",")[1:]), ids
+    ids = ids[:-1]
+    assert len(ids) == len(ENGINE_NAMES) == len(bench.ENGINES), (len(ids), len(ENGINE_NAMES), len(bench.ENGINES))
+    assert len(set(ENGINE_NAMES)) == len(ENGINE_NAMES)
+    for i, (c, n) in enumerate(zip(ids, ENGINE_NAMES)):
+        want = "other" if c == "SG_ENG_OTHER" else c[len("SG_ENG_"):].lower()
+        want = want[len("conv_"):] if want.startswith("conv_") else want
+        assert n == want, f"id {i}: {c} is named {n!r} in tests/util.py"
+
+
 def test_struct_layouts_match_c():
     """ctypes mirrors of the descriptor structs have the sizes the C compiler gives them."""
     import ctypes

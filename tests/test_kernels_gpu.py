@@ -6,7 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
-from util import check, tol_for
+from util import check, tol_for, one_launch
 
 pytestmark = pytest.mark.gpu
 
@@ -129,8 +129,9 @@ def test_conv_fwd_dgrad_wgrad(sg, dtype, case):
     yref = TF.conv2d(xr, wr, bias.double(), stride=stride, padding=(ph, pw))
     w_fwd = w.permute(0, 2, 3, 1).contiguous().to(d)      # [Cout][R][S][Cin]
     xd = nhwc(x).to(d)
-    y = F.conv2d_raw(xd, w_fwd.data_ptr(), Cin, Cout, R, S, stride, ph, pw, bias=bias.to(d))
-    torch.cuda.synchronize()
+    # (every problem of this table is below the size or outside the shape each bf16 fast path asks for: both types run the generic engine)
+    with one_launch("gemm", f"conv fwd {case}"):
+        y = F.conv2d_raw(xd, w_fwd.data_ptr(), Cin, Cout, R, S, stride, ph, pw, bias=bias.to(d))
     check(f"conv fwd {case}", nchw(y.float().cpu()), yref, tol)
     # backward references
     gy = rnd(tuple(yref.shape), dtype, 14)
@@ -139,19 +140,19 @@ def test_conv_fwd_dgrad_wgrad(sg, dtype, case):
     Ho, Wo = yref.shape[2], yref.shape[3]
     if stride == 1:
         w_dg = w.flip(2, 3).permute(1, 2, 3, 0).contiguous().to(d)  # [Cin][R'][S'][Cout]
-        dx = F.conv2d_raw(gyd, w_dg.data_ptr(), Cout, Cin, R, S, 1, R - 1 - ph, S - 1 - pw)
-        torch.cuda.synchronize()
+        with one_launch("gemm", f"conv dgrad {case}"):
+            dx = F.conv2d_raw(gyd, w_dg.data_ptr(), Cout, Cin, R, S, 1, R - 1 - ph, S - 1 - pw)
         check(f"conv dgrad {case}", nchw(dx.float().cpu()), xr.grad, tol)
     else:
         # strided convolution: data gradient = transposed gather over the UNflipped [Cin][R][S][Cout] image
         w_dg = w.permute(1, 2, 3, 0).contiguous().to(d)
-        dx = F.conv2d_raw(gyd, w_dg.data_ptr(), Cout, Cin, R, S, stride, ph, pw, L.PIX_TRANSPOSED, transposed_out_hw=(H, W))
-        torch.cuda.synchronize()
+        with one_launch("gemm", f"conv strided dgrad {case}"):
+            dx = F.conv2d_raw(gyd, w_dg.data_ptr(), Cout, Cin, R, S, stride, ph, pw, L.PIX_TRANSPOSED, transposed_out_hw=(H, W))
         check(f"conv strided dgrad {case}", nchw(dx.float().cpu()), xr.grad, tol)
     for no_tr in ([0, 1] if dtype == torch.bfloat16 else [0]):
         dw = torch.zeros((Cout, R, S, Cin), dtype=torch.float32, device=d)
-        F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, R, S, Ho, Wo, stride, ph, pw, no_tr=no_tr)
-        torch.cuda.synchronize()
+        with one_launch("wgrad_gemm", f"conv wgrad {case} no_tr={no_tr}"):
+            F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, R, S, Ho, Wo, stride, ph, pw, no_tr=no_tr)
         check(f"conv wgrad {case} no_tr={no_tr}", dw.cpu().permute(0, 3, 1, 2), wr.grad, tol)
 
 
@@ -231,19 +232,19 @@ def test_conv_transpose(sg, dtype, case):
     Ho, Wo = yref.shape[2], yref.shape[3]
     w_fwd = w.permute(1, 2, 3, 0).contiguous().to(d)        # [Cout][R][S][Cin], unflipped
     xd = nhwc(x).to(d)
-    y = F.conv2d_raw(xd, w_fwd.data_ptr(), Cin, Cout, R, R, stride, pad, pad, L.PIX_TRANSPOSED, bias=bias.to(d), transposed_out_hw=(Ho, Wo))
-    torch.cuda.synchronize()
+    with one_launch("gemm", f"deconv fwd {case}"):           # (the transposed gather exists on the generic engine only)
+        y = F.conv2d_raw(xd, w_fwd.data_ptr(), Cin, Cout, R, R, stride, pad, pad, L.PIX_TRANSPOSED, bias=bias.to(d), transposed_out_hw=(Ho, Wo))
     check(f"deconv fwd {case}", nchw(y.float().cpu()), yref, tol)
     gy = rnd(tuple(yref.shape), dtype, 24)
     yref.backward(gy.double())
     gyd = nhwc(gy).to(d)
     w_dg = w.permute(0, 2, 3, 1).contiguous().to(d)         # [Cin][R][S][Cout]
-    dx = F.conv2d_raw(gyd, w_dg.data_ptr(), Cout, Cin, R, R, stride, pad, pad)
-    torch.cuda.synchronize()
+    with one_launch("gemm", f"deconv dgrad {case}"):         # (a plain strided convolution, fewer than 256 output pixels)
+        dx = F.conv2d_raw(gyd, w_dg.data_ptr(), Cout, Cin, R, R, stride, pad, pad)
     check(f"deconv dgrad {case}", nchw(dx.float().cpu()), xr.grad, tol)
     dw = torch.zeros((Cin, R, R, Cout), dtype=torch.float32, device=d)   # roles of x and dy exchanged
-    F.conv2d_wgrad_raw(gyd, xd, dw.data_ptr(), Cout, Cin, R, R, H, W, stride, pad, pad)
-    torch.cuda.synchronize()
+    with one_launch("wgrad_gemm", f"deconv wgrad {case}"):
+        F.conv2d_wgrad_raw(gyd, xd, dw.data_ptr(), Cout, Cin, R, R, H, W, stride, pad, pad)
     check(f"deconv wgrad {case}", dw.cpu().permute(0, 3, 1, 2), wr.grad, tol)
 
 
@@ -269,20 +270,20 @@ def test_conv_fused_flags(sg, dtype):
         yref = _conv_ref(xr, wr, 1, 1, relu_in, up, pool, None, res)
         pf = (L.PIX_RELU if relu_in else 0) | (L.PIX_UPSAMPLE if up else 0)
         ef = L.EPI_POOL if pool else 0
-        y = F.conv2d_raw(xd, w_fwd.data_ptr(), Cin, Cout, 3, 3, 1, 1, 1, pf, ef, res=nhwc(res).to(d), alpha=0.25 if pool else 1.0)
-        torch.cuda.synchronize()
         tag = f"relu={relu_in} up={up} pool={pool}"
+        with one_launch("gemm", "conv fused fwd " + tag):      # (32 -> 96 channels at 8 x 8: the generic engine in both types)
+            y = F.conv2d_raw(xd, w_fwd.data_ptr(), Cin, Cout, 3, 3, 1, 1, 1, pf, ef, res=nhwc(res).to(d), alpha=0.25 if pool else 1.0)
         check("conv fused fwd " + tag, nchw(y.float().cpu()), yref, tol)
         gy = rnd(tuple(yref.shape), dtype, 24)
         yref.backward(gy.double())
         gyd = nhwc(gy).to(d)
-        dx = F.conv2d_raw(gyd, w_dg.data_ptr(), Cout, Cin, 3, 3, 1, 1, 1, L.PIX_UPSAMPLE if pool else 0, L.EPI_POOL if up else 0,
-                          mask=xd if relu_in else None, alpha=0.25 if pool else 1.0)
-        torch.cuda.synchronize()
+        with one_launch("gemm", "conv fused dgrad " + tag):
+            dx = F.conv2d_raw(gyd, w_dg.data_ptr(), Cout, Cin, 3, 3, 1, 1, 1, L.PIX_UPSAMPLE if pool else 0, L.EPI_POOL if up else 0,
+                              mask=xd if relu_in else None, alpha=0.25 if pool else 1.0)
         check("conv fused dgrad " + tag, nchw(dx.float().cpu()), xr.grad, tol)
         dw = torch.zeros((Cout, 3, 3, Cin), dtype=torch.float32, device=d)
-        F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, 3, 3, Ho, Ho, 1, 1, 1, pf, L.PIX_UPSAMPLE if pool else 0, alpha=0.25 if pool else 1.0)
-        torch.cuda.synchronize()
+        with one_launch("wgrad_gemm", "conv fused wgrad " + tag):
+            F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, 3, 3, Ho, Ho, 1, 1, 1, pf, L.PIX_UPSAMPLE if pool else 0, alpha=0.25 if pool else 1.0)
         check("conv fused wgrad " + tag, dw.cpu().permute(0, 3, 1, 2), wr.grad, tol)
 
 
@@ -300,10 +301,13 @@ def test_conv_large_splitk_and_tiles(sg, dtype):
     gy = rnd(tuple(yref.shape), dtype, 33)
     yref.backward(gy.float())
     xd, gyd = nhwc(x).to(d), nhwc(gy).to(d)
-    y = F.conv2d_raw(xd, w.permute(0, 2, 3, 1).contiguous().to(d).data_ptr(), Cin, Cout, 3, 3, 1, 1, 1)
+    wd = w.permute(0, 2, 3, 1).contiguous().to(d)
+    # forward: 32 tiles of 96 couts, below every bf16 kernel's tile floor -> generic engine; weight gradient: 4096 pixels and 864 x 192 -> the bf16 tile kernel
+    with one_launch("gemm", "conv fwd large"):
+        y = F.conv2d_raw(xd, wd.data_ptr(), Cin, Cout, 3, 3, 1, 1, 1)
     dw = torch.zeros((Cout, 3, 3, Cin), dtype=torch.float32, device=d)
-    F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, 3, 3, H, H, 1, 1, 1)
-    torch.cuda.synchronize()
+    with one_launch("wgrad_v2" if dtype == torch.bfloat16 else "wgrad_gemm", "conv wgrad large"):
+        F.conv2d_wgrad_raw(xd, gyd, dw.data_ptr(), Cin, Cout, 3, 3, H, H, 1, 1, 1)
     check("conv fwd large", nchw(y.float().cpu()), yref, tol)
     check("conv wgrad large", dw.cpu().permute(0, 3, 1, 2), wr.grad, tol)
 

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import quad_ref as Q
-from util import check
+from util import check, one_launch
 from test_kernels_gpu import rnd
 
 pytestmark = pytest.mark.gpu
@@ -77,8 +77,9 @@ def test_conv_q_matches_torch(sg, case, bj, monkeypatch):
     wq = torch.empty(Cout, 16, C, dtype=dt, device="cuda:0")
     w9d = _dev(w9)
     F.quad_pack_raw(w9d.data_ptr(), wq, form, Cout, C)
-    y = F.conv2d_q_raw(_dev(x), wq.data_ptr(), form, C, Cout, L.PIX_RELU if relu_in else 0, L.EPI_RELU if relu_out else 0,
-                       bias=None if bias is None else _dev(bias), res=None if res is None else _dev(res), mask=None if mask is None else _dev(mask))
+    with one_launch("q", f"conv_q {case}"):
+        y = F.conv2d_q_raw(_dev(x), wq.data_ptr(), form, C, Cout, L.PIX_RELU if relu_in else 0, L.EPI_RELU if relu_out else 0,
+                           bias=None if bias is None else _dev(bias), res=None if res is None else _dev(res), mask=None if mask is None else _dev(mask))
     assert y is not None, "the quad kernel refused an eligible problem"
     torch.cuda.synchronize()
     check(f"conv_q {case}", y.float().cpu(), ref, 6e-3)
@@ -112,7 +113,8 @@ def test_conv_q_data_gradients_match_autograd(sg):
         (dx,) = torch.autograd.grad(y, x, dy.float())
         wq = torch.empty(C, 16, Cout, dtype=dt, device="cuda:0")
         F.quad_pack_raw(wftd.data_ptr(), wq, 2 + form, C, Cout)
-        got = F.conv2d_q_raw(_dev(dy), wq.data_ptr(), 1 - form, Cout, C)
+        with one_launch("q", f"conv_q dgrad of form {form}"):
+            got = F.conv2d_q_raw(_dev(dy), wq.data_ptr(), 1 - form, Cout, C)
         assert got is not None
         torch.cuda.synchronize()
         check(f"conv_q dgrad of form {form}", got.float().cpu(), dx, 6e-3)
@@ -148,7 +150,8 @@ def test_wgrad_q_matches_autograd(sg, case):
         dwd = torch.zeros(Cout, 9, C, dtype=torch.float32, device="cuda:0")
         dwd[0, 0, 0] = 1.0                              # the kernel ACCUMULATES
         db = torch.zeros(Cout, dtype=torch.float32, device="cuda:0") if with_bias else None
-        ok = F.conv2d_q_wgrad_raw(_dev(x), _dev(dy), dwd.data_ptr(), form, C, Cout, L.PIX_RELU if relu else 0, dbias=db, splits=splits)
+        with one_launch("wgrad_q", f"wgrad_q {case} splits {splits}"):
+            ok = F.conv2d_q_wgrad_raw(_dev(x), _dev(dy), dwd.data_ptr(), form, C, Cout, L.PIX_RELU if relu else 0, dbias=db, splits=splits)
         assert ok, "the quad weight-gradient kernel refused an eligible problem"
         torch.cuda.synchronize()
         got = dwd.cpu().reshape(Cout, 3, 3, C)
@@ -174,7 +177,8 @@ def test_wgrad_q_lean_matches_round4_kernel(sg, case, monkeypatch):
         for splits in (0, 3):
             dwd = torch.zeros(Cout, 9, C, dtype=torch.float32, device="cuda:0")
             db = torch.zeros(Cout, dtype=torch.float32, device="cuda:0")
-            assert F.conv2d_q_wgrad_raw(x, dy, dwd.data_ptr(), form, C, Cout, L.PIX_RELU if relu else 0, alpha=0.5, dbias=db, splits=splits)
+            with one_launch("wgrad_q", f"wgrad_q lean={lean} {case} splits {splits}"):
+                assert F.conv2d_q_wgrad_raw(x, dy, dwd.data_ptr(), form, C, Cout, L.PIX_RELU if relu else 0, alpha=0.5, dbias=db, splits=splits)
             torch.cuda.synchronize()
             outs[(lean, splits)] = (dwd.cpu(), db.cpu())
     for splits in (0, 3):
@@ -221,8 +225,9 @@ def test_conv_q_fused_skip_matches_torch(sg, case, monkeypatch):
     w0q = (w0d.float() * 0.25).to(dt)
     if img:
         w0q = w0q.repeat(1, 4).contiguous()
-    y = F.conv2d_q_raw(_dev(h), wq.data_ptr(), L.Q_POOL, C, Cout, L.PIX_RELU if relu else 0, 0, bias=_dev(b2),
-                       x2=_dev(x), w2q_ptr=w0q.data_ptr(), bias2=_dev(b0), x2_norelu=img)
+    with one_launch("q_skip", f"conv_q fused skip {case}"):
+        y = F.conv2d_q_raw(_dev(h), wq.data_ptr(), L.Q_POOL, C, Cout, L.PIX_RELU if relu else 0, 0, bias=_dev(b2),
+                           x2=_dev(x), w2q_ptr=w0q.data_ptr(), bias2=_dev(b0), x2_norelu=img)
     assert y is not None
     torch.cuda.synchronize()
     check(f"conv_q fused skip {case}", y.float().cpu(), ref, 6e-3)
@@ -274,13 +279,15 @@ def test_conv_epilogue_bn_statistics(sg, kind, monkeypatch):
         x = rnd((N, Hl, Wl, C) if form == L.Q_UP else (N, 2 * Hl, 2 * Wl, C), dt, 503)
         wq = torch.empty(Cout, 16, C, dtype=dt, device="cuda:0")
         F.quad_pack_raw(w9d.data_ptr(), wq, form, Cout, C)
-        y = F.conv2d_q_raw(_dev(x), wq.data_ptr(), form, C, Cout, 0, 0, bias=_dev(bias), stats=True)
+        with one_launch("q", f"epilogue BN statistics {kind}"):
+            y = F.conv2d_q_raw(_dev(x), wq.data_ptr(), form, C, Cout, 0, 0, bias=_dev(bias), stats=True)
     else:
         x = rnd((N, 2 * Hl, 2 * Wl, C), dt, 503)
         x2 = rnd((N, Hl, Wl, 32), dt, 504)
         w0 = rnd((Cout, 32), dt, 505, 0.2)
         w0d = _dev(w0)
-        y = F.conv2d_skip_raw(_dev(x), w9d.data_ptr(), C, Cout, _dev(x2), w0d.data_ptr(), 32, True, 0, 0, bias=_dev(bias), bias2=_dev(bias), stats=True)
+        with one_launch("v4_skip", f"epilogue BN statistics {kind}"):
+            y = F.conv2d_skip_raw(_dev(x), w9d.data_ptr(), C, Cout, _dev(x2), w0d.data_ptr(), 32, True, 0, 0, bias=_dev(bias), bias2=_dev(bias), stats=True)
     assert y is not None and F._STATS_OFFER[0] is not None, "no statistics were offered"
     _, ptr, shape, st, rows, Cc, ver = F._STATS_OFFER[0]
     assert ptr == y.data_ptr() and Cc == Cout and ver == y._version

@@ -1,4 +1,6 @@
 """Shared helpers for the parity tests."""
+import contextlib
+import ctypes
 import json
 import os
 
@@ -6,6 +8,46 @@ import numpy as np
 import torch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+# short names of the convolution engine's kernel families, in the order of csrc/common.h's SG_ENG_* enum (tests/test_host_cpu.py checks the order against the header)
+ENGINE_NAMES = ("other", "sk", "rs", "v4", "v3", "v2", "gemm", "v4_skip", "q", "q_skip", "wgrad_sk", "wgrad_v3", "wgrad_v2", "wgrad_gemm", "wgrad_q")
+
+
+@contextlib.contextmanager
+def engine_launches():
+    """Which kernel family took each convolution launch made inside the block: yields a dict engine name -> launch count (every name of
+    ENGINE_NAMES, zeros included) that is filled when the block ends. Uses the library's launch profiler (bit 0: the contraction engine, quad
+    launches included); only convolution forward / data-gradient and weight-gradient launches carry a family tag, and a weight gradient's
+    split-K reduction is not a launch of its own here. The log holds 16384 launches."""
+    from studiogan_amd import _lib as L
+    counts = dict.fromkeys(ENGINE_NAMES, 0)
+    L.call("sg_prof_enable", 1)
+    try:
+        yield counts
+        torch.cuda.synchronize()
+        n = len(ENGINE_NAMES)
+        t = (ctypes.c_double * (n * 5))()
+        L.call("sg_prof_collect_tags", t, n)
+        for i, name in enumerate(ENGINE_NAMES):
+            counts[name] = int(t[i * 5])
+    finally:
+        torch.cuda.synchronize()
+        L.call("sg_prof_collect", (ctypes.c_double * 9)(), 3)      # drains the log
+        L.call("sg_prof_enable", 0)
+
+
+def launched(counts):
+    """the non-zero entries of an engine_launches() result"""
+    return {k: v for k, v in counts.items() if v}
+
+
+@contextlib.contextmanager
+def one_launch(engine, what=""):
+    """the block must make exactly one tagged convolution launch, of the family `engine`"""
+    with engine_launches() as counts:
+        yield counts
+    assert launched(counts) == {engine: 1}, f"{what}: expected one {engine} launch, the profiler saw {launched(counts)}"
 
 
 class Sampled:
