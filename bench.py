@@ -10,9 +10,14 @@ bf16 compute (fp32 master weights / statistics / optimizer), synthetic ImageNet-
 Weak scaling: every rank runs batch 256; gradients are all-reduced over RCCL once per update, G's batch norms are
 synchronised (one fp64 all-reduce per BN layer and direction).
 
-Prints ONE JSON line (rank 0): value = global images per second; roofline = achieved algorithmic TFLOP/s of the dominant
-kernel family (the MFMA implicit-GEMM convolution engine) measured live with hipEvents on the launch stream;
-cpu_baseline = the CPU oracle (restatement of the reference, oracle/restate.py) timed on the host cores at a reduced batch.
+Prints ONE JSON line (rank 0): value = global images per second of the timed steps. A plain run does what that figure needs and no more: set-up,
+warm-up, the timed steps, --dump-outputs, the line (roofline.dominant_kernel comes from the event pairs the timed steps carry anyway).
+
+--full adds every other leg, each a run of its own after the timed steps: roofline = achieved algorithmic TFLOP/s of the dominant kernel family (the
+MFMA implicit-GEMM convolution engine) measured live with hipEvents on the launch stream over two further steps, roofline_hbm, the D forward
+stack, the FID feature-extraction leg in three precisions, the other BASELINE.json configurations (extra_workloads) and cpu_baseline = the CPU oracle
+(restatement of the reference, oracle/restate.py) timed on the host cores at a reduced batch. --no-cpu-baseline, --no-extras, --fid-samples 0 and
+--strict select among and judge those legs; without --full they have nothing to act on. The timed steps are the same with and without --full.
 
 --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs below). Weights, real baskets, latents and
 labels all come from fixed seeds, and with this flag the last timed step starts again from the seeded weights and optimizer state, so two
@@ -448,7 +453,7 @@ def cpu_baseline(workload, cpu_batch, timeout_s=170, unit="images/sec"):
                 "sample": f"the {workload} CPU sample at batch {cpu_batch} did not finish within the {timeout_s}s bound"}
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # defaults: the first steps after process start run 2-3 % slower on the GPU side (r7q, same box: 5 steps after 2 warm-up 128.3 ms, 20 after 5 124.85 ms, the host > 100 ms ahead in
@@ -458,10 +463,14 @@ def main():
     ap.add_argument("--workload", default="biggan128")
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch")
     ap.add_argument("--fp32", action="store_true", help="fp32 compute instead of bf16 (not the benchmark configuration)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--fid-samples", type=int, default=50000, help="samples of the FID feature-extraction leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: the convolution engine's family roofline and the HBM-bound families (two further "
+                         "profiled steps), the D forward stack, the FID feature-extraction leg, the extra workloads and the CPU baselines (minutes, not seconds). "
+                         "Off by default: a plain run sets up, warms up, times its steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--fid-samples", type=int, default=50000, help="--full: samples of the FID feature-extraction leg (0 = skip)")
     ap.add_argument("--cpu-batch", type=int, default=8)
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra workloads (C2 fp32, C5 WGAN-GP, C4 per GPU)")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extra workloads (C2 fp32, C5 WGAN-GP, C4 per GPU)")
     ap.add_argument("--native-comm", action="store_true", help="same as --comm native")
     ap.add_argument("--comm", choices=["auto", "native", "torch"], default=os.environ.get("SG_COMM", "auto"),
                     help="N > 1: who carries the exchanges. auto (default): libsgamd.so's own RCCL communicators for the gradient arena (sg_allreduce_flat on HIP "
@@ -470,13 +479,34 @@ def main():
                          "same without the fallback (a failing self-test aborts); torch: torch.distributed only")
     ap.add_argument("--strong", action="store_true", help="strong scaling: --batch is the GLOBAL batch, every rank takes batch / world of it (what the reference does: "
                     "src/loader.py:162 divides the configured batch over the ranks); default is weak scaling (--batch per GPU)")
-    ap.add_argument("--strict", action="store_true", help="exit non-zero when an extra workload / leg fails (the line is still printed)")
+    ap.add_argument("--strict", action="store_true", help="--full: exit non-zero when an extra workload / leg fails (the line is still printed)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed (rank 0: losses, generator images, discriminator logits) as DIR/<name>.npy in float32. That "
                          "step starts from the seeded weights, optimizer state and generator state again, so two builds run with the same arguments compare "
                          "output for output")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def legs_after_timed_steps(args, world):
+    """What a run does between its timed steps and its result line, each leg a run of its own. Nothing without --full: a plain run is set-up, warm-up,
+    the timed steps, --dump-outputs and the line."""
+    if not args.full:
+        return set()
+    c3, legs = args.workload == "biggan128", {"profiled_steps"}
+    if c3:
+        legs.add("d_forward")
+    if c3 and args.fid_samples > 0:
+        legs.add("fid")
+    if c3 and world == 1 and not args.no_extras:
+        legs.add("extras")
+    if world == 1 and not args.no_cpu_baseline:
+        legs.add("cpu_baseline")
+    return legs
+
+
+def main():
+    args = parse_args()
     if args.cpu_baseline_child:
         cpu_baseline_child(args.workload, args.cpu_batch)
         return
@@ -666,29 +696,33 @@ def main():
     assert d_last > 1e-2, f"discriminator saturated in the timed region (d_loss {d_last}): the measured step would multiply zero gradients"
     fake_chk = w.last_g[0]
     assert bool(torch.isfinite(fake_chk).all()) and float(fake_chk.abs().max()) <= 1.0, "generator images of the last step are not finite / not in [-1, 1]"
-    # PMC byte counts need their own rocprofv3 passes: the committed summary of those passes over this same command (tools/pmc_traffic.py). The
+    # --full: PMC byte counts need their own rocprofv3 passes: the committed summary of those passes over this same command (tools/pmc_traffic.py). The
     # summary carries the hash of the kernel sources it was taken on; a summary of OTHER sources is reported as stale, never silently used as current
-    pmc_tab, pmc_src, pmc_sha, cur_sha = None, None, None, csrc_sha16()
-    try:
-        pmc_name = next(n for n in ("r06_conv_hbm_traffic_pmc.json", "r05_conv_hbm_traffic_pmc.json", "r04_conv_hbm_traffic_pmc.json") if os.path.exists(os.path.join(ROOT, "profiles", n)))
-        pj = json.load(open(os.path.join(ROOT, "profiles", pmc_name)))
-        pmc_tab, pmc_sha = pj.get("per_kernel"), pj.get("csrc_sha16")
-        pmc_src = "profiles/" + pmc_name
-    except Exception:
-        pass
+    legs = legs_after_timed_steps(args, world)
+    pmc_tab, pmc_src, pmc_sha, cur_sha = None, None, None, None
+    if "profiled_steps" in legs:
+        cur_sha = csrc_sha16()
+        try:
+            pmc_name = next(n for n in ("r06_conv_hbm_traffic_pmc.json", "r05_conv_hbm_traffic_pmc.json", "r04_conv_hbm_traffic_pmc.json") if os.path.exists(os.path.join(ROOT, "profiles", n)))
+            pj = json.load(open(os.path.join(ROOT, "profiles", pmc_name)))
+            pmc_tab, pmc_sha = pj.get("per_kernel"), pj.get("csrc_sha16")
+            pmc_src = "profiles/" + pmc_name
+        except Exception:
+            pass
     per_kernel_timed = per_kernel_table(L, args.steps, PEAK_BF16_TFLOPS if mixed else PEAK_F32_TFLOPS, pmc_tab)      # (prof_all: every family; else the dominant kernel's rows)
     prof4 = (ctypes.c_double * 12)()
     L.call("sg_prof_collect_ex", prof4, 3)
     L.call("sg_prof_enable", 0)
-    per_kernel, psteps = per_kernel_timed, args.steps          # (replaced below by the profiled steps' table unless prof_all)
+    per_kernel, psteps = per_kernel_timed, args.steps          # (--full replaces it below by the profiled steps' table unless prof_all)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # ======== every leg from here to the result line is a run of its own behind --full: a plain run goes straight to the line ========
     # ---- north-star target figure: the BigGAN-128 (BigGAN-256.yaml) D FORWARD conv stack at batch 256 -----------
     # 21.673 GFLOP/img whole forward, 21.170 GFLOP/img conv-only; conv-only time = hipEvent brackets of the conv launches.
     dfwd = None
-    if args.workload == "biggan128" and rank == 0:
+    if "d_forward" in legs and rank == 0:
         x, y = pool[0]
         with torch.no_grad():
             for _ in range(2):
@@ -723,7 +757,7 @@ def main():
                 "per_kernel": dfwd_kernels}
     # ---- HBM-bound kernel families of the step: algorithmic bytes / hipEvent time per family over two more steps --------
     hbm = None
-    if rank == 0 or world > 1:
+    if "profiled_steps" in legs:
         L.call("sg_prof_enable", 2 if prof_all else 3)          # bit 1: spectral norm, batch norm, attention score kernels, Adam / EMA; bit 0: every engine launch
         hsteps = 2
         for i in range(hsteps):
@@ -763,7 +797,7 @@ def main():
                             "only to show that HBM is not the roof"}
     # ---- second metric: FID-50k feature extraction (reference src/metrics/features.py:17-65) ------------------------
     fid = None
-    if args.fid_samples > 0 and args.workload == "biggan128":
+    if "fid" in legs:
         from studiogan_amd import metrics as M
         from studiogan_amd.worker import make_GAN_untrainable
         make_GAN_untrainable(G, w.Gen_ema, D)
@@ -902,6 +936,11 @@ def main():
                                      "launch inside the timed region costs ~3 ms of dispatch gaps per step (two barrier packets per launch; tools/kt_gaps.py, "
                                      "profiles/r06_step_gaps_*.txt), i.e. the instrument slowed `value`")},
     }
+    if not ("profiled_steps" in legs or prof_all):
+        # the timed steps bracketed the dominant kernel alone: the family figures above would be that kernel's under the family's name
+        out["roofline"] = {**{k: out["roofline"][k] for k in ("bound", "peak", "unit", "dominant_kernel")},
+                           "measured_on": f"hipEvent pairs around every launch of that kernel in the timed region ({args.steps} steps); the family total, per_kernel, "
+                                          "traffic and roofline_hbm take further steps with pairs around every launch: --full"}
     if hbm is not None:
         out["roofline_hbm"] = hbm
     if dfwd is not None:
@@ -910,7 +949,7 @@ def main():
         out["fid_extract"] = fid
     if wl["gflop"]:
         out["step_tflops"] = round(wl["gflop"] * global_batch / 1e3 / (ms_per_step * 1e-3), 2)  # whole-step algorithmic TFLOP/s
-    if world == 1 and not args.no_extras and args.workload == "biggan128":
+    if "extras" in legs:
         del w, G, D, pool
         torch.cuda.empty_cache()
         out["extra_workloads"] = {}
@@ -922,7 +961,7 @@ def main():
                 failed.append(name)
                 sys.stderr.write(f"[bench] EXTRA WORKLOAD FAILED: {name}: {ex!r}\n")
         w = G = D = pool = None
-    if not args.no_cpu_baseline and world == 1:
+    if "cpu_baseline" in legs:
         w = G = D = pool = None
         torch.cuda.empty_cache()
         sys.stderr.write("[bench] gpu result: " + json.dumps(out) + "\n")

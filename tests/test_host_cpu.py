@@ -154,6 +154,20 @@ def test_bench_dump_outputs_is_float32_capped_and_repeatable(tmp_path):
     assert all(np.array_equal(v, np.load(tmp_path / "b" / (k + ".npy"))) for k, v in got.items())
 
 
+def test_bench_plain_run_goes_from_the_timed_steps_to_the_line():
+    """bench.py: without --full no leg runs after the timed steps, whatever the leg options say; --full turns every leg on, the leg options
+    select among them, and the legs that need one GPU or the benchmarked workload stay with it."""
+    import bench
+    legs = lambda *argv, world=1: bench.legs_after_timed_steps(bench.parse_args(list(argv)), world)
+    assert not bench.parse_args([]).full
+    assert legs("--gpus", "1", "--steps", "20", "--warmup", "5") == set()
+    assert legs("--dump-outputs", "d", "--strict", "--fid-samples", "1000", "--cpu-batch", "4") == set()
+    assert legs("--full") == {"profiled_steps", "d_forward", "fid", "extras", "cpu_baseline"}
+    assert legs("--full", "--no-extras", "--no-cpu-baseline", "--fid-samples", "0") == {"profiled_steps", "d_forward"}
+    assert legs("--full", "--gpus", "2", world=2) == {"profiled_steps", "d_forward", "fid"}
+    assert legs("--full", "--workload", "biggan32") == {"profiled_steps", "cpu_baseline"}
+
+
 def test_loss_schedule_helpers():
     """reference src/utils/losses.py:364-366 (adjust_k) and src/utils/ops.py:106-133 (LeCamEMA)."""
     from studiogan_amd import losses as SL, ops

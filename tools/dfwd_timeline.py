@@ -2,7 +2,7 @@
 start offset, duration and kernel of every dispatch from the NCHW->NHWC conversion of the input image to the projection head, plus
 the sum over the convolution-engine launches (the `d_forward_stack.conv_stack_ms` figure of bench.py, per launch).
 
-    rocprofv3 --kernel-trace --output-format csv -d out -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --fid-samples 0
+    rocprofv3 --kernel-trace --output-format csv -d out -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --fid-samples 0
     python tools/dfwd_timeline.py out/*/*_kernel_trace.csv
 """
 import csv

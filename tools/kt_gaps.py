@@ -1,7 +1,7 @@
 """Is the traced step GPU-bound? From a rocprofv3 --kernel-trace CSV: the window of the last `steps` training steps (delimited by k_adam_ema launches, 3 per C3 step),
 busy time (union of kernel intervals) / span, the idle time by size class, and the kernels that most often sit in front of an idle gap.
     python tools/kt_gaps.py <..._kernel_trace.csv> [steps=6] [adams_per_step=3] [skip_last_steps=2]
-(bench.py runs two more steps after the timed ones, with a host synchronisation in front: skip_last_steps keeps them out of the window.)"""
+(bench.py --full runs two more steps after the timed ones, with a host synchronisation in front: skip_last_steps keeps them out of the window; 0 for the trace of a plain run.)"""
 import csv
 import re
 import sys

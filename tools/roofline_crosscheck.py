@@ -1,7 +1,7 @@
 """Cross-check bench.py's live `roofline` figures (hipEvent brackets, csrc/capi.hip) against the rocprofv3 kernel trace of the same
 process: sums the convolution-engine kernels over the timed steps of the trace and prints both side by side.
 
-    rocprofv3 --kernel-trace --output-format csv -d out -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --fid-samples 0 > bench.log
+    rocprofv3 --kernel-trace --output-format csv -d out -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --fid-samples 0 > bench.log
     python tools/roofline_crosscheck.py out/*/*_kernel_trace.csv bench.log 1 3 > profiles/<name>.txt        (warmup steps, timed steps)
 """
 import csv
