@@ -441,6 +441,10 @@ int sg_u8_to_nhwc(int dtype, const uint8_t* x, const uint8_t* flip, void* y, int
  * OHxOW -> clip(0,255) -> (x/255-0.5)/0.5 -> T NHWC.  quant_out (optional) receives the uint8 NCHW image. */
 int sg_quantize_resize_normalize(int dtype, const float* x, void* out, uint8_t* quant_out, int N, int C, int H, int W,
                                  int OH, int OW, int quantize, sg_stream_t s);
+/* the same with per-channel constants, (x/255 - mean[c]) / std[c] (host arrays of C <= 4 floats): the torch backbones' ImageNet statistics,
+ * reference src/metrics/preparation.py:70-71. The entry point above is this one with mean = std = 0.5. */
+int sg_quantize_resize_normalize_ms(int dtype, const float* x, void* out, uint8_t* quant_out, int N, int C, int H, int W,
+                                    int OH, int OW, int quantize, const float* mean, const float* std, sg_stream_t s);
 /* generic pooling on NHWC: mode 0 max, 1 avg (count_include_pad), 2 avg excluding padding */
 int sg_pool2d(int dtype, const void* x, void* y, int N, int H, int W, int C, int k, int stride, int pad, int mode, int ldy, int c_off, sg_stream_t s);
 /* PIL resizers of reference src/utils/resize.py:39-78 ("clean": bicubic, "friendly": bilinear for InceptionV3_tf) on quantised images: Pillow's
@@ -449,6 +453,9 @@ int sg_pool2d(int dtype, const void* x, void* y, int N, int H, int W, int C, int
 int sg_pil_resize_normalize(int dtype, const float* x, void* out, float* tmp, int N, int C, int H, int W, int OH, int OW,
                             const int* bounds_h, const double* kk_h, int ksize_h, const int* bounds_v, const double* kk_v, int ksize_v,
                             int quantize, sg_stream_t s);
+int sg_pil_resize_normalize_ms(int dtype, const float* x, void* out, float* tmp, int N, int C, int H, int W, int OH, int OW,
+                               const int* bounds_h, const double* kk_h, int ksize_h, const int* bounds_v, const double* kk_v, int ksize_v,
+                               int quantize, const float* mean, const float* std, sg_stream_t s);
 /* global average pool [N,HW,C] -> fp32 [N,C] */
 int sg_global_avgpool(int dtype, const void* x, float* y, int N, int HW, int C, sg_stream_t s);
 /* hits[n] = 1 iff the true class is within the top k of scores[n][0..ncls) with sklearn's tie rule (higher index wins a tie) */
@@ -476,6 +483,26 @@ int sg_contrastive_loss(int kind, const float* S, const float* p, const int64_t*
                         float* row_loss, float* loss, float* dS, float* dp, sg_stream_t s);
 int sg_gather_cols(const float* z, const int64_t* label, int rows, int cols, float* out, sg_stream_t s);       /* MD head: z[r][label[r]] */
 int sg_scatter_cols(const float* g, const int64_t* label, int rows, int cols, float* dz, sg_stream_t s);
+/* ---- ViT evaluation backbone (reference src/metrics/vit.py, eval_backbone "DINO_torch"), inference only: csrc/vit.hip, csrc/mha.hip ----------------
+ * LayerNorm over `rows` fp32 rows of C channels (C % 8 == 0, C <= 2048), row r at x + r * pitch; y (out_dtype: bf16 or fp32) at y + r * ldo.
+ * Variance on centred values; one wave per row. */
+int sg_layernorm_rows(int out_dtype, const float* x, long long pitch, const float* gamma, const float* beta, void* y, long long ldo, int rows, int C,
+                      float eps, sg_stream_t s);
+/* fp32 residual stream x[B][N][C]: x[b][0] = cls + pos[0], x[b][1 + p] = patch[b][p] + pos[1 + p]; patch [B][N - 1][C] fp32 */
+int sg_vit_tokens(const float* patch, const float* cls, const float* pos, float* x, int B, int N, int C, sg_stream_t s);
+/* exact (erf) GELU on n fp32 values, n % 4 == 0; y may be x */
+int sg_gelu_f32(const float* x, float* y, long long n, sg_stream_t s);
+/* out[m][n] = epi(sum_k a[m][k] w[n][k] + bias[n]): a [M][lda] bf16, w [N][K] bf16, fp32 accumulation; K, N multiples of 64, any M.
+ * epi 0: -> bf16 out[m * ldo + n]; 1: exact GELU -> bf16; 2: out (fp32) += result, in place (the residual stream). */
+int sg_tok_gemm(int epi, const void* a, int lda, const void* w, const float* bias, void* out, int ldo, int M, int N, int K, sg_stream_t s);
+/* O = softmax(scale * Q K^T) V per (image, head) from the packed bf16 activation qkv [B][N][3][H][D] -> out [B][N][H * D] bf16; D == 64, any N >= 1.
+ * Single pass, scores and probabilities stay on chip. sg_mha_fwd_ok: 1 when the shape is served. */
+int sg_mha_fwd_ok(int B, int N, int H, int D);
+int sg_mha_fwd(const void* qkv, void* out, int B, int N, int H, int D, float scale, sg_stream_t s);
+/* launches of the two fused kernels by this process: which path a forward took (tests, benchmarks) */
+long long sg_tok_gemm_launches(void);
+long long sg_mha_launches(void);
+
 /* ---- precision / recall / density / coverage (reference src/metrics/prdc.py:87-168) on squared distances. The cross term
  * D[r][c] = |y_c|^2 - 2 x_r . y_c comes from sg_gemm (fp32, alpha = -2, bias = |y|^2) one row block at a time. */
 int sg_row_sqnorm(const float* f, int n, int C, float* sq, sg_stream_t s);

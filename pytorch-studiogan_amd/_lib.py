@@ -202,6 +202,16 @@ _PROTOS = {
     "sg_ema_lerp": [_vp, _vp, _ll, _f, _vp],
     "sg_quantize_resize_normalize": [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "sg_pil_resize_normalize": [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp],
+    "sg_quantize_resize_normalize_ms": [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp],
+    "sg_pil_resize_normalize_ms": [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp],
+    "sg_layernorm_rows": [_i, _vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _f, _vp],
+    "sg_vit_tokens": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "sg_gelu_f32": [_vp, _vp, _ll, _vp],
+    "sg_tok_gemm": [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "sg_mha_fwd_ok": [_i, _i, _i, _i],
+    "sg_mha_fwd": [_vp, _vp, _i, _i, _i, _i, _f, _vp],
+    "sg_tok_gemm_launches": [],                            # returns a count
+    "sg_mha_launches": [],                                 # returns a count
     "sg_pool2d": [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "sg_global_avgpool": [_i, _vp, _vp, _i, _i, _i, _vp],
     "sg_feat_moments_accumulate": [_vp, _i, _i, _vp, _vp, _vp],
@@ -280,6 +290,8 @@ def lib():
             fn.argtypes = args
             fn.restype = _i
         l.sg_conv_rs_launches.restype = _ll
+        l.sg_tok_gemm_launches.restype = _ll
+        l.sg_mha_launches.restype = _ll
         # SG_F32_MODE=bf16x3: the fp32 convolutions (forward, data gradient, weight gradient) of the generic engine process-wide on the split-precision
         # path (functional.f32_mode is the scoped form); default = exact fp32 MFMA
         if os.environ.get("SG_F32_MODE", "exact") == "bf16x3":

@@ -25,7 +25,11 @@ __global__ void k_quantize_u8(const float* x, uint8_t* q, long long n) {
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) q[i] = (uint8_t)quant_u8(x[i]);
 }
 // bilinear, align_corners=False (torch area_pixel_compute_source_index): src = scale*(dst+0.5)-0.5 clamped at 0
-template <typename T> __global__ void k_qrn(const float* x, T* out, int N, int C, int H, int W, int OH, int OW, int quantize, float sh, float sw) {
+// per-channel normalisation constants (v / 255 - mean[c]) / std[c], by value in the kernel arguments (the resizers see at most 4 channels)
+struct NormMS { float mean[4], std[4]; };
+static inline NormMS norm_half() { NormMS n; for (int c = 0; c < 4; c++) { n.mean[c] = 0.5f; n.std[c] = 0.5f; } return n; }
+static inline NormMS norm_ms(const float* mean, const float* std, int C) { NormMS n = norm_half(); for (int c = 0; c < C; c++) { n.mean[c] = mean[c]; n.std[c] = std[c]; } return n; }
+template <typename T> __global__ void k_qrn(const float* x, T* out, int N, int C, int H, int W, int OH, int OW, int quantize, float sh, float sw, NormMS nm) {
   const long long total = (long long)N * OH * OW * C;
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int c = (int)(i % C); long long t = i / C; const int ow = (int)(t % OW); t /= OW; const int oh = (int)(t % OH); const int n = (int)(t / OH);
@@ -40,18 +44,27 @@ template <typename T> __global__ void k_qrn(const float* x, T* out, int N, int C
     else { v00 = truncf(v00); v01 = truncf(v01); v10 = truncf(v10); v11 = truncf(v11); }
     float v = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
     v = fminf(fmaxf(v, 0.f), 255.f);
-    v = (v / 255.0f - 0.5f) / 0.5f;
+    v = (v / 255.0f - nm.mean[c & 3]) / nm.std[c & 3];
     out[i] = from_f<T>(v);
   }
 }
-extern "C" int sg_quantize_resize_normalize(int dtype, const float* x, void* out, uint8_t* quant_out, int N, int C, int H, int W, int OH, int OW, int quantize, sg_stream_t s) {
+static int quantize_resize_normalize(int dtype, const float* x, void* out, uint8_t* quant_out, int N, int C, int H, int W, int OH, int OW, int quantize, NormMS nm, sg_stream_t s) {
   SG_CHECK(x && out && N > 0 && C > 0, "sg_quantize_resize_normalize: bad args");
   hipStream_t st = (hipStream_t)s;
   if (quant_out) hipLaunchKernelGGL(k_quantize_u8, dim3(grid1d((long long)N * C * H * W)), dim3(256), 0, st, x, quant_out, (long long)N * C * H * W);
   const float sh = (float)H / (float)OH, sw = (float)W / (float)OW;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(k_qrn<T>, dim3(grid1d((long long)N * OH * OW * C)), dim3(256), 0, st, x, (T*)out, N, C, H, W, OH, OW, quantize, sh, sw));
+  DISPATCH_T(dtype, hipLaunchKernelGGL(k_qrn<T>, dim3(grid1d((long long)N * OH * OW * C)), dim3(256), 0, st, x, (T*)out, N, C, H, W, OH, OW, quantize, sh, sw, nm));
   SG_LAUNCH_CHECK();
   return 0;
+}
+extern "C" int sg_quantize_resize_normalize(int dtype, const float* x, void* out, uint8_t* quant_out, int N, int C, int H, int W, int OH, int OW, int quantize, sg_stream_t s) {
+  return quantize_resize_normalize(dtype, x, out, quant_out, N, C, H, W, OH, OW, quantize, norm_half(), s);
+}
+// the same kernel with per-channel constants on the host: (v / 255 - mean[c]) / std[c] (the torch backbones' ImageNet statistics, reference src/metrics/preparation.py:70-71)
+extern "C" int sg_quantize_resize_normalize_ms(int dtype, const float* x, void* out, uint8_t* quant_out, int N, int C, int H, int W, int OH, int OW, int quantize,
+                                               const float* mean, const float* std, sg_stream_t s) {
+  SG_CHECK(mean && std && C > 0 && C <= 4, "sg_quantize_resize_normalize_ms: mean / std of at most 4 channels");
+  return quantize_resize_normalize(dtype, x, out, quant_out, N, C, H, W, OH, OW, quantize, norm_ms(mean, std, C), s);
 }
 
 // generic NHWC pooling; output may be a channel slice [c_off, c_off+C) of a wider (ldy) concat tensor
@@ -374,7 +387,7 @@ __global__ __launch_bounds__(256) void k_pil_resample_h(const float* x, float* t
 }
 // pass 2: tmp [N][C][H][OW] -> out [N][OH][OW][C] NHWC, normalised (v / 255 - 0.5) / 0.5 (no clipping: PIL's bicubic overshoot is kept,
 // unlike the legacy resizer)
-template <typename T> __global__ __launch_bounds__(256) void k_pil_resample_v(const float* tmp, T* out, int N, int C, int H, int OH, int OW, const int* bounds, const double* kk, int ksize) {
+template <typename T> __global__ __launch_bounds__(256) void k_pil_resample_v(const float* tmp, T* out, int N, int C, int H, int OH, int OW, const int* bounds, const double* kk, int ksize, NormMS nm) {
   const long long total = (long long)N * OH * OW * C;
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int c = (int)(i % C); long long t = i / C; const int ox = (int)(t % OW); t /= OW; const int oy = (int)(t % OH); const int n = (int)(t / OH);
@@ -384,17 +397,28 @@ template <typename T> __global__ __launch_bounds__(256) void k_pil_resample_v(co
     double ss = 0.0;
     for (int j = 0; j < cnt; j++) ss += (double)p[(long long)j * OW] * k[j];
     float v = (float)ss;
-    v = (v / 255.0f - 0.5f) / 0.5f;
+    v = (v / 255.0f - nm.mean[c & 3]) / nm.std[c & 3];
     out[i] = from_f<T>(v);
   }
+}
+static int pil_resize_normalize(int dtype, const float* x, void* out, float* tmp, int N, int C, int H, int W, int OH, int OW,
+                                const int* bounds_h, const double* kk_h, int ksize_h, const int* bounds_v, const double* kk_v, int ksize_v,
+                                int quantize, NormMS nm, sg_stream_t s) {
+  SG_CHECK(x && out && tmp && bounds_h && kk_h && bounds_v && kk_v && N > 0 && C > 0 && ksize_h > 0 && ksize_v > 0, "sg_pil_resize_normalize: bad args");
+  hipStream_t st = (hipStream_t)s;
+  hipLaunchKernelGGL(k_pil_resample_h, dim3(grid1d((long long)N * C * H * OW)), dim3(256), 0, st, x, tmp, N, C, H, W, OW, bounds_h, kk_h, ksize_h, quantize);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(k_pil_resample_v<T>, dim3(grid1d((long long)N * OH * OW * C)), dim3(256), 0, st, (const float*)tmp, (T*)out, N, C, H, OH, OW, bounds_v, kk_v, ksize_v, nm));
+  SG_LAUNCH_CHECK();
+  return 0;
 }
 extern "C" int sg_pil_resize_normalize(int dtype, const float* x, void* out, float* tmp, int N, int C, int H, int W, int OH, int OW,
                                        const int* bounds_h, const double* kk_h, int ksize_h, const int* bounds_v, const double* kk_v, int ksize_v,
                                        int quantize, sg_stream_t s) {
-  SG_CHECK(x && out && tmp && bounds_h && kk_h && bounds_v && kk_v && N > 0 && C > 0 && ksize_h > 0 && ksize_v > 0, "sg_pil_resize_normalize: bad args");
-  hipStream_t st = (hipStream_t)s;
-  hipLaunchKernelGGL(k_pil_resample_h, dim3(grid1d((long long)N * C * H * OW)), dim3(256), 0, st, x, tmp, N, C, H, W, OW, bounds_h, kk_h, ksize_h, quantize);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(k_pil_resample_v<T>, dim3(grid1d((long long)N * OH * OW * C)), dim3(256), 0, st, (const float*)tmp, (T*)out, N, C, H, OH, OW, bounds_v, kk_v, ksize_v));
-  SG_LAUNCH_CHECK();
-  return 0;
+  return pil_resize_normalize(dtype, x, out, tmp, N, C, H, W, OH, OW, bounds_h, kk_h, ksize_h, bounds_v, kk_v, ksize_v, quantize, norm_half(), s);
+}
+extern "C" int sg_pil_resize_normalize_ms(int dtype, const float* x, void* out, float* tmp, int N, int C, int H, int W, int OH, int OW,
+                                          const int* bounds_h, const double* kk_h, int ksize_h, const int* bounds_v, const double* kk_v, int ksize_v,
+                                          int quantize, const float* mean, const float* std, sg_stream_t s) {
+  SG_CHECK(mean && std && C > 0 && C <= 4, "sg_pil_resize_normalize_ms: mean / std of at most 4 channels");
+  return pil_resize_normalize(dtype, x, out, tmp, N, C, H, W, OH, OW, bounds_h, kk_h, ksize_h, bounds_v, kk_v, ksize_v, quantize, norm_ms(mean, std, C), s);
 }

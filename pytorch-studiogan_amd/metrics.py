@@ -1,6 +1,6 @@
 """FID / IS feature-extraction path on the GPU, mirroring the reference's evaluation interfaces:
 
-  LoadEvalModel(...).get_outputs(x, quantize)           reference src/metrics/preparation.py:43-122
+  LoadEvalModel(...).get_outputs(x, quantize)           reference src/metrics/preparation.py:43-122 (InceptionV3_tf, DINO_torch)
   generate_images_and_stack_features(...)               reference src/metrics/features.py:17-65
   calculate_moments / frechet_inception_distance        reference src/metrics/fid.py:34-98
   calculate_kl_div / top-k accuracy                     reference src/metrics/ins.py:28-79
@@ -255,13 +255,241 @@ class InceptionV3:
         return feat, logits
 
 
-def preprocess(x, dtype, quantize=True, size=299, want_uint8=False):
-    """ops.quantize_images + resize_images('legacy') + normalise on the device (reference utils/ops.py:251-263)."""
+# ---- DINO ViT backbone (eval_backbone "DINO_torch") ---------------------------------------------------------------------------------------------------
+# reference src/metrics/preparation.py:69-74: vit_small(patch_size=8, num_classes=1000, num_last_blocks=4) with the published DINO backbone and linear-
+# classifier weights (src/utils/misc.py:632-691). The two files cannot be fetched here and carry no hash in their names; what identifies them -- the file
+# names and a strict structural check -- is enforced, and their sha256 digests are reported for the user to compare.
+DINO_WEIGHTS_URL = "https://dl.fbaipublicfiles.com/dino/dino_deitsmall8_pretrain/"
+DINO_BACKBONE_FILE = "dino_deitsmall8_pretrain.pth"
+DINO_LINEAR_FILE = "dino_deitsmall8_linearweights.pth"
+DINO_PUBLISHED_GEOMETRY = (384, 12, 8, 785, 1000)       # dino_manifest arguments of vit_small(patch_size=8, num_classes=1000) at 224 x 224
+LN_EPS = 1e-6                 # reference src/metrics/vit.py:237 (partial(nn.LayerNorm, eps=1e-6))
+VIT_HEAD_DIM = 64             # every DINO ViT (tiny 192 / 3, small 384 / 6, base 768 / 12); the fused attention kernel is built for it
+
+_BLOCK_PARAMS = ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias", "norm2.weight", "norm2.bias",
+                 "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
+
+
+def dino_manifest(embed, depth, patch, tokens, classes, hidden=None, num_last_blocks=4):
+    """{state_dict key: shape} of the reference's VisionTransformer with a linear head over the class tokens of the last `num_last_blocks` blocks."""
+    hidden = 4 * embed if hidden is None else hidden
+    m = {"cls_token": (1, 1, embed), "pos_embed": (1, tokens, embed), "patch_embed.proj.weight": (embed, 3, patch, patch), "patch_embed.proj.bias": (embed,),
+         "norm.weight": (embed,), "norm.bias": (embed,), "linear.weight": (classes, num_last_blocks * embed), "linear.bias": (classes,)}
+    shapes = {"norm1.weight": (embed,), "norm1.bias": (embed,), "attn.qkv.weight": (3 * embed, embed), "attn.qkv.bias": (3 * embed,),
+              "attn.proj.weight": (embed, embed), "attn.proj.bias": (embed,), "norm2.weight": (embed,), "norm2.bias": (embed,),
+              "mlp.fc1.weight": (hidden, embed), "mlp.fc1.bias": (hidden,), "mlp.fc2.weight": (embed, hidden), "mlp.fc2.bias": (embed,)}
+    for i in range(depth):
+        for k in _BLOCK_PARAMS:
+            m[f"blocks.{i}.{k}"] = shapes[k]
+    return m
+
+
+def validate_dino_state_dict(sd, num_heads=None, num_last_blocks=4):
+    """Reads the geometry off the tensor shapes and enforces what a strict load of the reference's model would: every expected tensor present with its
+    shape, floating point, nothing else. Returns dict(embed, depth, heads, patch, tokens, grid, classes, hidden, num_last_blocks); raises RuntimeError
+    naming the offending keys. num_heads: default embed / 64 (all DINO ViTs); any value that does not give head dimension 64 is refused."""
+    def bad(msg):
+        raise RuntimeError("not a DINO ViT state_dict (" + DINO_BACKBONE_FILE + " + " + DINO_LINEAR_FILE + "): " + msg)
+    for k in ("cls_token", "pos_embed", "patch_embed.proj.weight", "linear.weight"):
+        if k not in sd:
+            bad(f"missing {k}")
+        if not torch.is_tensor(sd[k]) or not torch.is_floating_point(sd[k]):
+            bad(f"{k} is not a floating-point tensor")
+    if sd["cls_token"].dim() != 3 or sd["pos_embed"].dim() != 3 or sd["patch_embed.proj.weight"].dim() != 4 or sd["linear.weight"].dim() != 2:
+        bad("wrong rank of cls_token / pos_embed / patch_embed.proj.weight / linear.weight")
+    embed = int(sd["cls_token"].shape[-1])
+    tokens = int(sd["pos_embed"].shape[1])
+    patch = int(sd["patch_embed.proj.weight"].shape[-1])
+    classes = int(sd["linear.weight"].shape[0])
+    depth = 0
+    while f"blocks.{depth}.norm1.weight" in sd:
+        depth += 1
+    heads = embed // VIT_HEAD_DIM if num_heads is None else int(num_heads)
+    if heads < 1 or heads * VIT_HEAD_DIM != embed:
+        bad(f"embed {embed} with {heads} heads: the head dimension must be {VIT_HEAD_DIM}")
+    grid = int(round(math.sqrt(max(tokens - 1, 0))))
+    if tokens < 2 or grid * grid != tokens - 1:
+        bad(f"pos_embed holds {tokens} tokens: 1 + a square patch grid expected")
+    if depth < num_last_blocks:
+        bad(f"{depth} blocks, fewer than num_last_blocks = {num_last_blocks}")
+    hidden = int(sd["blocks.0.mlp.fc1.weight"].shape[0]) if "blocks.0.mlp.fc1.weight" in sd and sd["blocks.0.mlp.fc1.weight"].dim() == 2 else 4 * embed
+    if embed % 64 or hidden % 64:
+        bad(f"embed {embed} / hidden {hidden}: multiples of 64 expected")
+    man = dino_manifest(embed, depth, patch, tokens, classes, hidden, num_last_blocks)
+    missing = sorted(set(man) - set(sd))
+    unexpected = sorted(set(sd) - set(man))
+    wrong = sorted(k for k in man if k in sd and (tuple(sd[k].shape) != man[k] or not torch.is_floating_point(sd[k])))
+    if missing or unexpected or wrong:
+        def head(v):
+            return ", ".join(v[:4]) + (f" (+{len(v) - 4} more)" if len(v) > 4 else "")
+        bad((f"missing {len(missing)}: {head(missing)}; " if missing else "") + (f"unexpected {len(unexpected)}: {head(unexpected)}; " if unexpected else "")
+            + (f"wrong shape / dtype {len(wrong)}: {head(wrong)}" if wrong else ""))
+    return dict(embed=embed, depth=depth, heads=heads, patch=patch, tokens=tokens, grid=grid, classes=classes, hidden=hidden, num_last_blocks=num_last_blocks)
+
+
+def _sha256(path):
+    import hashlib
+    h = hashlib.sha256()
+    with open(path, "rb") as f:
+        for chunk in iter(lambda: f.read(1 << 20), b""):
+            h.update(chunk)
+    return h.hexdigest()
+
+
+def load_dino_weights(backbone_path, linear_path, checkpoint_key="teacher"):
+    """The two published files -> one state_dict under the reference's names, with the layout handling of src/utils/misc.py:632-691: the backbone
+    optionally under `checkpoint_key`, `module.` / `backbone.` prefixes stripped, tensors the model does not own (a training checkpoint's projection
+    head) dropped as the reference's non-strict load drops them; the classifier under "state_dict" with `module.linear.` stripped. There is no
+    download. Returns (state_dict, (sha256 backbone, sha256 linear), pinned); pinned: both files carry the published names AND the merged dict is
+    exactly the ViT-S/8 manifest (DINO_PUBLISHED_GEOMETRY). No digest of the published files is known offline, so the flag is name- and shape-based
+    only: compare the returned digests with your download to be sure."""
+    import os
+    for what, path, name in (("weights_path", backbone_path, DINO_BACKBONE_FILE), ("linear_weights_path", linear_path, DINO_LINEAR_FILE)):
+        if path is None or not os.path.isfile(path):
+            raise RuntimeError(f"{what}={path!r}: DINO_torch needs both {DINO_BACKBONE_FILE} and {DINO_LINEAR_FILE} (from {DINO_WEIGHTS_URL}); there is no "
+                               "network access here")
+    bb = torch.load(backbone_path, map_location="cpu")
+    if checkpoint_key is not None and checkpoint_key in bb:
+        bb = bb[checkpoint_key]
+    bb = {k.replace("module.", "").replace("backbone.", ""): v for k, v in bb.items()}
+    lin = torch.load(linear_path, map_location="cpu")["state_dict"]
+    lin = {k.replace("module.linear.", ""): v for k, v in lin.items()}
+    if set(lin) != {"weight", "bias"}:
+        raise RuntimeError(f"{linear_path}: a linear classifier (weight, bias) expected under 'state_dict', found {sorted(lin)[:4]}")
+    own = ("cls_token", "pos_embed", "patch_embed.", "blocks.", "norm.")
+    sd = {k: v for k, v in bb.items() if k.startswith(own)}
+    sd["linear.weight"], sd["linear.bias"] = lin["weight"], lin["bias"]
+    geo = validate_dino_state_dict(sd)
+    published = dino_manifest(*DINO_PUBLISHED_GEOMETRY)
+    pinned = (os.path.basename(backbone_path) == DINO_BACKBONE_FILE and os.path.basename(linear_path) == DINO_LINEAR_FILE
+              and geo["num_last_blocks"] == 4 and {k: tuple(v.shape) for k, v in sd.items()} == published)
+    return sd, (_sha256(backbone_path), _sha256(linear_path)), pinned
+
+
+class DINOViT:
+    """The reference's VisionTransformer forward (src/metrics/vit.py:198-224), inference only: patch embedding, `depth` pre-norm blocks on an fp32
+    residual stream, and as output the class tokens of the last four blocks, each through the final norm, concatenated (+ the linear head on them).
+    `state_dict` uses the reference's key names; the geometry is read from the shapes (validate_dino_state_dict).
+
+    dtype=torch.bfloat16: the fused path -- per block LayerNorm -> bf16, qkv GEMM (bias), sg_mha_fwd on the packed qkv, proj GEMM (+= residual),
+    LayerNorm, fc1 GEMM (bias + GELU), fc2 GEMM (+= residual): 7 launches, nothing elementwise in between.
+    dtype=torch.float32: the same graph on the exact-fp32 sg_gemm, scores per head as batched sg_gemm + sg_softmax_rows + sg_gemm and an fp32 GELU
+    pass: the exact path (and the A/B partner of the fused one); not built for speed."""
+
+    def __init__(self, state_dict, device, dtype=torch.float32, num_heads=None):
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"DINOViT: dtype {dtype}")
+        self.geometry = g = validate_dino_state_dict(state_dict, num_heads=num_heads)
+        if not L.lib().sg_mha_fwd_ok(1, g["tokens"], g["heads"], g["embed"] // g["heads"]):
+            raise RuntimeError(f"DINOViT: no attention kernel for {g}")
+        self.device, self.dtype = torch.device(device), dtype
+        L.require_gpu(self.device)
+        f32 = lambda k: state_dict[k].detach().to(device=self.device, dtype=torch.float32).contiguous()
+        wt = lambda k: state_dict[k].detach().to(device=self.device, dtype=torch.float32).to(dtype).contiguous()
+        with torch.no_grad():
+            self.patch_w = state_dict["patch_embed.proj.weight"].detach().to(device=self.device, dtype=torch.float32).permute(0, 2, 3, 1).contiguous().to(dtype)
+            self.patch_b = f32("patch_embed.proj.bias")
+            self.cls, self.pos = f32("cls_token").view(-1), f32("pos_embed").view(g["tokens"], g["embed"])
+            self.blocks = []
+            for i in range(g["depth"]):
+                p = f"blocks.{i}."
+                self.blocks.append({k: (wt(p + k) if k.endswith("weight") and "norm" not in k else f32(p + k)) for k in _BLOCK_PARAMS})
+            self.norm_w, self.norm_b = f32("norm.weight"), f32("norm.bias")
+            self.lin_w, self.lin_b = f32("linear.weight"), f32("linear.bias")
+        self.scale = float(VIT_HEAD_DIM) ** -0.5
+
+    def _ln(self, x, rows, pitch, w, b, out, ldo):
+        L.call("sg_layernorm_rows", L.dt(out), L.ptr(x), pitch, L.ptr(w), L.ptr(b), L.ptr(out), ldo, rows, self.geometry["embed"], LN_EPS, L.stream())
+
+    def _linear_f32(self, x, w, b, out, M, N, K, res=None):
+        F.gemm_raw(L.F32, w, 0, K, x, 0, K, out, N, N, M, K, bias=b, res=res, ldr=N if res is not None else 0)
+
+    def _attention_f32(self, qkv, att, B):
+        g = self.geometry
+        N, C, H, D = g["tokens"], g["embed"], g["heads"], VIT_HEAD_DIM
+        S = torch.empty((B, N, N), dtype=torch.float32, device=qkv.device)
+        P = torch.empty_like(S)
+        base = L.ptr(qkv)
+        for h in range(H):
+            q, k, v = base + 4 * (h * D), base + 4 * (C + h * D), base + 4 * (2 * C + h * D)
+            F.gemm_raw(L.F32, k, 0, 3 * C, q, 0, 3 * C, S, N, N, N, D, batch=B, p_bs=N * 3 * C, q_bs=N * 3 * C, out_bs=N * N, alpha=self.scale)
+            L.call("sg_softmax_rows", L.F32, L.ptr(S), L.ptr(P), B * N, N, L.stream())
+            F.gemm_raw(L.F32, v, 1, 3 * C, P, 0, N, L.ptr(att) + 4 * h * D, C, D, N, N, batch=B, p_bs=N * 3 * C, q_bs=N * N, out_bs=N * C)
+
+    @torch.no_grad()
+    def forward_nhwc(self, x):
+        """x: [B, res, res, 3] NHWC in the compute dtype, normalised -> (embed [B, 4 * C], logits [B, classes]), fp32. Only the native grid is
+        served (the identity branch of interpolate_pos_encoding, vit.py:165); any other input size raises."""
+        g = self.geometry
+        C, N, Hd, p, nlb = g["embed"], g["tokens"], g["hidden"], g["patch"], g["num_last_blocks"]
+        B = x.shape[0]
+        if x.dtype != self.dtype or tuple(x.shape[1:]) != (g["grid"] * p, g["grid"] * p, 3):
+            raise ValueError(f"DINOViT: input {tuple(x.shape)} {x.dtype}; [B, {g['grid'] * p}, {g['grid'] * p}, 3] {self.dtype} expected "
+                             "(position-embedding interpolation for other sizes is not implemented)")
+        bf = self.dtype == torch.bfloat16
+        dev = x.device
+        patches = F.conv2d_raw(x.contiguous(), self.patch_w.data_ptr(), 3, C, p, p, stride=p, epi_flags=L.EPI_OUT_F32 if bf else 0, bias=self.patch_b)
+        M = B * N
+        xs = torch.empty((M, C), dtype=torch.float32, device=dev)
+        L.call("sg_vit_tokens", L.ptr(patches), L.ptr(self.cls), L.ptr(self.pos), L.ptr(xs), B, N, C, L.stream())
+        y = torch.empty((M, C), dtype=self.dtype, device=dev)
+        qkv = torch.empty((M, 3 * C), dtype=self.dtype, device=dev)
+        att = torch.empty((M, C), dtype=self.dtype, device=dev)
+        hid = torch.empty((M, Hd), dtype=self.dtype, device=dev)
+        embed = torch.empty((B, nlb * C), dtype=torch.float32, device=dev)
+        st = L.stream()
+        for i, w in enumerate(self.blocks):
+            self._ln(xs, M, C, w["norm1.weight"], w["norm1.bias"], y, C)
+            if bf:
+                L.call("sg_tok_gemm", 0, L.ptr(y), C, L.ptr(w["attn.qkv.weight"]), L.ptr(w["attn.qkv.bias"]), L.ptr(qkv), 3 * C, M, 3 * C, C, st)
+                L.call("sg_mha_fwd", L.ptr(qkv), L.ptr(att), B, N, g["heads"], VIT_HEAD_DIM, self.scale, st)
+                L.call("sg_tok_gemm", 2, L.ptr(att), C, L.ptr(w["attn.proj.weight"]), L.ptr(w["attn.proj.bias"]), L.ptr(xs), C, M, C, C, st)
+            else:
+                self._linear_f32(y, w["attn.qkv.weight"], w["attn.qkv.bias"], qkv, M, 3 * C, C)
+                self._attention_f32(qkv, att, B)
+                self._linear_f32(att, w["attn.proj.weight"], w["attn.proj.bias"], xs, M, C, C, res=xs)
+            self._ln(xs, M, C, w["norm2.weight"], w["norm2.bias"], y, C)
+            if bf:
+                L.call("sg_tok_gemm", 1, L.ptr(y), C, L.ptr(w["mlp.fc1.weight"]), L.ptr(w["mlp.fc1.bias"]), L.ptr(hid), Hd, M, Hd, C, st)
+                L.call("sg_tok_gemm", 2, L.ptr(hid), Hd, L.ptr(w["mlp.fc2.weight"]), L.ptr(w["mlp.fc2.bias"]), L.ptr(xs), C, M, C, Hd, st)
+            else:
+                self._linear_f32(y, w["mlp.fc1.weight"], w["mlp.fc1.bias"], hid, M, Hd, C)
+                L.call("sg_gelu_f32", L.ptr(hid), L.ptr(hid), M * Hd, st)
+                self._linear_f32(hid, w["mlp.fc2.weight"], w["mlp.fc2.bias"], xs, M, C, Hd, res=xs)
+            j = i - (g["depth"] - nlb)
+            if j >= 0:      # the class-token rows only (row pitch N * C) through the final norm, into their slice of the concatenation
+                L.call("sg_layernorm_rows", L.F32, L.ptr(xs), N * C, L.ptr(self.norm_w), L.ptr(self.norm_b), L.ptr(embed) + 4 * j * C, nlb * C, B, C, LN_EPS, st)
+        logits = torch.empty((B, g["classes"]), dtype=torch.float32, device=dev)
+        F.gemm_raw(L.F32, self.lin_w, 0, nlb * C, embed, 0, nlb * C, logits, g["classes"], g["classes"], B, nlb * C, bias=self.lin_b)
+        return embed, logits
+
+
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)      # reference src/metrics/preparation.py:70-71 (every torch backbone)
+
+
+def _ms_args(mean, std, channels):
+    """host float arrays for the *_ms entry points; None -> the (0.5, 0.5) entry point is called instead"""
+    if mean is None and std is None:
+        return None
+    if mean is None or std is None or len(mean) != channels or len(std) != channels:
+        raise ValueError(f"mean and std must both be given, one value per channel ({channels})")
+    import ctypes
+    arr = ctypes.c_float * channels
+    return arr(*[float(v) for v in mean]), arr(*[float(v) for v in std])
+
+
+def preprocess(x, dtype, quantize=True, size=299, want_uint8=False, mean=None, std=None):
+    """ops.quantize_images + resize_images('legacy') + normalise on the device (reference utils/ops.py:251-263). mean / std: per-channel
+    constants of (x / 255 - mean) / std; default (0.5, 0.5) as for InceptionV3_tf."""
     x = x.float().contiguous()
     N, Cc, H, W = x.shape
     out = torch.empty((N, size, size, Cc), dtype=dtype, device=x.device)
     q = torch.empty((N, Cc, H, W), dtype=torch.uint8, device=x.device) if want_uint8 else None
-    L.call("sg_quantize_resize_normalize", L.dt(dtype), L.ptr(x), L.ptr(out), L.ptr(q), N, Cc, H, W, size, size, 1 if quantize else 0, L.stream())
+    ms = _ms_args(mean, std, Cc)
+    if ms is None:
+        L.call("sg_quantize_resize_normalize", L.dt(dtype), L.ptr(x), L.ptr(out), L.ptr(q), N, Cc, H, W, size, size, 1 if quantize else 0, L.stream())
+    else:
+        L.call("sg_quantize_resize_normalize_ms", L.dt(dtype), L.ptr(x), L.ptr(out), L.ptr(q), N, Cc, H, W, size, size, 1 if quantize else 0, ms[0], ms[1], L.stream())
     return (out, q) if want_uint8 else out
 
 
@@ -302,9 +530,9 @@ def pil_coeffs(in_size, out_size, filt):
 _PIL_CACHE = {}
 
 
-def preprocess_pil(x, dtype, filt, quantize=True, size=299):
+def preprocess_pil(x, dtype, filt, quantize=True, size=299, mean=None, std=None):
     """ops.quantize_images + resize_images with a PIL resizer (reference utils/resize.py:39-78: 'clean' = bicubic, 'friendly' = bilinear for
-    InceptionV3_tf) + normalise, on the device."""
+    InceptionV3_tf and DINO_torch) + normalise, on the device. mean / std as in `preprocess`."""
     x = x.float().contiguous()
     N, Cc, H, W = x.shape
     key = (H, W, size, filt, str(x.device))
@@ -316,24 +544,45 @@ def preprocess_pil(x, dtype, filt, quantize=True, size=299):
     bh, kh, nh, bv, kv, nv = _PIL_CACHE[key]
     tmp = torch.empty((N, Cc, H, size), dtype=torch.float32, device=x.device)
     out = torch.empty((N, size, size, Cc), dtype=dtype, device=x.device)
-    L.call("sg_pil_resize_normalize", L.dt(dtype), L.ptr(x), L.ptr(out), L.ptr(tmp), N, Cc, H, W, size, size, L.ptr(bh), L.ptr(kh), nh, L.ptr(bv), L.ptr(kv), nv,
-           1 if quantize else 0, L.stream())
+    ms = _ms_args(mean, std, Cc)
+    if ms is None:
+        L.call("sg_pil_resize_normalize", L.dt(dtype), L.ptr(x), L.ptr(out), L.ptr(tmp), N, Cc, H, W, size, size, L.ptr(bh), L.ptr(kh), nh, L.ptr(bv), L.ptr(kv), nv,
+               1 if quantize else 0, L.stream())
+    else:
+        L.call("sg_pil_resize_normalize_ms", L.dt(dtype), L.ptr(x), L.ptr(out), L.ptr(tmp), N, Cc, H, W, size, size, L.ptr(bh), L.ptr(kh), nh, L.ptr(bv), L.ptr(kv), nv,
+               1 if quantize else 0, ms[0], ms[1], L.stream())
     return out
 
 
 class LoadEvalModel:
-    """reference src/metrics/preparation.py:43-122 for eval_backbone == "InceptionV3_tf" with the post-resizers "legacy" (torch bilinear),
-    "clean" (PIL bicubic) and "friendly" (PIL bilinear), reference src/utils/resize.py:49-69."""
+    """reference src/metrics/preparation.py:43-122 for eval_backbone "InceptionV3_tf" (299 x 299, (0.5, 0.5) normalisation) and "DINO_torch" (ViT-S/8 at
+    224 x 224, ImageNet mean / std) with the post-resizers "legacy" (torch bilinear), "clean" (PIL bicubic) and "friendly" (PIL bilinear for both
+    backbones), reference src/utils/resize.py:49-69."""
+    BACKBONES = ("InceptionV3_tf", "DINO_torch")
+    RESIZERS = ("legacy", "clean", "friendly")
 
     def __init__(self, eval_backbone="InceptionV3_tf", post_resizer="legacy", world_size=1, distributed_data_parallel=False, device="cuda",
-                 state_dict=None, dtype=torch.float32, weights_path=None, f32_mode="exact"):
-        """state_dict: tensors under torchvision's inception_v3 names, checked against inception_manifest() like the reference's strict load
-        (anything else raises); weights_path: the published file itself, additionally checked against the sha256 prefix in its name.
-        `self.weights_pinned` says which: True only for a hash-verified file -- FID / IS values from any other weights (the seeded random
+                 state_dict=None, dtype=torch.float32, weights_path=None, f32_mode="exact", linear_weights_path=None):
+        """state_dict: tensors under the backbone's own names (torchvision's inception_v3 / the reference's vit.py), checked like the reference's strict
+        load (anything else raises); weights_path: the published file itself (InceptionV3_tf: additionally checked against the sha256 prefix in its
+        name; DINO_torch: the backbone file, with linear_weights_path the linear-classifier file).
+        `self.weights_pinned` says which: True only for the published files -- FID / IS values from any other weights (the seeded random
         ones of bench.py and the tests) are NOT comparable with published numbers."""
-        if eval_backbone != "InceptionV3_tf" or post_resizer not in ("legacy", "clean", "friendly"):
-            raise NotImplementedError("InceptionV3_tf with the legacy / clean / friendly resizers is on the hot path (SURVEY §2)")
+        if eval_backbone not in self.BACKBONES or post_resizer not in self.RESIZERS:
+            raise NotImplementedError(f"eval_backbone {eval_backbone!r} / post_resizer {post_resizer!r}: {' and '.join(self.BACKBONES)} with the "
+                                      f"{' / '.join(self.RESIZERS)} resizers are on the hot path (SURVEY §2, DESIGN §7)")
         self.weights_pinned, self.weights_sha256 = False, None
+        self.eval_backbone, self.post_resizer, self.device = eval_backbone, post_resizer, torch.device(device)
+        self.dtype = dtype
+        if eval_backbone == "DINO_torch":
+            if weights_path is not None or linear_weights_path is not None:
+                state_dict, self.weights_sha256, self.weights_pinned = load_dino_weights(weights_path, linear_weights_path)
+            if state_dict is None:
+                raise RuntimeError("pass the DINO ViT-S/8 weights (weights_path=.../" + DINO_BACKBONE_FILE + " and linear_weights_path=.../" + DINO_LINEAR_FILE +
+                                   ", both from " + DINO_WEIGHTS_URL + ", or a merged state_dict); there is no network access here")
+            self.res, self.mean, self.std = 224, IMAGENET_MEAN, IMAGENET_STD
+            self.model = DINOViT(state_dict, self.device, dtype)
+            return
         if weights_path is not None:
             state_dict, self.weights_sha256 = load_fid_weights(weights_path)
             self.weights_pinned = True
@@ -341,19 +590,19 @@ class LoadEvalModel:
             raise RuntimeError("pass the FID Inception weights (weights_path=.../" + FID_WEIGHTS_FILE + ", from " + FID_WEIGHTS_URL +
                                ", or its state_dict); there is no network access here")
         validate_inception_state_dict(state_dict)
-        self.eval_backbone, self.post_resizer, self.device = eval_backbone, post_resizer, torch.device(device)
-        self.res = 299
+        self.res, self.mean, self.std = 299, None, None
         self.model = InceptionV3(state_dict, self.device, dtype, f32_mode=f32_mode)      # f32_mode: InceptionV3.__init__
-        self.dtype = dtype
 
     def eval(self):
         pass
 
     @torch.no_grad()
     def get_outputs(self, x, quantize=False):
+        """(features, logits), fp32: InceptionV3_tf [B, 2048] / [B, 1008]; DINO_torch [B, 4 * embed] / [B, 1000]"""
         if self.post_resizer == "legacy":
-            return self.model.forward_nhwc(preprocess(x, self.dtype, quantize, self.res))
-        return self.model.forward_nhwc(preprocess_pil(x, self.dtype, "bicubic" if self.post_resizer == "clean" else "bilinear", quantize, self.res))
+            return self.model.forward_nhwc(preprocess(x, self.dtype, quantize, self.res, mean=self.mean, std=self.std))
+        return self.model.forward_nhwc(preprocess_pil(x, self.dtype, "bicubic" if self.post_resizer == "clean" else "bilinear", quantize, self.res,
+                                                      mean=self.mean, std=self.std))
 
 
 def softmax_rows(logits):
@@ -365,7 +614,8 @@ def softmax_rows(logits):
 @torch.no_grad()
 def generate_images_and_stack_features(generator, eval_model, num_generate, batch_size, z_dim, num_classes, quantize=True, world_size=1,
                                        DDP=False, device="cuda", moments=None, z_prior="gaussian", truncation_factor=-1.0, MODEL=None, latent_opt=None, langevin=None):
-    """reference src/metrics/features.py:17-65. Returns (features [n,2048], probs [n,1008], labels list).
+    """reference src/metrics/features.py:17-65. Returns (features [n, dim], probs [n, classes], labels list); dim / classes are the backbone's
+    (InceptionV3_tf 2048 / 1008, DINO_torch 1536 / 1000).
     moments: optional `FeatureMoments` accumulator fed on the device. It receives exactly the rows the reference keeps
     (`fake_feats[:num_generate]` of the rank-major gathered stack, src/metrics/fid.py:68-69): the over-generated tail --
     ceil(num_generate / batch) batches, `num_batches // world_size + 1` per rank under DDP -- is NOT accumulated.
@@ -428,7 +678,8 @@ def generate_images_and_stack_features(generator, eval_model, num_generate, batc
 
 class FeatureMoments:
     """sum f and sum f f^T in fp64 on the device (replaces np.mean / np.cov over gathered features, fid.py:96-97); in
-    data-parallel runs the two accumulators are all-reduced instead of gathering 50k x 2048 floats per rank."""
+    data-parallel runs the two accumulators are all-reduced instead of gathering 50k x dim floats per rank (dim: 2048 for InceptionV3_tf, 1536 for
+    DINO_torch -- any width)."""
 
     def __init__(self, dim, device):
         self.dim, self.n = dim, 0
@@ -555,19 +806,21 @@ def convert_labels(labels, class_to_idx, folder_label_dict):
     return [folder_label_dict[loader_label_folder_dict[int(l)]] for l in labels]
 
 
-def eval_features(probs, labels, num_features, split, is_acc, class_to_idx=None, folder_label_dict=None, topk_fn=None):
-    """reference src/metrics/ins.py:45-79 for the TF-Inception backbone on ImageNet: IS over the first num_features rows; top-1 / top-5 of
-    the remapped labels against probs[:, 1:1001] (the reference passes `[i + 1 for i in converted]` with that slice to sklearn, which
-    maps label i + 1 to column i: the same decision as testing 0-based class i here). The accuracy itself runs on the device
-    (`top_k_accuracy`: sklearn's tie rule, bit-exact)."""
+def eval_features(probs, labels, num_features, split, is_acc, class_to_idx=None, folder_label_dict=None, topk_fn=None, is_torch_backbone=False):
+    """reference src/metrics/ins.py:45-79 on ImageNet: IS over the first num_features rows; top-1 / top-5 of the remapped labels. TF-Inception
+    (the default): against probs[:, 1:1001] (the reference passes `[i + 1 for i in converted]` with that slice to sklearn, which
+    maps label i + 1 to column i: the same decision as testing 0-based class i here). is_torch_backbone (ins.py:57-66, DINO_torch and the other
+    torch backbones): the classes are columns 0..999, no offset. The accuracy itself runs on the device (`top_k_accuracy`: sklearn's tie rule,
+    bit-exact)."""
     topk_fn = topk_fn or top_k_accuracy
     probs, labels = probs[:num_features], labels[:num_features]
     m_scores, m_std = calculate_kl_div(probs, splits=split)
     top1, top5 = "N/A", "N/A"
     if is_acc:
         converted = convert_labels(labels, class_to_idx, folder_label_dict)
-        top1 = topk_fn(probs, converted, 1, 1, 1000)
-        top5 = topk_fn(probs, converted, 5, 1, 1000)
+        c0 = 0 if is_torch_backbone else 1
+        top1 = topk_fn(probs, converted, 1, c0, 1000)
+        top5 = topk_fn(probs, converted, 5, c0, 1000)
     return m_scores, m_std, top1, top5
 
 
