@@ -377,28 +377,22 @@ int sg_gp_fwd(int kind, const float* grads, int B, long long n, float* norms, fl
 int sg_gp_bwd(int kind, const float* grads, const float* norms, const float* gout, float* dgrads, int B, long long n, sg_stream_t s);
 int sg_masked_sum_hw(int dtype, const void* t, const void* x, float* out, int B, int HW, int C, sg_stream_t s);
 
-/* ---- fused self-attention scores (reference utils/ops.py:83-103: softmax(theta . maxpool(phi)^T) and its backward), bf16 only.
- * theta [B][HW][Dp], phi [B][HW4][Dp] (pooled), g [B][HW4][Cg] (pooled), dO [B][HW][Cg]; Dp <= 32, Dp % 8 == 0.
- *   sg_attn_probs_fwd: P [B][HW][HW4] bf16 = row softmax of the scores, lse [B][HW] = row log-sum-exp (scores stay in registers)
- *   sg_attn_ds_bwd:    dS [B][HW][HW4] bf16 = P * (dP - sum_k P dP), dP = dO . g^T, P recomputed from theta / phi / lse
- * sg_attn_fused_ok returns 1 when the shape is supported (HW % 128 == 0, HW4 % 256 == 0, HW4 <= 2048, Cg <= 128). */
-int sg_attn_fused_ok(int B, int HW, int HW4, int Dp, int Cg);
-/* fused forward of the attention core: O = softmax(theta phi^T) g per image in one launch (probabilities stored only when P != NULL) */
-int sg_attn_fwd_fused_ok(int B, int HW, int HW4, int Dp, int Cg);
-/* the P == NULL form streams keys and values in 256-key chunks: no bound on HW4 (16384 queries x 4096 keys of BigGAN-deep-256's D,
- * reference models/big_resnet_deep_legacy.py:80-95); sg_attn_fwd_fused accepts P == NULL whenever this returns 1 */
+/* ---- fused self-attention core (reference utils/ops.py:83-103: softmax(theta . maxpool(phi)^T) . maxpool(g) and its backward), bf16 only
+ * (csrc/attn.hip): scores, probabilities and their gradients never reach HBM.
+ * theta [B][HW][Dp], phi [B][HW4][Dp] (pooled), g [B][HW4][Cg] (pooled), O / dO [B][HW][Cg], lse [B][HW] = row log-sum-exp of the scores (fp32).
+ * The *_ok functions return 1 when the shape is supported: 1 <= B <= 65535, HW % 128 == 0, HW4 % 256 == 0, Dp in {8, 16, 24, 32}, Cg % 8 == 0,
+ * 8 <= Cg <= 128 (the backward also asks HW % 256 == 0 and HW4 % 128 == 0, which HW4 == HW / 4 implies: the two agree on every shape the reference's
+ * SelfAttention can run). Keys and values stream in 256-key chunks: no bound on HW4 (16384 queries x 4096 keys of BigGAN-deep-256's D, reference
+ * models/big_resnet_deep_legacy.py:80-95).
+ * sg_attn_fwd_fused: O = softmax(theta phi^T) g per image and lse in one launch; O32 (may be NULL) = unrounded fp32 copy of O [B][HW][Cg] */
 int sg_attn_fwd_flash_ok(int B, int HW, int HW4, int Dp, int Cg);
-int sg_attn_fwd_fused(const void* theta, const void* phi, const void* g, void* P, float* lse, void* O, float* O32, int B, int HW, int HW4, int Dp, int Cg, sg_stream_t s);
+int sg_attn_fwd_fused(const void* theta, const void* phi, const void* g, float* lse, void* O, float* O32, int B, int HW, int HW4, int Dp, int Cg, sg_stream_t s);
 /* fused backward of the attention core: dtheta, dphi, dg from theta / phi / g / dO / lse with P and dS recomputed on the fly (two launches:
- * query side + key side); delta = fp32 scratch [B][HW]. O32 = the unrounded fp32 copy of the forward output [B][HW][Cg] that
- * sg_attn_fwd_fused writes on request (P == NULL path): delta_q = dO_q . O_q, one key pass on the query side; NULL: delta from an extra pass
- * over the keys */
+ * query side + key side); delta = fp32 scratch [B][HW]. O32 = the fp32 copy of the forward output that sg_attn_fwd_fused writes on request:
+ * delta_q = dO_q . O_q, one key pass on the query side; NULL: delta from an extra pass over the keys */
 int sg_attn_bwd_fused_ok(int B, int HW, int HW4, int Dp, int Cg);
 int sg_attn_bwd_fused(const void* theta, const void* phi, const void* g, const void* dO, const float* O32, const float* lse, float* delta, void* dtheta, void* dphi,
                       void* dg, int B, int HW, int HW4, int Dp, int Cg, sg_stream_t s);
-int sg_attn_probs_fwd(const void* theta, const void* phi, void* P, float* lse, int B, int HW, int HW4, int Dp, sg_stream_t s);
-int sg_attn_ds_bwd(const void* theta, const void* phi, const void* g, const void* dO, const float* lse, void* dS,
-                   int B, int HW, int HW4, int Dp, int Cg, sg_stream_t s);
 
 /* ---- projection front end of the self-attention block as one launch per direction (csrc/attn_proj.hip), bf16 only.
  * x [B][H][W][ldx] (C channels used); w_theta / w_phi [Dp][C], w_g [Cg][C]: forward images of the three 1x1 layers (Dp includes the zero rows of a

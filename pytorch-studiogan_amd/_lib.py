@@ -170,14 +170,10 @@ _PROTOS = {
     "sg_bn_bwd2_finalize": [_vp, _i, _i, _vp, _vp],
     "sg_bn_bwd2_dgain": [_vp, _vp, C.c_double, _vp, _i, _i, _vp, _vp],
     "sg_bn_bwd2_apply": [_i, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp, _i, _vp, C.c_double, _i, _vp],
-    "sg_attn_fused_ok": [_i, _i, _i, _i, _i],
-    "sg_attn_fwd_fused_ok": [_i, _i, _i, _i, _i],
     "sg_attn_fwd_flash_ok": [_i, _i, _i, _i, _i],
-    "sg_attn_fwd_fused": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "sg_attn_fwd_fused": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "sg_attn_bwd_fused_ok": [_i, _i, _i, _i, _i],
     "sg_attn_bwd_fused": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "sg_attn_probs_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "sg_attn_ds_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "sg_attn_proj_ok": [_i, _i, _i, _i, _i, _i, _i],
     "sg_attn_proj_fwd": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "sg_attn_proj_bwd_data": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],

@@ -6,20 +6,20 @@
 // owns ONE query and 16 of the 32 keys of a block (max / sum in-lane plus one v_permlane32_swap); the bf16 probabilities go from the score accumulators
 // straight into the B operand of O^T += V^T P with the V^T fragments gathered by ds_read_b64_tr_b16; one pass with a running maximum that is only raised when a
 // block exceeds it by MH_THR. New here:
-//   - head dimension 64: K and V are each two [keys][32 channels] images of 64-byte rows (the conflict-free layout of at_stage), four score MFMAs per block;
+//   - head dimension 64: K and V are each two [keys][32 channels] images of 64-byte rows (the tile image of lds_tile.h), four score MFMAs per block;
 //   - `scale` lives in the exponent's multiplier: p = exp2(s * scale * log2 e - m * log2 e);
 //   - K + V of a head at N = 785 is 200 KB: keys stream in 128-key chunks through a 2-deep ring (2 x 32 KiB: two workgroups per CU), one barrier per
 //     chunk. The LDS-DMA of chunk c + 1 is ISSUED in front of chunk c's arithmetic, but the code object does not let it fly under that arithmetic: hipcc
 //     (ROCm 7.2) puts an `s_waitcnt vmcnt(0)` in front of the first transposing LDS read of the block loop, so a wave waits for its own share of chunk
 //     c + 1 before its first P V product of chunk c. What the ring buys is overlap ACROSS waves and across the two workgroups of a CU;
-//   - ordering rule of the ring: LDS-DMA data is visible to a ds_read only after the ISSUING wave's vmcnt has retired it and the reader has passed a
-//     barrier behind that. Every wave -- the ones that skip the arithmetic included -- therefore drains its own DMA with an explicit `s_waitcnt vmcnt(0)`
-//     right in front of the chunk barrier; nothing here relies on where the compiler happens to place its own waits;
+//   - every wave -- the ones that skip the arithmetic included -- drains its own DMA in front of the chunk barrier (lt_drain_barrier: the ordering rule of
+//     LDS-DMA is written there);
 //   - ragged tail: rows >= N of a chunk are fetched from a zero line, never from beyond the tensor; their scores are set to -inf before the running maximum;
 //     32-key blocks that start at or beyond N are not visited at all (a block therefore always holds a live key, and the running maximum starts at a
 //     FINITE floor: no exp(-inf + inf)); queries >= N are computed on zero rows and not stored. A wave whose 32 queries all lie beyond N skips the block
 //     loop as a whole wave -- it still stages and meets every barrier; partial waves run with every lane active (the transposing LDS read wants that).
 #include "common.h"
+#include "lds_tile.h"
 #include "../../include/sgamd.h"
 
 #ifndef MH_THR
@@ -29,56 +29,7 @@
 #define MH_IMG (MH_KC * 64)
 #define MH_STAGE (4 * MH_IMG)            // K channels 0-31 / 32-63, V channels 0-31 / 32-63
 
-typedef __attribute__((address_space(1))) const void* mh_gptr_t;
-typedef __attribute__((address_space(3))) void* mh_lptr_t;
-typedef __bf16 mh_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float mh_f32x16 __attribute__((ext_vector_type(16)));
-
-static __device__ u32x4 sg_mha_zero[4];
 static long long g_mha_launches = 0;
-
-// MH_KC key rows x 32 channels: rows k0 .. of `src` (row pitch ld, already offset to the head and channel group) -> lane-linear image; rows >= N are zeros
-__device__ __forceinline__ void mh_stage(char* img, const bf16_t* src, int k0, int N, int ld, int wave, int lane) {
-  const int r16 = lane >> 2;
-  const int chunk = (lane & 3) ^ ((lane >> 4) & 3);
-#pragma unroll
-  for (int g = wave; g < MH_KC / 16; g += 4) {
-    const int row = k0 + g * 16 + r16;
-    const bf16_t* p = (row < N) ? (src + (long long)row * ld + chunk * 8) : (const bf16_t*)sg_mha_zero;
-    __builtin_amdgcn_global_load_lds((mh_gptr_t)p, (mh_lptr_t)(img + g * 1024), 16, 0, 0);
-  }
-}
-__device__ __forceinline__ mh_bf16x8 mh_frag(const char* img, int kb, int t, int lane) {
-  const int row = kb * 32 + (lane & 31);
-  const int slot = (2 * t + (lane >> 5)) ^ ((row >> 2) & 3);
-  const u32x4 v = *(const u32x4*)(img + row * 64 + slot * 16);
-  return __builtin_bit_cast(mh_bf16x8, v);
-}
-// V^T fragment (at_vfrag of attn.hip): channel = lane & 31 of this image, keys kbase .. + 3 (elements 0-3) and kbase + 8 .. + 11 (elements 4-7)
-__device__ __forceinline__ mh_bf16x8 mh_vfrag(const char* img, int kbase, int lane) {
-  const int g16 = lane >> 4, t = lane & 15;
-  const int row = kbase + (t >> 2);
-  const int slot = (2 * (g16 & 1) + ((t & 3) >> 1)) ^ ((row >> 2) & 3);
-  const char* p = img + row * 64 + slot * 16 + 8 * (t & 1);
-  const int slot2 = (2 * (g16 & 1) + ((t & 3) >> 1)) ^ (((row + 8) >> 2) & 3);
-  const char* p2 = img + (row + 8) * 64 + slot2 * 16 + 8 * (t & 1);
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p2);
-  s16x8 r;
-  r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; r[3] = a[3];
-  r[4] = b[0]; r[5] = b[1]; r[6] = b[2]; r[7] = b[3];
-  return __builtin_bit_cast(mh_bf16x8, r);
-}
-__device__ __forceinline__ float mh_half_max(float v) {
-  const uint32_t u = __float_as_uint(v);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float mh_half_sum(float v) {
-  const uint32_t u = __float_as_uint(v);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
 
 // grid (ceil(N / 128), H, B), 256 threads, 2 * MH_STAGE bytes of LDS. Two workgroups per CU (LDS), two waves per SIMD: the register budget is set to match.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_mha_fwd(const bf16_t* qkv, bf16_t* O, int N, int H, float scale) {
@@ -93,20 +44,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const bf16_t* base = qkv + (long long)b * N * ld + head * 64;     // q of this head; k at + H * 64, v at + 2 * H * 64
   const bf16_t* kbase = base + H * 64;
   const bf16_t* vbase = base + 2 * H * 64;
-  mh_bf16x8 qf[4];                                                  // channels 16 i + 8 h .. + 8 of this lane's query
+  bf16x8_t qf[4];                                                  // channels 16 i + 8 h .. + 8 of this lane's query
   {
     const u32x4 z = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int i = 0; i < 4; i++) {
       const u32x4 v = (q < N) ? *(const u32x4*)(base + (long long)q * ld + 16 * i + 8 * h) : z;
-      qf[i] = __builtin_bit_cast(mh_bf16x8, v);
+      qf[i] = __builtin_bit_cast(bf16x8_t, v);
     }
   }
   const float c2 = scale * LOG2E;
   float m = -1.0e30f;          // running reference maximum (scaled scores, natural-log units), equal in both lane halves; finite on purpose
   float m2 = m * LOG2E;
   float l = 0.f;
-  mh_f32x16 o[2];
+  f32x16 o[2];
 #pragma unroll
   for (int cg = 0; cg < 2; cg++)
 #pragma unroll
@@ -114,16 +65,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   auto stage = [&](int c) {
     char* st = mh_smem + (c & 1) * MH_STAGE;
     const int k0 = c * MH_KC;
-    mh_stage(st, kbase, k0, N, ld, wave, lane);
-    mh_stage(st + MH_IMG, kbase + 32, k0, N, ld, wave, lane);
-    mh_stage(st + 2 * MH_IMG, vbase, k0, N, ld, wave, lane);
-    mh_stage(st + 3 * MH_IMG, vbase + 32, k0, N, ld, wave, lane);
+    lt_stage_rows(st, kbase, k0, N, ld, 0, wave, lane);
+    lt_stage_rows(st + MH_IMG, kbase, k0, N, ld, 32, wave, lane);
+    lt_stage_rows(st + 2 * MH_IMG, vbase, k0, N, ld, 0, wave, lane);
+    lt_stage_rows(st + 3 * MH_IMG, vbase, k0, N, ld, 32, wave, lane);
   };
   const int nch = (N + MH_KC - 1) / MH_KC;
   stage(0);
   for (int c = 0; c < nch; c++) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // this wave's share of chunk c has landed (idle waves never wait anywhere else) ...
-    __syncthreads();                                               // ... and so has everybody's; every wave is done with the other stage
+    lt_drain_barrier();                                            // chunk c has landed (idle waves wait for their share nowhere else); every wave is done with the other stage
     if (c + 1 < nch) stage(c + 1);
     if (!active) continue;
     const char* kimg = mh_smem + (c & 1) * MH_STAGE;
@@ -133,13 +83,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int nb = left >= MH_KC ? MH_KC / 32 : (left + 31) / 32;
 #pragma unroll 1
     for (int kc = 0; kc < nb; kc++) {
-      mh_f32x16 s;
+      f32x16 s;
 #pragma unroll
       for (int r = 0; r < 16; r++) s[r] = 0.f;
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mh_frag(kimg, kc, 0, lane), qf[0], s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mh_frag(kimg, kc, 1, lane), qf[1], s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mh_frag(kimg + MH_IMG, kc, 0, lane), qf[2], s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mh_frag(kimg + MH_IMG, kc, 1, lane), qf[3], s, 0, 0, 0);
+      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lt_frag(kimg, kc, 0, lane), qf[0], s, 0, 0, 0);
+      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lt_frag(kimg, kc, 1, lane), qf[1], s, 0, 0, 0);
+      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lt_frag(kimg + MH_IMG, kc, 0, lane), qf[2], s, 0, 0, 0);
+      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lt_frag(kimg + MH_IMG, kc, 1, lane), qf[3], s, 0, 0, 0);
       if (kc * 32 + 32 > left) {                                   // the last, partial block: keys >= N leave before the maximum is taken
 #pragma unroll
         for (int r = 0; r < 16; r++)
@@ -148,7 +98,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       float bm = s[0];
 #pragma unroll
       for (int r = 1; r < 16; r++) bm = fmaxf(bm, s[r]);
-      bm = mh_half_max(bm) * scale;                                // scale > 0: the maximum commutes with it
+      bm = lt_half_max(bm) * scale;                                // scale > 0: the maximum commutes with it
       if (bm > m + MH_THR) {                                       // (the first block always)
         const float alpha = __builtin_amdgcn_exp2f((m - bm) * LOG2E);
         l *= alpha;
@@ -165,17 +115,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       u32x4 pa, pb;                                                // regs 0-7 / 8-15 = contraction slots of the two k-steps
 #pragma unroll
       for (int i = 0; i < 4; i++) { pa[i] = pack2bf(p[2 * i], p[2 * i + 1]); pb[i] = pack2bf(p[8 + 2 * i], p[8 + 2 * i + 1]); }
-      const mh_bf16x8 pfa = __builtin_bit_cast(mh_bf16x8, pa), pfb = __builtin_bit_cast(mh_bf16x8, pb);
+      const bf16x8_t pfa = __builtin_bit_cast(bf16x8_t, pa), pfb = __builtin_bit_cast(bf16x8_t, pb);
 #pragma unroll
       for (int cg = 0; cg < 2; cg++) {
         const char* vi = vimg + cg * MH_IMG;
-        o[cg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mh_vfrag(vi, kc * 32 + 4 * h, lane), pfa, o[cg], 0, 0, 0);
-        o[cg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mh_vfrag(vi, kc * 32 + 16 + 4 * h, lane), pfb, o[cg], 0, 0, 0);
+        o[cg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lt_vfrag(vi, kc * 32 + 4 * h, lane), pfa, o[cg], 0, 0, 0);
+        o[cg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lt_vfrag(vi, kc * 32 + 16 + 4 * h, lane), pfb, o[cg], 0, 0, 0);
       }
     }
   }
   if (!active || q >= N) return;                                   // (no barrier behind this point)
-  l = mh_half_sum(l);
+  l = lt_half_sum(l);
   const float inv = 1.f / l;
   // O^T tile: lane = (query, h) holds channels cg * 32 + 8 * g4 + 4 h + (0..3)
   bf16_t* orow = O + ((long long)b * N + q) * (H * 64) + head * 64;
@@ -197,8 +147,8 @@ extern "C" int sg_mha_fwd(const void* qkv, void* out, int B, int N, int H, int D
   SG_CHECK(scale > 0.f, "sg_mha_fwd: scale must be positive");
   SG_CHECK((((uintptr_t)qkv | (uintptr_t)out) & 15) == 0, "sg_mha_fwd: pointers must be 16-byte aligned");
   hipStream_t st = (hipStream_t)s;
-  static bool done = false;
-  if (!done) { SG_CHECK(hipFuncSetAttribute((const void*)k_mha_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * MH_STAGE) == hipSuccess, "sg_mha_fwd: LDS attribute"); done = true; }
+  static const bool ok = lt_allow_lds(k_mha_fwd, 2 * MH_STAGE);
+  SG_CHECK(ok, "sg_mha_fwd: LDS attribute");
   {
     SgProfScope prof(st, 4.0 * (double)B * H * (double)N * (double)N * 64.0, 2);
     hipLaunchKernelGGL(k_mha_fwd, dim3((N + 127) / 128, H, B), dim3(256), 2 * MH_STAGE, st, (const bf16_t*)qkv, (bf16_t*)out, N, H, scale);

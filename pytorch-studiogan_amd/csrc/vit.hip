@@ -8,19 +8,13 @@
 // sg_tok_gemm. One workgroup = 4 waves = a 128 (tokens) x 128 (features) tile, each wave 64 x 64 as 2 x 2 MFMA 32x32x16 tiles with A = WEIGHT rows and
 // B = TOKEN rows: a lane then owns ONE token and, per register group, four consecutive output features -- bias / GELU / residual run on 8- or 16-byte
 // pieces of an output row without any cross-lane movement. Both operands are k-contiguous ([row][k]), staged 64 channels per step as two [128][32 ch]
-// images of 64-byte rows by LDS-DMA (16 B per lane, the chunk index XOR-ed by (row >> 2) & 3 on the SOURCE side: conflict-free ds_read_b128, the layout
-// attn.hip established), two stages: the DMA of step t + 1 flies under the MFMAs of step t, one barrier per step, in front of which every wave retires its
-// own DMA with an explicit `s_waitcnt vmcnt(0)` (the ordering rule of LDS-DMA: issuing wave's vmcnt, then a barrier the reader passes). Rows beyond M (B * 785 is a multiple of
-// nothing) and beyond N are fetched from a zero line instead of memory and masked at the store.
+// images of 64-byte rows (the LDS tile image of lds_tile.h, which attn.hip established), two stages: the DMA of step t + 1 flies under the MFMAs of step t, one
+// barrier per step, in front of which every wave retires its own DMA (lt_drain_barrier). Rows beyond M (B * 785 is a multiple of nothing) and beyond N are
+// fetched from a zero line instead of memory and masked at the store.
 #include "common.h"
+#include "lds_tile.h"
 #include "../../include/sgamd.h"
 
-typedef __attribute__((address_space(1))) const void* vt_gptr_t;
-typedef __attribute__((address_space(3))) void* vt_lptr_t;
-typedef __bf16 vt_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float vt_f32x16 __attribute__((ext_vector_type(16)));
-
-static __device__ u32x4 sg_vit_zero[4];
 static long long g_tok_gemm_launches = 0;
 
 static inline int vt_grid1d(long long total) { long long b = (total + 255) / 256; if (b > 256 * 32) b = 256 * 32; if (b < 1) b = 1; return (int)b; }
@@ -145,25 +139,6 @@ extern "C" int sg_gelu_f32(const float* x, float* y, long long n, sg_stream_t s)
 #define TG_IMG (128 * 64)                 // one [128 rows][32 channels] bf16 image
 #define TG_STAGE (4 * TG_IMG)             // tokens k-half 0 / 1, weights k-half 0 / 1
 
-// 128 rows x 32 channels (from channel c0) of a [.][ld] bf16 matrix -> lane-linear LDS image; rows >= nrows come from the zero line
-__device__ __forceinline__ void tg_stage(char* img, const bf16_t* src, int row0, int nrows, int ld, int c0, int wave, int lane) {
-  const int r16 = lane >> 2;
-  const int chunk = (lane & 3) ^ ((lane >> 4) & 3);
-#pragma unroll
-  for (int g = wave; g < 8; g += 4) {
-    const int row = row0 + g * 16 + r16;
-    const bf16_t* p = (row < nrows) ? (src + (long long)row * ld + c0 + chunk * 8) : (const bf16_t*)sg_vit_zero;
-    __builtin_amdgcn_global_load_lds((vt_gptr_t)p, (vt_lptr_t)(img + g * 1024), 16, 0, 0);
-  }
-}
-// MFMA fragment: image row rb + (lane & 31), 8 channels at 16 t + 8 h of the staged 32
-__device__ __forceinline__ vt_bf16x8 tg_frag(const char* img, int rb, int t, int lane) {
-  const int row = rb + (lane & 31);
-  const int slot = (2 * t + (lane >> 5)) ^ ((row >> 2) & 3);
-  const u32x4 v = *(const u32x4*)(img + row * 64 + slot * 16);
-  return __builtin_bit_cast(vt_bf16x8, v);
-}
-
 // EPI 0: bias -> bf16; 1: bias + GELU -> bf16; 2: out(fp32) += acc + bias (the residual stream, in place)
 template <int EPI>
 __global__ __launch_bounds__(256) void k_tok_gemm(const bf16_t* a, int lda, const bf16_t* w, const float* bias, void* out, int ldo, int M, int N, int K) {
@@ -171,7 +146,7 @@ __global__ __launch_bounds__(256) void k_tok_gemm(const bf16_t* a, int lda, cons
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n0 = blockIdx.x * TG_BN, m0 = blockIdx.y * TG_BM;
   const int wm = (wave & 1) * 64, wn = (wave >> 1) * 64;
-  vt_f32x16 acc[2][2];
+  f32x16 acc[2][2];
 #pragma unroll
   for (int mi = 0; mi < 2; mi++)
 #pragma unroll
@@ -183,23 +158,22 @@ __global__ __launch_bounds__(256) void k_tok_gemm(const bf16_t* a, int lda, cons
     char* st = tg_smem + (kt & 1) * TG_STAGE;
 #pragma unroll
     for (int kh = 0; kh < 2; kh++) {
-      tg_stage(st + kh * TG_IMG, a, m0, M, lda, kt * 64 + kh * 32, wave, lane);
-      tg_stage(st + (2 + kh) * TG_IMG, w, n0, N, K, kt * 64 + kh * 32, wave, lane);
+      lt_stage_rows(st + kh * TG_IMG, a, m0, M, lda, kt * 64 + kh * 32, wave, lane);
+      lt_stage_rows(st + (2 + kh) * TG_IMG, w, n0, N, K, kt * 64 + kh * 32, wave, lane);
     }
   };
   stage(0);
   for (int kt = 0; kt < nk; kt++) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // LDS-DMA is ordered for a reader only by the ISSUING wave's vmcnt, then a barrier: drain explicitly,
-    __syncthreads();                                         // do not lean on the fence lowering. Step kt has landed; every wave is done with the other stage
+    lt_drain_barrier();                                      // step kt has landed; every wave is done with the other stage
     if (kt + 1 < nk) stage(kt + 1);
     const char* st = tg_smem + (kt & 1) * TG_STAGE;
 #pragma unroll
     for (int kh = 0; kh < 2; kh++)
 #pragma unroll
       for (int t = 0; t < 2; t++) {
-        vt_bf16x8 xf[2], wf[2];
+        bf16x8_t xf[2], wf[2];
 #pragma unroll
-        for (int i = 0; i < 2; i++) { xf[i] = tg_frag(st + kh * TG_IMG, wm + 32 * i, t, lane); wf[i] = tg_frag(st + (2 + kh) * TG_IMG, wn + 32 * i, t, lane); }
+        for (int i = 0; i < 2; i++) { xf[i] = lt_frag_rows(st + kh * TG_IMG, wm + 32 * i, t, lane); wf[i] = lt_frag_rows(st + (2 + kh) * TG_IMG, wn + 32 * i, t, lane); }
 #pragma unroll
         for (int mi = 0; mi < 2; mi++)
 #pragma unroll
@@ -248,8 +222,8 @@ extern "C" int sg_tok_gemm(int epi, const void* a, int lda, const void* w, const
   const double flops = 2.0 * (double)M * (double)N * (double)K;
 #define TG_LAUNCH(E)                                                                                                                                   \
   {                                                                                                                                                    \
-    static bool done = false;                                                                                                                          \
-    if (!done) { SG_CHECK(hipFuncSetAttribute((const void*)k_tok_gemm<E>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TG_STAGE) == hipSuccess, "sg_tok_gemm: LDS attribute"); done = true; } \
+    static const bool ok = lt_allow_lds(k_tok_gemm<E>, 2 * TG_STAGE);                                                                                  \
+    SG_CHECK(ok, "sg_tok_gemm: LDS attribute");                                                                                                        \
     SgProfScope prof(st, flops, 2);                                                                                                                    \
     hipLaunchKernelGGL((k_tok_gemm<E>), grid, blk, 2 * TG_STAGE, st, (const bf16_t*)a, lda, (const bf16_t*)w, bias, out, ldo, M, N, K);                \
   }

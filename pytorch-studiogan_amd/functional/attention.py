@@ -184,7 +184,13 @@ def _attn_reference_graph(theta, phi, g, dims):
 
 
 class AttnPooledFn(torch.autograd.Function):
-    """the attention core on pooled keys / values: theta [B,H,W,Dp], phi [B,HW/4,Dp], g [B,HW/4,Cg] -> o [B,H,W,Cg]"""
+    """the attention core on pooled keys / values: theta [B,H,W,Dp], phi [B,HW/4,Dp], g [B,HW/4,Cg] -> o [B,H,W,Cg]. Two paths:
+      fused   (bf16 and sg_attn_fwd_flash_ok, and -- when a gradient is wanted -- sg_attn_bwd_fused_ok): one launch forward, sg_attn_bwd_fused backward;
+              scores and probabilities never reach HBM, keys and values stream through LDS (no bound on the number of keys: 16384 x 4096 scores per
+              image in BigGAN-deep-256's D, reference src/models/big_resnet_deep_legacy.py:80-95)
+      generic (everything else: fp32, small or unaligned shapes): fp32 scores by GEMM, sg_softmax_rows, P . g, and the GEMM / sg_softmax_rows_bwd backward.
+    The two predicates agree for every even H, W (tests/test_host_cpu.py). An odd H or W (HW4 != HW / 4), which the reference's SelfAttention cannot run
+    at all, can satisfy the forward's alone: with a gradient wanted it takes the generic chain."""
 
     @staticmethod
     def forward(ctx, theta, phi, g):
@@ -194,38 +200,23 @@ class AttnPooledFn(torch.autograd.Function):
         HW, HW4 = H * W, (H // 2) * (W // 2)
         dev, T = theta.device, theta.dtype
         sd = L.dt(T)
-        fused = T == torch.bfloat16 and L.lib().sg_attn_fused_ok(B, HW, HW4, Dp, Cg) == 1
-        # the bf16 probabilities are written only when a backward can come that needs them (they feed dg = P^T dO): never for the no-grad generator
-        # forwards of the discriminator update, nor when the backward recomputes them itself (sg_attn_bwd_fused: no P and no dS in HBM at all)
-        need_p = any(ctx.needs_input_grad) and L.lib().sg_attn_bwd_fused_ok(B, HW, HW4, Dp, Cg) != 1
-        if need_p:
-            fused_fwd = fused and L.lib().sg_attn_fwd_fused_ok(B, HW, HW4, Dp, Cg) == 1
-        else:
-            # keys and values streamed in 256-key chunks: no bound on the number of keys (16384 x 4096 scores per image in BigGAN-deep-256's D,
-            # reference src/models/big_resnet_deep_legacy.py:80-95, never exist in HBM)
-            fused_fwd = T == torch.bfloat16 and L.lib().sg_attn_fwd_flash_ok(B, HW, HW4, Dp, Cg) == 1
-        lse = o32 = None
-        if fused_fwd:
-            # one launch: scores, softmax and the product with the pooled values
-            P = torch.empty((B, HW, HW4), dtype=T, device=dev) if need_p else None
+        need_grad = any(ctx.needs_input_grad)
+        fused = (T == torch.bfloat16 and L.lib().sg_attn_fwd_flash_ok(B, HW, HW4, Dp, Cg) == 1
+                 and (not need_grad or L.lib().sg_attn_bwd_fused_ok(B, HW, HW4, Dp, Cg) == 1))
+        P = lse = o32 = None
+        o = torch.empty((B, H, W, Cg), dtype=T, device=dev)
+        if fused:
             lse = torch.empty((B, HW), dtype=torch.float32, device=dev)
-            o = torch.empty((B, H, W, Cg), dtype=T, device=dev)
             # the fused backward takes delta_q = dO_q . O_q from an unrounded fp32 copy of the output instead of a pass over the keys
-            o32 = torch.empty((B, HW, Cg), dtype=torch.float32, device=dev) if (P is None and any(ctx.needs_input_grad)) else None
-            L.call("sg_attn_fwd_fused", L.ptr(theta), L.ptr(phi), L.ptr(g), L.ptr(P), L.ptr(lse), L.ptr(o), L.ptr(o32), B, HW, HW4, Dp, Cg, L.stream())
+            o32 = torch.empty((B, HW, Cg), dtype=torch.float32, device=dev) if need_grad else None
+            L.call("sg_attn_fwd_fused", L.ptr(theta), L.ptr(phi), L.ptr(g), L.ptr(lse), L.ptr(o), L.ptr(o32), B, HW, HW4, Dp, Cg, L.stream())
         else:
+            S = torch.empty((B, HW, HW4), dtype=torch.float32, device=dev)
+            # S[q][k] = theta_q . phi_k
+            gemm_raw(sd, phi, 0, Dp, theta, 0, Dp, S, HW4, HW4, HW, Dp, batch=B, p_bs=HW4 * Dp, q_bs=HW * Dp, out_bs=HW * HW4, epi_flags=L.EPI_OUT_F32)
             P = torch.empty((B, HW, HW4), dtype=T, device=dev)
-            if fused:
-                # scores stay in registers: one pass writes the bf16 probabilities (csrc/attn.hip)
-                lse = torch.empty((B, HW), dtype=torch.float32, device=dev)
-                L.call("sg_attn_probs_fwd", L.ptr(theta), L.ptr(phi), L.ptr(P), L.ptr(lse), B, HW, HW4, Dp, L.stream())
-            else:
-                S = torch.empty((B, HW, HW4), dtype=torch.float32, device=dev)
-                # S[q][k] = theta_q . phi_k
-                gemm_raw(sd, phi, 0, Dp, theta, 0, Dp, S, HW4, HW4, HW, Dp, batch=B, p_bs=HW4 * Dp, q_bs=HW * Dp, out_bs=HW * HW4, epi_flags=L.EPI_OUT_F32)
-                L.call("sg_softmax_rows", sd, L.ptr(S), L.ptr(P), B * HW, HW4, L.stream())
-                del S
-            o = torch.empty((B, H, W, Cg), dtype=T, device=dev)
+            L.call("sg_softmax_rows", sd, L.ptr(S), L.ptr(P), B * HW, HW4, L.stream())
+            del S
             # o[q][c] = sum_k P[q][k] g[k][c]
             gemm_raw(sd, g, 1, Cg, P, 0, HW4, o, Cg, Cg, HW, HW4, batch=B, p_bs=HW4 * Cg, q_bs=HW * HW4, out_bs=HW * Cg)
         ctx.save_for_backward(theta, phi, g, P, lse, o32)
@@ -247,35 +238,27 @@ class AttnPooledFn(torch.autograd.Function):
         do = _c(do)
         dev, T = do.device, do.dtype
         sd = L.dt(T)
+        dtheta = torch.empty((B, H, W, Dp), dtype=T, device=dev)
+        dphi = torch.empty((B, HW4, Dp), dtype=T, device=dev)
+        dg = torch.empty((B, HW4, Cg), dtype=T, device=dev)
         if P is None:
             # fused backward (csrc/attn.hip k_attn_bwd_q / k_attn_bwd_k): P, dP and dS are recomputed per tile in registers on both the
             # query side (dtheta) and the key side (dphi, dg); only the row statistics (lse, delta) cross HBM
-            assert lse is not None
             delta = torch.empty((B, HW), dtype=torch.float32, device=dev)
-            dtheta = torch.empty((B, H, W, Dp), dtype=T, device=dev)
-            dphi = torch.empty((B, HW4, Dp), dtype=T, device=dev)
-            dg = torch.empty((B, HW4, Cg), dtype=T, device=dev)
             L.call("sg_attn_bwd_fused", L.ptr(theta), L.ptr(phi), L.ptr(g), L.ptr(do), L.ptr(o32), L.ptr(lse), L.ptr(delta), L.ptr(dtheta), L.ptr(dphi),
                    L.ptr(dg), B, HW, HW4, Dp, Cg, L.stream())
             return dtheta, dphi, dg
         # dg[k][c] = sum_q P[q][k] do[q][c]
-        dg = torch.empty((B, HW4, Cg), dtype=T, device=dev)
         gemm_raw(sd, do, 1, Cg, P, 1, HW4, dg, Cg, Cg, HW4, HW, batch=B, p_bs=HW * Cg, q_bs=HW * HW4, out_bs=HW4 * Cg)
+        # dP[q][k] = sum_c do[q][c] g[k][c]
+        dP = torch.empty((B, HW, HW4), dtype=torch.float32, device=dev)
+        gemm_raw(sd, g, 0, Cg, do, 0, Cg, dP, HW4, HW4, HW, Cg, batch=B, p_bs=HW4 * Cg, q_bs=HW * Cg, out_bs=HW * HW4, epi_flags=L.EPI_OUT_F32)
         dS = torch.empty((B, HW, HW4), dtype=T, device=dev)
-        if lse is not None:
-            # dS = P * (dP - sum_k P dP) with P and dP = dO . g^T recomputed in registers: no fp32 dP, no re-read of P (csrc/attn.hip)
-            L.call("sg_attn_ds_bwd", L.ptr(theta), L.ptr(phi), L.ptr(g), L.ptr(do), L.ptr(lse), L.ptr(dS), B, HW, HW4, Dp, Cg, L.stream())
-        else:
-            # dP[q][k] = sum_c do[q][c] g[k][c]
-            dP = torch.empty((B, HW, HW4), dtype=torch.float32, device=dev)
-            gemm_raw(sd, g, 0, Cg, do, 0, Cg, dP, HW4, HW4, HW, Cg, batch=B, p_bs=HW4 * Cg, q_bs=HW * Cg, out_bs=HW * HW4, epi_flags=L.EPI_OUT_F32)
-            L.call("sg_softmax_rows_bwd", sd, L.ptr(P), L.ptr(dP), L.ptr(dS), B * HW, HW4, L.stream())
-            del dP
+        L.call("sg_softmax_rows_bwd", sd, L.ptr(P), L.ptr(dP), L.ptr(dS), B * HW, HW4, L.stream())
+        del dP
         # dtheta[q][d] = sum_k dS[q][k] phi[k][d]
-        dtheta = torch.empty((B, H, W, Dp), dtype=T, device=dev)
         gemm_raw(sd, phi, 1, Dp, dS, 0, HW4, dtheta, Dp, Dp, HW, HW4, batch=B, p_bs=HW4 * Dp, q_bs=HW * HW4, out_bs=HW * Dp)
         # dphi[k][d] = sum_q dS[q][k] theta[q][d]
-        dphi = torch.empty((B, HW4, Dp), dtype=T, device=dev)
         gemm_raw(sd, theta, 1, Dp, dS, 1, HW4, dphi, Dp, Dp, HW4, HW, batch=B, p_bs=HW * Dp, q_bs=HW * HW4, out_bs=HW4 * Dp)
         return dtheta, dphi, dg
 

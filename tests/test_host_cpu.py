@@ -54,6 +54,25 @@ def test_abi_symbols_match_header():
     assert lib.sg_version() >= 1
 
 
+def test_attention_forward_and_backward_predicates_agree_on_even_sizes():
+    """functional.AttnPooledFn has two paths, the fused kernels of csrc/attn.hip forward AND backward or the generic GEMM chain both ways, and nothing that
+    stores probabilities for a backward the fused kernels cannot take: that leans on sg_attn_fwd_flash_ok == sg_attn_bwd_fused_ok wherever HW4 == HW / 4
+    (every even H, W: the only sizes the reference's SelfAttention.forward can run, src/utils/ops.py:83-100). The predicates run on the host."""
+    import studiogan_amd
+    lib = studiogan_amd.lib()
+    seen = set()
+    for H in range(2, 131, 2):
+        for W in range(2, 131, 2):
+            HW = H * W
+            for Dp in (0, 8, 16, 24, 32, 40):
+                for Cg in (4, 8, 40, 48, 96, 128, 136):
+                    for B in (1, 65535, 65536):
+                        f, b = lib.sg_attn_fwd_flash_ok(B, HW, HW // 4, Dp, Cg), lib.sg_attn_bwd_fused_ok(B, HW, HW // 4, Dp, Cg)
+                        assert f == b, (B, H, W, Dp, Cg, f, b)
+                        seen.add(f)
+    assert seen == {0, 1}, "the sample must hold supported and unsupported shapes"
+
+
 def test_engine_names_match_enum():
     """tests/util.py engine_launches reports launches per SG_ENG_* id: its names follow the enum of csrc/common.h one for one, and
     bench.py's table of the same ids has the same length, so a new engine cannot shift the ids unnoticed."""

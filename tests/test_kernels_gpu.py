@@ -440,13 +440,16 @@ def test_attention_core(sg, dtype, shape, monkeypatch):
     from studiogan_amd import functional as F, _lib as L
     d = dev()
     B, H, W, Dp, Dv, Cg = shape
+    ok = [fn(B, H * W, H * W // 4, Dp, Cg) for fn in (L.lib().sg_attn_fwd_flash_ok, L.lib().sg_attn_bwd_fused_ok)]
     if H * W > 8192:
         if dtype == torch.float32:
             pytest.skip("the 16384-query shape is the bf16 streaming path's case")
-        assert L.lib().sg_attn_fwd_flash_ok(B, H * W, H * W // 4, Dp, Cg) == 1 and L.lib().sg_attn_bwd_fused_ok(B, H * W, H * W // 4, Dp, Cg) == 1
-        calls = []
-        orig = L.call
-        monkeypatch.setattr(L, "call", lambda name, *a: (calls.append(name), orig(name, *a))[1])
+        assert ok == [1, 1]
+    assert ok == ([0, 0] if H * W == 64 else [1, 1]), ok
+    fused = dtype == torch.bfloat16 and ok == [1, 1]
+    calls = []
+    orig = L.call
+    monkeypatch.setattr(L, "call", lambda name, *a: (calls.append(name), orig(name, *a))[1])
     tol = 5e-4 if dtype == torch.float32 else 3e-2
     th = rnd((B, Dp, H, W), dtype, 61, 0.5); th[:, Dv:] = 0
     ph = rnd((B, Dp, H, W), dtype, 62, 0.5); ph[:, Dv:] = 0
@@ -467,8 +470,11 @@ def test_attention_core(sg, dtype, shape, monkeypatch):
     check("attn dtheta", nchw(thd.grad.float().cpu())[:, :Dv], thr.grad[:, :Dv], tol)
     check("attn dphi", nchw(phd.grad.float().cpu())[:, :Dv], phr.grad[:, :Dv], tol)
     check("attn dg", nchw(gd.grad.float().cpu()), gr.grad, tol)
-    if H * W > 8192:
-        assert "sg_attn_fwd_fused" in calls and "sg_attn_bwd_fused" in calls and "sg_gemm" not in calls and "sg_softmax_rows" not in calls, calls
+    # the two paths of AttnPooledFn: the fused kernels both ways, or the generic GEMM + softmax chain both ways (fp32; the 8 x 8 shape)
+    for name in ("sg_attn_fwd_fused", "sg_attn_bwd_fused"):
+        assert (name in calls) == fused, (name, calls)
+    for name in ("sg_gemm", "sg_softmax_rows", "sg_softmax_rows_bwd"):
+        assert (name in calls) == (not fused), (name, calls)
 
 
 @pytest.mark.parametrize("shape", [(2, 32, 16, 48, 0.5), (1, 32, 32, 96, 3.0), (1, 64, 32, 40, 6.0)])
@@ -629,11 +635,32 @@ def test_no_cpu_fallback(sg):
         m(torch.randn(1, 4, 8, 8))
 
 
+# max |lse - fp64 logsumexp| of k_attn_fwd_flash on MI355X, measured on the commit before the stored-probability kernels left, at the four shapes of the
+# two tests below: 1.49e-6, 1.31e-6, 1.84e-6, 1.88e-6 on the forward test's inputs, 1.74e-6, 1.60e-6, 2.38e-6, 2.09e-6 on the backward test's (|lse| up to 17)
+LSE_MEASURED = 2.375e-6
+LSE_TOL = 2 * LSE_MEASURED
+
+
+def _attn_generic_forward(theta, phi, g):
+    """the generic forward exactly as functional.AttnPooledFn spells it: fp32 scores by GEMM -> sg_softmax_rows -> bf16 P -> P . g by GEMM; returns (P, o)"""
+    from studiogan_amd import functional as F, _lib as L
+    (B, HW, Dp), HW4, Cg, T = theta.shape, phi.shape[1], g.shape[2], theta.dtype
+    S = torch.empty((B, HW, HW4), dtype=torch.float32, device=theta.device)
+    F.gemm_raw(L.BF16, phi, 0, Dp, theta, 0, Dp, S, HW4, HW4, HW, Dp, batch=B, p_bs=HW4 * Dp, q_bs=HW * Dp, out_bs=HW * HW4, epi_flags=L.EPI_OUT_F32)
+    P = torch.empty((B, HW, HW4), dtype=T, device=theta.device)
+    L.call("sg_softmax_rows", L.BF16, L.ptr(S), L.ptr(P), B * HW, HW4, L.stream())
+    o = torch.empty((B, HW, Cg), dtype=T, device=theta.device)
+    F.gemm_raw(L.BF16, g, 1, Cg, P, 0, HW4, o, Cg, Cg, HW, HW4, batch=B, p_bs=HW4 * Cg, q_bs=HW * HW4, out_bs=HW * Cg)
+    return P, o
+
+
 @pytest.mark.parametrize("shape", [(3, 32, 32, 24, 96), (2, 32, 32, 16, 48), (2, 64, 32, 32, 40), (1, 64, 64, 16, 48)])
 def test_attention_fused_forward_matches_unfused_chain(sg, shape):
-    """sg_attn_fwd_fused (scores, softmax and P.V in one launch) against the chain it replaces (sg_attn_probs_fwd + batched GEMM) on the
-    same inputs: identical probabilities / log-sum-exp, the output to fp32-summation-order differences of bf16 products; and without
-    the probability store (no-grad forward)."""
+    """sg_attn_fwd_fused (scores, softmax and P.V in one launch, k_attn_fwd_flash) against the generic chain of functional.AttnPooledFn (fp32 scores by GEMM,
+    sg_softmax_rows, P . g by GEMM) on the same inputs: the output to fp32-summation-order differences of bf16 products, the fp32 copy of O rounding to
+    the bf16 output bit for bit, and the row log-sum-exp against an fp64 logsumexp of the same bf16 inputs.
+    lse bound: LSE_TOL = 4.75e-6 = twice the worst |lse - fp64| measured for this kernel (2.375e-6, see LSE_MEASURED); the same measurement gave
+    4.2e-3, 5.7e-3, 5.2e-3 and 7.5e-3 for the output against the generic chain at the four shapes (bound 8e-3, kept)."""
     from studiogan_amd import functional as F, _lib as L
     d = dev()
     B, H, W, Dp, Cg = shape
@@ -642,36 +669,29 @@ def test_attention_fused_forward_matches_unfused_chain(sg, shape):
     theta = rnd((B, HW, Dp), T, 71, 0.7).to(d)
     phi = rnd((B, HW4, Dp), T, 72, 0.7).to(d)
     g = rnd((B, HW4, Cg), T, 73).to(d)
-    assert L.lib().sg_attn_fwd_fused_ok(B, HW, HW4, Dp, Cg) == 1
-    P0 = torch.empty((B, HW, HW4), dtype=T, device=d)
-    lse0 = torch.empty((B, HW), dtype=torch.float32, device=d)
-    L.call("sg_attn_probs_fwd", L.ptr(theta), L.ptr(phi), L.ptr(P0), L.ptr(lse0), B, HW, HW4, Dp, L.stream())
-    o0 = torch.empty((B, HW, Cg), dtype=T, device=d)
-    F.gemm_raw(L.BF16, g, 1, Cg, P0, 0, HW4, o0, Cg, Cg, HW, HW4, batch=B, p_bs=HW4 * Cg, q_bs=HW * HW4, out_bs=HW * Cg)
-    for store in (True, False):
-        P1 = torch.zeros((B, HW, HW4), dtype=T, device=d) if store else None
-        lse1 = torch.empty((B, HW), dtype=torch.float32, device=d)
-        o1 = torch.empty((B, HW, Cg), dtype=T, device=d)
-        o32 = None if store else torch.empty((B, HW, Cg), dtype=torch.float32, device=d)
-        L.call("sg_attn_fwd_fused", L.ptr(theta), L.ptr(phi), L.ptr(g), L.ptr(P1), L.ptr(lse1), L.ptr(o1), L.ptr(o32), B, HW, HW4, Dp, Cg, L.stream())
-        torch.cuda.synchronize()
-        if o32 is not None:
-            assert torch.equal(o32.to(T), o1), "the fp32 copy of O must round to the bf16 output"
-        if store:
-            assert torch.equal(P1, P0), "fused forward must store the same bf16 probabilities"
-            assert torch.equal(lse1, lse0)
-        else:   # max pass + unnormalised pass (k_attn_fwd_flash): same statistics up to the summation order / exp2 form
-            assert (lse1 - lse0).abs().max().item() < 2e-5
-        check(f"fused attention output (store_p={store})", o1.float().cpu(), o0.float().cpu(), 8e-3)
+    assert L.lib().sg_attn_fwd_flash_ok(B, HW, HW4, Dp, Cg) == 1
+    P0, o0 = _attn_generic_forward(theta, phi, g)
+    lse1 = torch.empty((B, HW), dtype=torch.float32, device=d)
+    o1 = torch.empty((B, HW, Cg), dtype=T, device=d)
+    o32 = torch.empty((B, HW, Cg), dtype=torch.float32, device=d)
+    L.call("sg_attn_fwd_fused", L.ptr(theta), L.ptr(phi), L.ptr(g), L.ptr(lse1), L.ptr(o1), L.ptr(o32), B, HW, HW4, Dp, Cg, L.stream())
+    torch.cuda.synchronize()
+    assert torch.equal(o32.to(T), o1), "the fp32 copy of O must round to the bf16 output"
+    S = theta.double().cpu() @ phi.double().cpu().transpose(1, 2)
+    lse_err = (lse1.double().cpu() - torch.logsumexp(S, -1)).abs().max().item()
+    print(f"lse vs fp64 logsumexp: max abs err {lse_err:.3e} (bound {LSE_TOL:.1e})")
+    assert lse_err <= LSE_TOL
+    check("fused attention output vs generic chain", o1.float().cpu(), o0.float().cpu(), 8e-3)
     # against fp64 softmax(theta phi^T) g
-    ref = torch.softmax(theta.double().cpu() @ phi.double().cpu().transpose(1, 2), -1) @ g.double().cpu()
+    ref = torch.softmax(S, -1) @ g.double().cpu()
     check("fused attention vs fp64", o1.float().cpu(), ref, 3e-2)
 
 
 @pytest.mark.parametrize("shape", [(3, 32, 32, 24, 96), (2, 32, 32, 16, 48), (2, 64, 32, 32, 40), (1, 64, 64, 16, 48)])
 def test_attention_fused_backward_matches_unfused_chain(sg, shape):
     """sg_attn_bwd_fused (query side: delta, dS in registers, dtheta; key side: P and dS recomputed in the transposed orientation, dphi, dg)
-    against the chain it replaces (stored P, sg_attn_ds_bwd + three batched GEMMs) and against fp64 autograd of softmax(theta phi^T) g."""
+    against the generic chain of functional.AttnPooledFn (P from sg_softmax_rows, dg = P^T dO, fp32 dP, sg_softmax_rows_bwd, two more batched GEMMs) and
+    against fp64 autograd of softmax(theta phi^T) g."""
     from studiogan_amd import functional as F, _lib as L
     d = dev()
     B, H, W, Dp, Cg = shape
@@ -682,14 +702,14 @@ def test_attention_fused_backward_matches_unfused_chain(sg, shape):
     g = rnd((B, HW4, Cg), T, 83).to(d)
     do = rnd((B, HW, Cg), T, 84).to(d)
     assert L.lib().sg_attn_bwd_fused_ok(B, HW, HW4, Dp, Cg) == 1
-    P = torch.empty((B, HW, HW4), dtype=T, device=d)
-    lse = torch.empty((B, HW), dtype=torch.float32, device=d)
-    L.call("sg_attn_probs_fwd", L.ptr(theta), L.ptr(phi), L.ptr(P), L.ptr(lse), B, HW, HW4, Dp, L.stream())
+    P, _ = _attn_generic_forward(theta, phi, g)
     sd = L.BF16
     dg0 = torch.empty((B, HW4, Cg), dtype=T, device=d)
     F.gemm_raw(sd, do, 1, Cg, P, 1, HW4, dg0, Cg, Cg, HW4, HW, batch=B, p_bs=HW * Cg, q_bs=HW * HW4, out_bs=HW4 * Cg)
+    dP = torch.empty((B, HW, HW4), dtype=torch.float32, device=d)
+    F.gemm_raw(sd, g, 0, Cg, do, 0, Cg, dP, HW4, HW4, HW, Cg, batch=B, p_bs=HW4 * Cg, q_bs=HW * Cg, out_bs=HW * HW4, epi_flags=L.EPI_OUT_F32)
     dS = torch.empty((B, HW, HW4), dtype=T, device=d)
-    L.call("sg_attn_ds_bwd", L.ptr(theta), L.ptr(phi), L.ptr(g), L.ptr(do), L.ptr(lse), L.ptr(dS), B, HW, HW4, Dp, Cg, L.stream())
+    L.call("sg_softmax_rows_bwd", sd, L.ptr(P), L.ptr(dP), L.ptr(dS), B * HW, HW4, L.stream())
     dth0 = torch.empty((B, HW, Dp), dtype=T, device=d)
     F.gemm_raw(sd, phi, 1, Dp, dS, 0, HW4, dth0, Dp, Dp, HW, HW4, batch=B, p_bs=HW4 * Dp, q_bs=HW * HW4, out_bs=HW * Dp)
     dph0 = torch.empty((B, HW4, Dp), dtype=T, device=d)
@@ -698,14 +718,14 @@ def test_attention_fused_backward_matches_unfused_chain(sg, shape):
     o = torch.softmax(tr @ pr.transpose(1, 2), -1) @ gr
     o.backward(do.double().cpu())
     # the forward output as the product path keeps it for the backward (unrounded fp32 copy from the fused forward): delta_q = dO_q . O_q
-    lse_f = torch.empty((B, HW), dtype=torch.float32, device=d)
+    lse = torch.empty((B, HW), dtype=torch.float32, device=d)
     o_f = torch.empty((B, HW, Cg), dtype=T, device=d)
     o32 = torch.empty((B, HW, Cg), dtype=torch.float32, device=d)
-    L.call("sg_attn_fwd_fused", L.ptr(theta), L.ptr(phi), L.ptr(g), None, L.ptr(lse_f), L.ptr(o_f), L.ptr(o32), B, HW, HW4, Dp, Cg, L.stream())
-    for what, o_arg, lse_arg in (("delta from a key pass", None, lse), ("delta = dO . O", o32, lse_f)):
+    L.call("sg_attn_fwd_fused", L.ptr(theta), L.ptr(phi), L.ptr(g), L.ptr(lse), L.ptr(o_f), L.ptr(o32), B, HW, HW4, Dp, Cg, L.stream())
+    for what, o_arg in (("delta from a key pass", None), ("delta = dO . O", o32)):
         delta = torch.empty((B, HW), dtype=torch.float32, device=d)
         dth1, dph1, dg1 = torch.empty_like(dth0), torch.empty_like(dph0), torch.empty_like(dg0)
-        L.call("sg_attn_bwd_fused", L.ptr(theta), L.ptr(phi), L.ptr(g), L.ptr(do), L.ptr(o_arg), L.ptr(lse_arg), L.ptr(delta), L.ptr(dth1), L.ptr(dph1),
+        L.call("sg_attn_bwd_fused", L.ptr(theta), L.ptr(phi), L.ptr(g), L.ptr(do), L.ptr(o_arg), L.ptr(lse), L.ptr(delta), L.ptr(dth1), L.ptr(dph1),
                L.ptr(dg1), B, HW, HW4, Dp, Cg, L.stream())
         torch.cuda.synchronize()
         check(f"fused bwd dtheta vs chain ({what})", dth1.float().cpu(), dth0.float().cpu(), 1e-2)

@@ -2,7 +2,8 @@
 benchmarked shapes, bf16:
     python tools/attn_bench.py [--iters 10]
 G of C3: batch 256, 64 x 64, 24 (padded 32) -> 96 channels; D of C3: 64 x 64, 12 (16) -> 48; D of C4 at 256^2: batch 64, 128 x 128, 32 -> 128.
-TF = MFMA FLOPs of the formulation (forward: scores twice -- max pass + main pass -- and P.V; backward: scores and dP on both sides, dtheta, dphi, dg) / time."""
+TF = FLOPs of the formula below / time. The forward makes ONE pass over the keys (scores and P.V); the formula still counts its scores twice, as when a
+max pass preceded the main pass: it is the convention of the recorded numbers. Backward: scores and dP on both sides, dtheta, dphi, dg."""
 import argparse
 import os
 import sys
