@@ -76,11 +76,20 @@ typedef struct {
   int ldo, ldr, ldm;
 } sg_conv_fwd_desc;
 int sg_conv2d_fwd(const sg_conv_fwd_desc* d, sg_stream_t stream);
-/* fp32 arithmetic of sg_conv2d_fwd's generic engine (process-wide; default 0): 0 = v_mfma_f32_32x32x2_f32, the exact fp32 FMA chain; 3 = "bf16x3": each fp32
+/* fp32 arithmetic of the generic engine (process-wide; default 0): 0 = v_mfma_f32_32x32x2_f32, the exact fp32 FMA chain; 3 = "bf16x3": each fp32
  * operand element is split into two bf16 terms in registers and a 16-wide k-tile runs as three bf16 MFMAs with fp32 accumulation (~2^-16 relative per
- * product, 5.3x the matrix-pipe rate). fp32 tensors in and out either way. Used by the FID / IS feature extractor (metrics.InceptionV3 f32_mode). */
+ * product, 5.3x the matrix-pipe rate); convolutions only (forward, data gradient, weight gradient). 6 = "bf16x6": three bf16 terms per element
+ * (h = bf16(x), m = bf16(x - h), l = bf16(x - h - m): x == h + m + l exactly) and the six products hh, hm, mh, mm, hl, lh per k-tile, fp32 accumulation;
+ * what is dropped (ml, lm, ll) is at most 2^-25 of a product, below fp32's own rounding of it (2.67x the matrix-pipe rate of mode 0). Mode 6 covers the
+ * convolutions AND the fp32 sg_gemm. Either split mode applies to all-vector operands only (16-byte aligned, channel counts / pitches multiples of 4);
+ * anything else keeps the exact MFMA. fp32 tensors in and out in every mode. Operand values beyond bf16's finite range (|x| > 3.39e38) overflow to
+ * infinity in the first term of a split: modes 3 and 6 are for finite data inside that range. Any other mode value is refused (-1).
+ * Used by the FID / IS feature extractors (metrics.InceptionV3 / metrics.DINOViT f32_mode). */
 int sg_set_f32_mode(int mode);
 int sg_get_f32_mode(void);
+/* number of launches so far that took the split path of `mode` (3 or 6; -1 for any other value): a relaxed atomic counter, for tests that have to
+ * prove which arithmetic ran */
+long long sg_f32_split_launches(int mode);
 
 /* Residual-block tail in ONE launch (bf16): out = epilogue( alpha * [ conv3x3(x; w) + conv1x1(up2?(x2); w2) ] + bias + bias2 ).
  * Replaces `x0 = conv2d0(x0); out = x + x0` of the reference's blocks (src/models/big_resnet.py:28-42 GenBlock with nearest x2 on the

@@ -154,7 +154,9 @@ __device__ __forceinline__ float block_max_256(float v, float* sm) {
 
 // error reporting shared by every C-ABI entry point (capi.cpp owns the storage)
 extern "C" void sg_set_error(const char* msg);
-extern int g_sg_f32_mode;      // fp32 arithmetic of the generic engine (conv.hip sg_set_f32_mode): 0 exact fp32 MFMA, 3 bf16x3 split
+extern int g_sg_f32_mode;      // fp32 arithmetic of the generic engine (conv.hip sg_set_f32_mode): 0 exact fp32 MFMA, 3 bf16x3 split, 6 bf16x6 split
+extern long long g_sg_f32_split_launches[2];   // launches that took the split path of mode 3 / mode 6 (conv.hip sg_f32_split_launches)
+static inline void sg_f32_split_count(int mode) { __atomic_fetch_add(&g_sg_f32_split_launches[mode == 6], 1, __ATOMIC_RELAXED); }
 extern "C" int sg_prof_begin(hipStream_t st, double flops, int kind);
 extern "C" int sg_prof_begin_q(hipStream_t st, double flops, int kind);
 extern "C" void sg_prof_end(hipStream_t st, int slot);

@@ -5,14 +5,27 @@
 #include "conv_common.h"
 #include "conv_v2.h"
 
-// fp32 arithmetic mode of the generic engine's convolutions -- forward, data gradient (here) and weight gradient (conv_wgrad.hip) -- (sg_set_f32_mode): 0 = exact fp32 MFMA, 3 = bf16x3 split (gemm_core.h SPLIT)
+// fp32 arithmetic mode of the generic engine (sg_set_f32_mode): 0 = exact fp32 MFMA; 3 = bf16x3 split (gemm_core.h SPLIT): the convolutions -- forward, data
+// gradient (here) and weight gradient (conv_wgrad.hip); 6 = bf16x6 split: the same convolutions and the fp32 sg_gemm (gemm.hip)
 int g_sg_f32_mode = 0;
+long long g_sg_f32_split_launches[2] = {0, 0};
 extern "C" int sg_set_f32_mode(int mode) {
-  SG_CHECK(mode == 0 || mode == 3, "sg_set_f32_mode: 0 (exact fp32 MFMA) or 3 (bf16x3 split)");
+  SG_CHECK(mode == 0 || mode == 3 || mode == 6, "sg_set_f32_mode: 0 (exact fp32 MFMA), 3 (bf16x3 split) or 6 (bf16x6 split)");
   g_sg_f32_mode = mode;
   return 0;
 }
 extern "C" int sg_get_f32_mode() { return g_sg_f32_mode; }
+extern "C" long long sg_f32_split_launches(int mode) {
+  if (mode != 3 && mode != 6) return -1;
+  return __atomic_load_n(&g_sg_f32_split_launches[mode == 6], __ATOMIC_RELAXED);
+}
+
+template <typename T, class LP, class LQ, int SPLIT>
+static void conv_fwd_tiles(const LP& lp, const LQ& lq, const Epilogue<T>& e, int I, int J, int K, hipStream_t st) {
+  if (I <= 32) sg_launch_gemm<T, LP, LQ, 32, 256, 1, 4, true, SPLIT>(lp, lq, e, I, J, K, 1, 1, st);
+  else if (I % 128 != 0 && (I % 96 == 0 || (I < 128 && I > 64))) sg_launch_gemm<T, LP, LQ, 96, 256, 1, 4, true, SPLIT>(lp, lq, e, I, J, K, 1, 1, st);
+  else sg_launch_gemm<T, LP, LQ, 128, 128, 2, 2, true, SPLIT>(lp, lq, e, I, J, K, 1, 1, st);
+}
 
 template <typename T, bool FAST>
 static void conv_fwd_launch(const sg_conv_fwd_desc* d, const Epilogue<T>& e, int I, int J, int K, int pflags, hipStream_t st) {
@@ -24,17 +37,12 @@ static void conv_fwd_launch(const sg_conv_fwd_desc* d, const Epilogue<T>& e, int
   LQ lq;
   fill_geom<T>(lq.g, d->x, d->N, d->Hs, d->Ws, d->C, d->ldx, d->Ho, d->Wo, d->R, d->S, d->stride, d->pad_h, d->pad_w, pflags);
   lq.rows = J; lq.K = K;
-  if constexpr (sizeof(T) == 4 && FAST) {
-    if (g_sg_f32_mode == 3) {      // fp32 in / fp32 out, three bf16 MFMAs per k-tile (all-vector operands only: the Inception stack, the fp32 backbones' aligned layers)
-      if (I <= 32) sg_launch_gemm<T, LP, LQ, 32, 256, 1, 4, true, 3>(lp, lq, e, I, J, K, 1, 1, st);
-      else if (I % 128 != 0 && (I % 96 == 0 || (I < 128 && I > 64))) sg_launch_gemm<T, LP, LQ, 96, 256, 1, 4, true, 3>(lp, lq, e, I, J, K, 1, 1, st);
-      else sg_launch_gemm<T, LP, LQ, 128, 128, 2, 2, true, 3>(lp, lq, e, I, J, K, 1, 1, st);
-      return;
-    }
+  if constexpr (sizeof(T) == 4 && FAST) {      // fp32 in / fp32 out on the bf16 MFMA (all-vector operands only: the Inception stack, the fp32 backbones' aligned layers)
+    const int mode = g_sg_f32_mode;
+    if (mode == 3) { sg_f32_split_count(3); return conv_fwd_tiles<T, LP, LQ, 3>(lp, lq, e, I, J, K, st); }      // three MFMAs per k-tile
+    if (mode == 6) { sg_f32_split_count(6); return conv_fwd_tiles<T, LP, LQ, 6>(lp, lq, e, I, J, K, st); }      // six
   }
-  if (I <= 32) sg_launch_gemm<T, LP, LQ, 32, 256, 1, 4>(lp, lq, e, I, J, K, 1, 1, st);
-  else if (I % 128 != 0 && (I % 96 == 0 || (I < 128 && I > 64))) sg_launch_gemm<T, LP, LQ, 96, 256, 1, 4>(lp, lq, e, I, J, K, 1, 1, st);
-  else sg_launch_gemm<T, LP, LQ, 128, 128, 2, 2>(lp, lq, e, I, J, K, 1, 1, st);
+  conv_fwd_tiles<T, LP, LQ, 0>(lp, lq, e, I, J, K, st);
 }
 
 // second-generation kernel (conv_v2.h) for the hot bf16 shapes; returns false when the problem is not eligible

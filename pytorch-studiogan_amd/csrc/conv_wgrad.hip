@@ -283,6 +283,14 @@ static void splitk_reduce_launch(const float* partial, float* out, int splits, l
   }
 }
 
+template <typename T, class LM, bool TR, int SPLIT>
+static void conv_wgrad_tiles(const LM& lp, const LM& lq, const Epilogue<T>& e, int I, int J, int K, int BI, int BJ, int splits, hipStream_t st) {
+  if (BI == 32) sg_launch_gemm<T, LM, LM, 32, 256, 1, 4, TR, SPLIT>(lp, lq, e, I, J, K, splits, 1, st);
+  else if (BJ == 32) sg_launch_gemm<T, LM, LM, 256, 32, 4, 1, TR, SPLIT>(lp, lq, e, I, J, K, splits, 1, st);
+  else if (BJ == 96) sg_launch_gemm<T, LM, LM, 256, 96, 4, 1, TR, SPLIT>(lp, lq, e, I, J, K, splits, 1, st);
+  else sg_launch_gemm<T, LM, LM, 128, 128, 2, 2, TR, SPLIT>(lp, lq, e, I, J, K, splits, 1, st);
+}
+
 template <typename T, bool TR, bool FAST>
 static void conv_wgrad_launch(const sg_conv_wgrad_desc* d, const Epilogue<T>& e, int I, int J, int K, int BI, int BJ, int splits, hipStream_t st) {
   typedef ConvPixMC<T, FAST> LM;
@@ -293,19 +301,12 @@ static void conv_wgrad_launch(const sg_conv_wgrad_desc* d, const Epilogue<T>& e,
   LM lq;
   fill_geom<T>(lq.g, d->dy, d->N, d->gHs, d->gWs, d->Cout, d->ldg, d->Ho, d->Wo, 1, 1, 1, 0, 0, d->g_flags & ~SG_PIX_QUAD);
   lq.rows = J; lq.K = K;
-  if constexpr (sizeof(T) == 4 && FAST) {
-    if (g_sg_f32_mode == 3) {      // bf16x3 split (gemm_core.h SPLIT): fp32 operands, three bf16 MFMAs per 16 pixels of the reduction
-      if (BI == 32) sg_launch_gemm<T, LM, LM, 32, 256, 1, 4, TR, 3>(lp, lq, e, I, J, K, splits, 1, st);
-      else if (BJ == 32) sg_launch_gemm<T, LM, LM, 256, 32, 4, 1, TR, 3>(lp, lq, e, I, J, K, splits, 1, st);
-      else if (BJ == 96) sg_launch_gemm<T, LM, LM, 256, 96, 4, 1, TR, 3>(lp, lq, e, I, J, K, splits, 1, st);
-      else sg_launch_gemm<T, LM, LM, 128, 128, 2, 2, TR, 3>(lp, lq, e, I, J, K, splits, 1, st);
-      return;
-    }
+  if constexpr (sizeof(T) == 4 && FAST) {      // split modes (gemm_core.h SPLIT): fp32 operands, three or six bf16 MFMAs per 16 pixels of the reduction
+    const int mode = g_sg_f32_mode;
+    if (mode == 3) { sg_f32_split_count(3); return conv_wgrad_tiles<T, LM, TR, 3>(lp, lq, e, I, J, K, BI, BJ, splits, st); }
+    if (mode == 6) { sg_f32_split_count(6); return conv_wgrad_tiles<T, LM, TR, 6>(lp, lq, e, I, J, K, BI, BJ, splits, st); }
   }
-  if (BI == 32) sg_launch_gemm<T, LM, LM, 32, 256, 1, 4, TR>(lp, lq, e, I, J, K, splits, 1, st);
-  else if (BJ == 32) sg_launch_gemm<T, LM, LM, 256, 32, 4, 1, TR>(lp, lq, e, I, J, K, splits, 1, st);
-  else if (BJ == 96) sg_launch_gemm<T, LM, LM, 256, 96, 4, 1, TR>(lp, lq, e, I, J, K, splits, 1, st);
-  else sg_launch_gemm<T, LM, LM, 128, 128, 2, 2, TR>(lp, lq, e, I, J, K, splits, 1, st);
+  conv_wgrad_tiles<T, LM, TR, 0>(lp, lq, e, I, J, K, BI, BJ, splits, st);
 }
 
 // algorithmic HBM bytes of a weight gradient: x and dy once (stored sizes), the fp32 gradient read and written

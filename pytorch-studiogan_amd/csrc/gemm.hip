@@ -5,14 +5,25 @@
 
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-template <typename T, class LP, class LQ, bool TR>
+template <typename T, class LP, class LQ, bool TR, int SPLIT>
+static void gemm_tiles(const LP& lp, const LQ& lq, const Epilogue<T>& e, int I, int J, int K, int splits, int batch, hipStream_t st) {
+  if (I <= 32) sg_launch_gemm<T, LP, LQ, 32, 256, 1, 4, TR, SPLIT>(lp, lq, e, I, J, K, splits, batch, st);
+  else if (I % 128 != 0 && (I % 96 == 0 || (I < 128 && I > 64))) sg_launch_gemm<T, LP, LQ, 96, 256, 1, 4, TR, SPLIT>(lp, lq, e, I, J, K, splits, batch, st);
+  else sg_launch_gemm<T, LP, LQ, 128, 128, 2, 2, TR, SPLIT>(lp, lq, e, I, J, K, splits, batch, st);
+}
+
+template <typename T, class LP, class LQ, bool TR, bool FAST>
 static int gemm_launch(const LP& lp, const LQ& lq, const Epilogue<T>& e, const sg_gemm_desc* d, hipStream_t st) {
   const int I = d->I, J = d->J, K = d->K;
   const int splits = d->splits > 1 ? d->splits : 1;
   const int prof = sg_prof_begin(st, 2.0 * (double)I * (double)J * (double)K * (double)d->batch, 2);
-  if (I <= 32) sg_launch_gemm<T, LP, LQ, 32, 256, 1, 4, TR>(lp, lq, e, I, J, K, splits, d->batch, st);
-  else if (I % 128 != 0 && (I % 96 == 0 || (I < 128 && I > 64))) sg_launch_gemm<T, LP, LQ, 96, 256, 1, 4, TR>(lp, lq, e, I, J, K, splits, d->batch, st);
-  else sg_launch_gemm<T, LP, LQ, 128, 128, 2, 2, TR>(lp, lq, e, I, J, K, splits, d->batch, st);
+  // bf16x6 (gemm_core.h SPLIT) is fp32-faithful: every all-vector fp32 contraction takes it; mode 3 stays convolution-only
+  const int mode = (sizeof(T) == 4 && FAST && g_sg_f32_mode == 6) ? 6 : 0;
+  if (mode == 6) {
+    if constexpr (sizeof(T) == 4 && FAST) { sg_f32_split_count(6); gemm_tiles<T, LP, LQ, TR, 6>(lp, lq, e, I, J, K, splits, d->batch, st); }
+  } else {
+    gemm_tiles<T, LP, LQ, TR, 0>(lp, lq, e, I, J, K, splits, d->batch, st);
+  }
   sg_prof_end(st, prof);
   SG_LAUNCH_CHECK();
   return 0;
@@ -32,16 +43,16 @@ template <typename T, bool TR, bool FAST> static int gemm_forms(const Epilogue<T
   typedef StridedMC<T, FAST> MCL;
   if (d->p_form == 0 && d->q_form == 0) {
     KCL lp, lq; fill_kc<T>(lp, d->p, d->p_bstride, d->ldp, d->I, d->K); fill_kc<T>(lq, d->q, d->q_bstride, d->ldq, d->J, d->K);
-    return gemm_launch<T, KCL, KCL, TR>(lp, lq, e, d, st);
+    return gemm_launch<T, KCL, KCL, TR, FAST>(lp, lq, e, d, st);
   } else if (d->p_form == 0 && d->q_form == 1) {
     KCL lp; MCL lq; fill_kc<T>(lp, d->p, d->p_bstride, d->ldp, d->I, d->K); fill_mc<T>(lq, d->q, d->q_bstride, d->ldq, d->J, d->K);
-    return gemm_launch<T, KCL, MCL, TR>(lp, lq, e, d, st);
+    return gemm_launch<T, KCL, MCL, TR, FAST>(lp, lq, e, d, st);
   } else if (d->p_form == 1 && d->q_form == 0) {
     MCL lp; KCL lq; fill_mc<T>(lp, d->p, d->p_bstride, d->ldp, d->I, d->K); fill_kc<T>(lq, d->q, d->q_bstride, d->ldq, d->J, d->K);
-    return gemm_launch<T, MCL, KCL, TR>(lp, lq, e, d, st);
+    return gemm_launch<T, MCL, KCL, TR, FAST>(lp, lq, e, d, st);
   } else {
     MCL lp, lq; fill_mc<T>(lp, d->p, d->p_bstride, d->ldp, d->I, d->K); fill_mc<T>(lq, d->q, d->q_bstride, d->ldq, d->J, d->K);
-    return gemm_launch<T, MCL, MCL, TR>(lp, lq, e, d, st);
+    return gemm_launch<T, MCL, MCL, TR, FAST>(lp, lq, e, d, st);
   }
 }
 

@@ -439,6 +439,41 @@ __device__ __forceinline__ void frag_mc_f32_split(const char* tile, int pitch, i
   lo = __builtin_bit_cast(bf16x8_t, r);
 }
 
+// SPLIT = 6 ("bf16x6"): three bf16 terms per element, x == hi + mid + lo exactly for every fp32 x inside bf16's finite range (8 + 8 + 8 significand bits, each
+// term the round-to-nearest-even pack of the fp32 remainder before it; both remainders are exact in fp32).
+__device__ __forceinline__ void f32x8_split3(const float (&x)[8], bf16x8_t& hi, bf16x8_t& mid, bf16x8_t& lo) {
+  u32x4 h, m, r;
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    const uint32_t hp = pack2bf(x[2 * e], x[2 * e + 1]);
+    const float r0 = x[2 * e] - __uint_as_float(hp << 16), r1 = x[2 * e + 1] - __uint_as_float(hp & 0xffff0000u);
+    const uint32_t mp = pack2bf(r0, r1);
+    h[e] = hp;
+    m[e] = mp;
+    r[e] = pack2bf(r0 - __uint_as_float(mp << 16), r1 - __uint_as_float(mp & 0xffff0000u));
+  }
+  hi = __builtin_bit_cast(bf16x8_t, h);
+  mid = __builtin_bit_cast(bf16x8_t, m);
+  lo = __builtin_bit_cast(bf16x8_t, r);
+}
+// [row][k] image: the addresses of frag_kc_f32_split
+__device__ __forceinline__ void frag_kc_f32_split3(const char* tile, int row0, bf16x8_t& hi, bf16x8_t& mid, bf16x8_t& lo) {
+  const int l = threadIdx.x & 63;
+  const char* p = tile + (row0 + (l & 31)) * SG_KC_STRIDE + 32 * (l >> 5);
+  const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 16);
+  const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+  f32x8_split3(x, hi, mid, lo);
+}
+// [k][row] image: the addresses of frag_mc_f32_split
+__device__ __forceinline__ void frag_mc_f32_split3(const char* tile, int pitch, int row0, bf16x8_t& hi, bf16x8_t& mid, bf16x8_t& lo) {
+  const int l = threadIdx.x & 63;
+  const char* p = tile + (8 * (l >> 5)) * pitch + (row0 + (l & 31)) * 4;
+  float x[8];
+#pragma unroll
+  for (int e = 0; e < 8; e++) x[e] = *(const float*)(p + e * pitch);
+  f32x8_split3(x, hi, mid, lo);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // The kernel
 // ---------------------------------------------------------------------------------------------------
@@ -446,6 +481,8 @@ __device__ __forceinline__ void frag_mc_f32_split(const char* tile, int pitch, i
 // 3 = "bf16x3": every fp32 operand element is split into two bf16 terms at fragment time and a k-tile of 16 runs as THREE v_mfma_f32_32x32x16_bf16
 // (lo*hi + hi*lo + hi*hi, fp32 accumulation) = 96 cycles per SIMD instead of 512. Dropped: lo*lo and the second-order split remainders, ~2^-16 relative per
 // product with random sign -- 60x finer than the TF32 convolutions (10-bit mantissa) torch runs the reference's "fp32" evaluation with on its usual hardware.
+// 6 = "bf16x6": three bf16 terms per element (exact: x == h + m + l) and SIX MFMAs per k-tile, smallest products first: h*l, l*h, m*m, m*h, h*m, h*h = 192 cycles.
+// Dropped: m*l, l*m, l*l, at most 2^-25 of the product -- below the fp32 rounding of the product itself; what remains is the fp32 accumulation, as in mode 0.
 template <typename T, class LP, class LQ, int BI, int BJ, int WI, int WJ, bool TR, int SPLIT = 0>
 __global__ __launch_bounds__(256) void sg_gemm_kernel(LP lp, LQ lq, Epilogue<T> epi, int I, int J, int K,
                                                        int klen, int tilesI, int tilesJ) {
@@ -563,6 +600,27 @@ __global__ __launch_bounds__(256) void sg_gemm_kernel(LP lp, LQ lq, Epilogue<T> 
         for (int b = 0; b < TJ; b++) {
           acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pl[a], qh[b], acc[a][b], 0, 0, 0);
           acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ph[a], ql[b], acc[a][b], 0, 0, 0);
+          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ph[a], qh[b], acc[a][b], 0, 0, 0);
+        }
+    } else if constexpr (SPLIT == 6) {
+      bf16x8_t ph[TI], pm[TI], pl[TI], qh[TJ], qm[TJ], ql[TJ];
+#pragma unroll
+      for (int a = 0; a < TI; a++) {
+        if constexpr (LP::KC) frag_kc_f32_split3(ps, wi0 + a * 32, ph[a], pm[a], pl[a]); else frag_mc_f32_split3(ps, P_PITCH, wi0 + a * 32, ph[a], pm[a], pl[a]);
+      }
+#pragma unroll
+      for (int b = 0; b < TJ; b++) {
+        if constexpr (LQ::KC) frag_kc_f32_split3(qs, wj0 + b * 32, qh[b], qm[b], ql[b]); else frag_mc_f32_split3(qs, Q_PITCH, wj0 + b * 32, qh[b], qm[b], ql[b]);
+      }
+#pragma unroll
+      for (int a = 0; a < TI; a++)
+#pragma unroll
+        for (int b = 0; b < TJ; b++) {
+          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ph[a], ql[b], acc[a][b], 0, 0, 0);
+          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pl[a], qh[b], acc[a][b], 0, 0, 0);
+          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pm[a], qm[b], acc[a][b], 0, 0, 0);
+          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pm[a], qh[b], acc[a][b], 0, 0, 0);
+          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ph[a], qm[b], acc[a][b], 0, 0, 0);
           acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ph[a], qh[b], acc[a][b], 0, 0, 0);
         }
     } else {

@@ -95,10 +95,12 @@ def _take_stats(x):
 # raw launch helpers (also used directly by the kernel-level tests)
 # ---------------------------------------------------------------------------------------------------------
 class f32_mode:
-    """with f32_mode("bf16x3"): the generic engine's fp32 forward convolutions (all-vector operands) run as three bf16 MFMAs per 16-wide k-tile on operands split
+    """with f32_mode("bf16x3"): the generic engine's fp32 convolutions (all-vector operands) run as three bf16 MFMAs per 16-wide k-tile on operands split
     into two bf16 terms in registers -- fp32 tensors in and out, fp32 accumulation, ~2^-16 relative per product, 5.3x the matrix-pipe rate of the exact fp32 MFMA
-    (csrc/gemm_core.h SPLIT, sg_set_f32_mode). "exact" (the default everywhere) = v_mfma_f32_32x32x2_f32. Process-wide switch: restored on exit."""
-    MODES = {"exact": 0, "bf16x3": 3}
+    (csrc/gemm_core.h SPLIT, sg_set_f32_mode). "bf16x6": three bf16 terms per element (their sum is the fp32 value exactly) and six MFMAs per k-tile; what is
+    dropped is below fp32's own rounding of a product, so the mode meets the exact path's bounds; it covers the convolutions AND the fp32 sg_gemm (gemm_raw),
+    2.67x the matrix-pipe rate in cycles, 1.2-1.4x measured on this engine (profiles/f32_modes_bench.txt). "exact" (the default everywhere) = v_mfma_f32_32x32x2_f32. Process-wide switch: restored on exit."""
+    MODES = {"exact": 0, "bf16x3": 3, "bf16x6": 6}
 
     def __init__(self, mode):
         if mode not in self.MODES:

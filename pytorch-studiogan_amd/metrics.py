@@ -140,7 +140,9 @@ class InceptionV3:
 
     def __init__(self, state_dict, device, dtype=torch.float32, f32_mode="exact"):
         """f32_mode (dtype fp32 only): "exact" = fp32 MFMA; "bf16x3" = fp32 tensors, every convolution's operands split into two bf16 terms in registers and
-        contracted with three bf16 MFMAs per k-tile (functional.f32_mode): ~2^-16 relative per product, measured 3e-6 on the pool3 features against the oracle."""
+        contracted with three bf16 MFMAs per k-tile (functional.f32_mode): ~2^-16 relative per product, measured 3e-6 on the pool3 features against the oracle;
+        "bf16x6" = three bf16 terms (exact split) and six MFMAs per k-tile, in the convolutions and the final linear layer: fp32-grade arithmetic on the bf16
+        matrix pipe (measured figures: profiles/f32_modes_bench.txt)."""
         self.device, self.dtype = device, dtype
         if f32_mode not in F.f32_mode.MODES:
             raise ValueError(f"InceptionV3: f32_mode {f32_mode!r}")
@@ -374,11 +376,17 @@ class DINOViT:
     dtype=torch.bfloat16: the fused path -- per block LayerNorm -> bf16, qkv GEMM (bias), sg_mha_fwd on the packed qkv, proj GEMM (+= residual),
     LayerNorm, fc1 GEMM (bias + GELU), fc2 GEMM (+= residual): 7 launches, nothing elementwise in between.
     dtype=torch.float32: the same graph on the exact-fp32 sg_gemm, scores per head as batched sg_gemm + sg_softmax_rows + sg_gemm and an fp32 GELU
-    pass: the exact path (and the A/B partner of the fused one); not built for speed."""
+    pass: the exact path (and the A/B partner of the fused one); not built for speed.
+    f32_mode (dtype fp32 only, as InceptionV3's): "exact", or a functional.f32_mode name applied around the forward -- "bf16x6" puts the sg_gemm launches of
+    the graph on the bf16 matrix pipe at fp32 accuracy, those with all-vector operands (the linear layers, q k^T; P V only when the token count is a multiple
+    of 4, and the 3-channel patch embedding never: they keep the exact MFMA); "bf16x3" is convolution-only and changes nothing here."""
 
-    def __init__(self, state_dict, device, dtype=torch.float32, num_heads=None):
+    def __init__(self, state_dict, device, dtype=torch.float32, num_heads=None, f32_mode="exact"):
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"DINOViT: dtype {dtype}")
+        if f32_mode not in F.f32_mode.MODES:
+            raise ValueError(f"DINOViT: f32_mode {f32_mode!r}")
+        self.f32_mode = f32_mode if dtype == torch.float32 else "exact"
         self.geometry = g = validate_dino_state_dict(state_dict, num_heads=num_heads)
         if not L.lib().sg_mha_fwd_ok(1, g["tokens"], g["heads"], g["embed"] // g["heads"]):
             raise RuntimeError(f"DINOViT: no attention kernel for {g}")
@@ -420,6 +428,12 @@ class DINOViT:
     def forward_nhwc(self, x):
         """x: [B, res, res, 3] NHWC in the compute dtype, normalised -> (embed [B, 4 * C], logits [B, classes]), fp32. Only the native grid is
         served (the identity branch of interpolate_pos_encoding, vit.py:165); any other input size raises."""
+        if self.f32_mode != "exact":
+            with F.f32_mode(self.f32_mode):
+                return self._forward_nhwc(x)
+        return self._forward_nhwc(x)
+
+    def _forward_nhwc(self, x):
         g = self.geometry
         C, N, Hd, p, nlb = g["embed"], g["tokens"], g["hidden"], g["patch"], g["num_last_blocks"]
         B = x.shape[0]
@@ -581,7 +595,7 @@ class LoadEvalModel:
                 raise RuntimeError("pass the DINO ViT-S/8 weights (weights_path=.../" + DINO_BACKBONE_FILE + " and linear_weights_path=.../" + DINO_LINEAR_FILE +
                                    ", both from " + DINO_WEIGHTS_URL + ", or a merged state_dict); there is no network access here")
             self.res, self.mean, self.std = 224, IMAGENET_MEAN, IMAGENET_STD
-            self.model = DINOViT(state_dict, self.device, dtype)
+            self.model = DINOViT(state_dict, self.device, dtype, f32_mode=f32_mode)      # f32_mode: DINOViT.__init__
             return
         if weights_path is not None:
             state_dict, self.weights_sha256 = load_fid_weights(weights_path)

@@ -21,7 +21,7 @@ def main():
     ap.add_argument("--samples", type=int, default=5120)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--f32-mode", default="exact", choices=["exact", "bf16x3"], help="fp32 Inception: exact fp32 MFMA or the bf16x3 split (functional.f32_mode)")
+    ap.add_argument("--f32-mode", default="exact", choices=["exact", "bf16x3", "bf16x6"], help="fp32 Inception: exact fp32 MFMA, the bf16x3 split or the bf16x6 split (functional.f32_mode)")
     args = ap.parse_args()
     from studiogan_amd import metrics as M
     dev = torch.device("cuda:0")
