@@ -13,7 +13,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 
-// `s_setprio 1` around the MFMA clusters of the lean weight-gradient kernels (wgrad_ql.h, wgrad_v3l.h): their workgroups share a CU in different phases (one in
+// `s_setprio 1` around the MFMA clusters of the lean bodies of the weight-gradient kernels (LEAN = true in wgrad_q.h, wgrad_v3.h): their workgroups share a CU in different phases (one in
 // its MFMA cluster while another issues its LDS-DMA or sits at its barrier), the structure cdna_hip_programming.md T5 prices the hint for. Measured in round 5
 // (same box, profiles/r05_variant_ab_layer_tables_b.txt): -1.0 % / -1.7 % on the two weight-gradient layer tables, -0.7 ms on the C3 step: always on.
 #define SG_PRIO_UP() __builtin_amdgcn_s_setprio(1)

@@ -6,7 +6,6 @@
 #include "wgrad_v2.h"
 #include "wgrad_sk.h"
 #include "wgrad_v3.h"
-#include "wgrad_v3l.h"
 
 // what every bf16 weight-gradient kernel asks first: stride 1, ds_read_b64_tr_b16 fragments allowed, plain (not transposed) operands, and
 // buffer-descriptor DMA -- bit 31 of a byte offset must be out of range
@@ -103,11 +102,10 @@ static int wgrad_v3_launch(const sg_conv_wgrad_desc* d, const V3Plan& s, hipStre
   p.out = d->work; p.split_stride = s.stride;
   p.bias_off = d->dbias ? s.n : -1; p.bias_scale = p.g_up ? 0.25f : 1.f;
   p.alpha = d->alpha; p.alpha_ptr = d->alpha_ptr;
-  // the lean kernel (wgrad_v3l.h; round 5, same box: the wgrad_v3 layers of C3 -8..-12 %, profiles/r05_variant_ab_layer_tables_b.txt); it hands problems whose
-  // operands are read through a 2x upsampling to wgrad_v3.h's kernel. SG_WGRAD_V3_LEAN=0 (read per call): that kernel everywhere (the bit-identity reference of
+  // the lean body (round 5, same box: the wgrad_v3 layers of C3 -8..-12 %, profiles/r05_variant_ab_layer_tables_b.txt); the launcher keeps problems whose
+  // operands are read through a 2x upsampling on the round-4 body. SG_WGRAD_V3_LEAN=0 (read per call): that body everywhere (the bit-identity reference of
   // tests/test_conv_v2_gpu.py)
-  if (env_mode("SG_WGRAD_V3_LEAN") == '0') return sg_launch_wgrad_v3(p, s.NB, st);
-  return sg_launch_wgrad_v3l(p, s.NB, st);
+  return sg_launch_wgrad_v3(p, s.NB, env_mode("SG_WGRAD_V3_LEAN") != '0', st);
 }
 
 // ---- tile kernel (wgrad_v2.h). SG_CONV_V2=0 disables it, =force takes narrow problems too. ---------------------------------------------

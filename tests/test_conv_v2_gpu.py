@@ -499,8 +499,8 @@ def test_wgrad_v3_full_size_layers(sg):
 
 @pytest.mark.parametrize("case", WV3_CASES)
 def test_wgrad_v3_lean_matches_round4_kernel(sg, case, monkeypatch):
-    """csrc/wgrad_v3l.h (the default since round 5: ReLU-on-load as a template parameter, bias gradient through v_dot2) against the round-4 kernel
-    (SG_WGRAD_V3_LEAN=0, csrc/wgrad_v3.h): the same MFMAs in the same order -> dW bit for bit (one split layout), bias gradient to fp32 rounding."""
+    """csrc/wgrad_v3.h: the lean body (the default since round 5: ReLU-on-load as a template parameter, bias gradient through v_dot2) against the round-4
+    body (SG_WGRAD_V3_LEAN=0): the same MFMAs in the same order -> dW bit for bit (one split layout), bias gradient to fp32 rounding."""
     from studiogan_amd import functional as F, _lib as L
     N, Cin, Cout, H, relu, up, pool = case
     d = torch.device("cuda:0")

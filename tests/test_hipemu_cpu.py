@@ -64,7 +64,7 @@ def test_wgrad_v3_pins_interpreter(wg, shape):
 
 @pytest.mark.parametrize("shape", V3_SHAPES)
 def test_wgrad_v3_lean_equals_shipped(wg, shape):
-    """wgrad_v3l.h (SG_WGRAD_V3_LEAN=1): same MFMAs in the same order -> dW bit for bit; bias gradient summed in another order -> fp32 rounding"""
+    """wgrad_v3.h's lean body (SG_WGRAD_V3_LEAN=1): same MFMAs in the same order -> dW bit for bit; bias gradient summed in another order -> fp32 rounding"""
     x, dy = _data(shape, 12)
     emu.config(wg, dma_late=1, greedy=1, seed=5)
     for xf in (0, emu.PIX_RELU):
@@ -182,7 +182,7 @@ def test_conv_q_forward_pins_interpreter(cq, form, shape):
 @pytest.mark.parametrize("form", [emu.Q_POOL, emu.Q_UP])
 @pytest.mark.parametrize("shape", Q_SHAPES)
 def test_wgrad_q_pins_interpreter_and_lean_equals_shipped(cq, form, shape):
-    """shipped sg_wgrad_q_kernel + k_quad_reduce_fold against the fp64 restatement; wgrad_ql.h (SG_WGRAD_Q_LEAN=1: DMA addresses once per workgroup,
+    """shipped sg_wgrad_q_kernel + k_quad_reduce_fold against the fp64 restatement; wgrad_q.h's lean body (SG_WGRAD_Q_LEAN=1: DMA addresses once per workgroup,
     ReLU as a template parameter, bias gradient through v_dot2) bit for bit against the shipped kernel"""
     import torch
     import quad_ref as Q

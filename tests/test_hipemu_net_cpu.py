@@ -247,7 +247,7 @@ def forced_fast_kernels(monkeypatch):
 def test_emulated_fullwidth_bf16_step_vs_golden(forced_fast_kernels, monkeypatch, lean):
     """the benchmarked network (BASELINE config 3: BigGAN, ImageNet-128 widths) with the benchmarked kernels -- conv_q / conv_v4 / conv_v3 / conv_sk /
     conv_rs forward and data gradient, wgrad_v3 / wgrad_q / wgrad_sk / wgrad_v2, flash attention, epilogue BN statistics: 901 launches, 52 M MFMAs --
-    one bf16 training step against the reference's golden vectors. lean = 1: the default weight-gradient kernels (wgrad_v3l.h / wgrad_ql.h), 0: the round-4 ones."""
+    one bf16 training step against the reference's golden vectors. lean = 1: the lean bodies of the weight-gradient kernels (wgrad_v3.h / wgrad_q.h), 0: the round-4 ones."""
     monkeypatch.setenv("SG_WGRAD_V3_LEAN", lean)
     monkeypatch.setenv("SG_WGRAD_Q_LEAN", lean)
     c = _step("biggan128w", True)

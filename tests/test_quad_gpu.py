@@ -163,7 +163,7 @@ def test_wgrad_q_matches_autograd(sg, case):
 
 @pytest.mark.parametrize("case", WG_CASES)
 def test_wgrad_q_lean_matches_round4_kernel(sg, case, monkeypatch):
-    """csrc/wgrad_ql.h (the default since round 5) against the round-4 kernel it replaced (SG_WGRAD_Q_LEAN=0, csrc/wgrad_q.h): the same MFMAs in the same
+    """csrc/wgrad_q.h: the lean body (the default since round 5) against the round-4 body it replaced (SG_WGRAD_Q_LEAN=0): the same MFMAs in the same
     order -> the 3x3 gradient bit for bit, the bias gradient to fp32 rounding (summed through v_dot2 on other waves)."""
     from studiogan_amd import functional as F, _lib as L
     form, N, Hl, Wl, C, Cout, relu, with_bias = case
