@@ -34,7 +34,7 @@ static inline long long bf16_extent(long long npix, int ld, int C) { return ((np
 
 template <typename D> static inline bool is_3x3_s1_p1(const D* d) { return d->R == 3 && d->S == 3 && d->stride == 1 && d->pad_h == 1 && d->pad_w == 1; }
 
-// 32-cout accumulator blocks per workgroup of the small-workgroup kernels (conv_v4.h, conv_q.h, wgrad_v3*.h, wgrad_q*.h): 3, 2, or 0 = not served
+// 32-cout accumulator blocks per workgroup of the small-workgroup kernels (conv_v4.h, conv_q.h, wgrad_v3.h, wgrad_q.h): 3, 2, or 0 = not served
 static inline int cout_blocks(int Cout) { return Cout % 96 == 0 ? 3 : Cout % 64 == 0 ? 2 : 0; }
 
 // cout tile of the 256-pixel tile kernels (conv_v2.h, conv_v3.h): the candidate that divides I and gives the most tiles, the first one with >= 512

@@ -20,10 +20,11 @@
 //     FOUR taps (ti, tj) read it at low-resolution offsets (ti - ea, tj - eb), (ea, eb) = (a, b) for POOL and (1 - a, 1 - b) for UP;
 //   * weights: the quad image [Cout][view][tap][C] (K = 16 C), one 32 NB x 32 tile per (view, slice, tap), two taps ahead through four buffers
 //     with counted waits (conv_v4.h's scheme; four buffers because a slice has four taps).
-// Tile = 256 low-resolution pixels x 32 NB couts, 4 waves, <= 53 KB of LDS: three workgroups per CU.
+// Tile = 256 low-resolution pixels x 32 NB couts, 4 waves, <= 53 KB of LDS: three workgroups per CU. The 64-byte-row LDS image, its DMA / fragment
+// addressing and the k-step are halo_tile.h's.
 #pragma once
 #include <type_traits>
-#include "conv_v2.h"
+#include "halo_tile.h"
 
 struct ConvQParams {
   const bf16_t* x; const bf16_t* w;
@@ -80,12 +81,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPMIN > 0 ?
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nt = tilesI * tilesJ * nph;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nt >> 3, r = nt & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int bid = sg_xcd_tile(blockIdx.x, tilesI * tilesJ * nph);
   // gj == 1: the phases and cout tiles of one pixel tile are neighbours in launch order: they share the patch through the XCD's L2. That order walks through
   // ALL weight sets (cout tile, phase) once per pixel tile: fine while the whole quad image stays in the 4 MB L2, but the deep layers' images are 19-75 MB and every
   // pixel tile then streams them from the Infinity Cache again (profiles/r06_quad_dispatch_traffic_q.txt: 1.7-3.7 GB of L2 misses per launch for 0.1 GB of tensors).
@@ -107,19 +103,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPMIN > 0 ?
   const int i0 = tI * BI, j0 = tJ * BJ;
   char* const pbufs = smem + p.wgt_off;
   float* sbias = (float*)(smem + p.bias_off);
-  if (epi.bias) {
-    for (int i = tid; i < BI; i += 64 * NW) {
-      float b = (i0 + i < epi.I) ? epi.bias[i0 + i] : 0.f;
-      if (SKIP && p.bias2 && i0 + i < epi.I) b += p.bias2[i0 + i];
-      sbias[i] = b;
-    }
-  }
-  if (tid < 32) ((unsigned*)(smem + p.zero_off))[tid] = 0u;
+  ht_stage_bias<BI, 64 * NW, SKIP>(sbias, epi, p.bias2, i0, tid);
+  ht_zero_line(smem, p.zero_off, tid);
 
   const auto rsx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.xbytes, 0x00020000);
-  const auto rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (int)p.wbytes, 0x00020000);
-  // DMA piece = 1 KiB = 16 rows x 64 B, LDS linear in lane order: lane -> (row sub = lane >> 2, physical chunk lane & 3); the logical
-  // 16-byte chunk it fetches is the swizzle inverse: lc = (lane & 3) ^ (row >> 2 & 3), and row = 16 g + sub gives (sub >> 2) & 3.
+  // DMA lane geometry = ht32_sub / ht32_chunk, the border mask below = ht_border_mask and the skip's weight tile = ht32_skip_weight_tile (halo_tile.h). The three
+  // are written out here: through the helpers, kernels of this family allocated 1-4 registers more (profiles/r11_halo_fold_code_identity.txt, section 6)
   const int sub = lane >> 2;
   const int lc = (lane & 3) ^ ((lane >> 4) & 3);
   const unsigned ldxb = 2u * (unsigned)p.ldx;
@@ -160,19 +149,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPMIN > 0 ?
   };
   // ---- weight DMA: BI rows x 32 channels of (view, slice s, tap t): per-lane row offsets once per workgroup, (view, tap, slice) through the scalar offset ----
   unsigned wvo[2];
-#pragma unroll
-  for (int i = 0; i < 2; i++) {
-    const int row = i0 + 16 * (wave + NW * i) + sub;
-    wvo[i] = (row < p.I) ? ((unsigned)row * (unsigned)p.K + (unsigned)(lc * 8)) * 2u : 0x80000000u;
-  }
-  auto weight_tile = [&](int buf, int view, int s, int t) {
-    const int so = ((view * 4 + t) * p.C + s * 32) * 2;
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-      const int g = wave + NW * i;
-      if (g < NWP) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (sg_lptr_t)(pbufs + buf * PB + g * 1024), 16, (int)wvo[i], so, 0, 0);
-    }
-  };
+  ht32_weight_offsets(wvo, i0, wave, sub, lc, p.I, p.K);
+  auto weight_tile = [&](int buf, int view, int s, int t) { ht32_weight_tile<NWP>(p.w, p.wbytes, pbufs + buf * PB, wvo, wave, ((view * 4 + t) * p.C + s * 32) * 2); };
 
   // ---- fragment rows of this lane ----------------------------------------------------------------------------------------------------
   const int wj0 = wave * (32 * TJ);
@@ -183,7 +161,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPMIN > 0 ?
   for (int b = 0; b < TJ; b++) {
     const int row = j0 + wj0 + b * 32 + frow;
     const int wo = row & wmask, ho = (row >> p.wlog) & ((1 << p.hlog) - 1);
-    unsigned m = 0;
+    unsigned m = 0;          // (= ht_border_mask, see above)
     if (row < p.J) {
 #pragma unroll
       for (int rr = 0; rr < 3; rr++)
@@ -194,21 +172,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPMIN > 0 ?
     qval[b] = m;
     rb[b] = row - P0;
   }
-  // weight fragment addresses: row = cout a * 32 + frow, chunk (ks * 2 + fhi) ^ (row >> 2 & 3); ks = 1 is the address ^ 32
-  unsigned wa[TI];
-#pragma unroll
-  for (int a = 0; a < TI; a++) {
-    const int row = a * 32 + frow;
-    wa[a] = (unsigned)(row * 64 + ((fhi ^ ((row >> 2) & 3)) << 4));
-  }
+  unsigned wa[TI];        // weight fragment addresses inside a weight tile
+  ht32_weight_frag_addr(wa, frow, fhi);
 
   f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int a = 0; a < TI; a++)
-#pragma unroll
-    for (int b = 0; b < TJ; b++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
+  ht_zero_acc(acc);
 
   // virtual slices: POOL walks (view 0..3) x (C / 32); UP walks the C / 32 slices of its one view (= phase)
   const int nv = pool ? 4 : 1;
@@ -268,27 +236,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPMIN > 0 ?
       }
       const char* ps = pbufs + t * PB;
 #pragma unroll
-      for (int ks = 0; ks < 2; ks++) {
-        bf16x8_t pf[TI], qf[TJ];
-#pragma unroll
-        for (int a = 0; a < TI; a++) {
-          u32x4 v = *(const u32x4*)(ps + (wa[a] ^ (unsigned)(ks * 32)));
-          pf[a] = __builtin_bit_cast(bf16x8_t, v);
-        }
-#pragma unroll
-        for (int b = 0; b < TJ; b++) {
-          unsigned qaddr = qat[t][b] ^ (unsigned)(ks * 32);
-          if constexpr (DB) qaddr += (qaddr < (unsigned)p.zero_off) ? pb : 0u;      // (the zero line is not double-buffered)
-          u32x4 v = *(const u32x4*)(smem + qaddr);
-          if (RELU) v = relu16<bf16_t>(v);
-          qf[b] = __builtin_bit_cast(bf16x8_t, v);
-        }
-#pragma unroll
-        for (int a = 0; a < TI; a++)
-#pragma unroll
-          for (int b = 0; b < TJ; b++)
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf[a], qf[b], acc[a][b], 0, 0, 0);
-      }
+      for (int ks = 0; ks < 2; ks++) ht32_kstep<RELU>(acc, ps, wa, smem, qat[t], ks, true, pb, DB ? (unsigned)p.zero_off : 0u);      // (the zero line is not double-buffered)
       if constexpr (DB) {
         // counted waits (see the kernel comment): n_w = 2 for the waves that issue two weight pieces per tap, else 1
         if (next_slice) {
@@ -337,7 +285,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPMIN > 0 ?
         off = (pix < p.J) ? off : 0x80000000u;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsx2, (sg_lptr_t)(smem + slot * P2B + g * 1024), 16, (int)off, 0, 0, 0);
       }
-      for (int g = wave; g < NWP; g += NW) {
+      for (int g = wave; g < NWP; g += NW) {           // (= ht32_skip_weight_tile, see above)
         const int row = i0 + 16 * g + sub;
         unsigned off = ((unsigned)row * (unsigned)p.C2 + (unsigned)(s2 * 32 + lc * 8)) * 2u;
         off = (row < p.I) ? off : 0x80000000u;
@@ -361,25 +309,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPMIN > 0 ?
         qa[b] = a;
       }
 #pragma unroll
-      for (int ks = 0; ks < 2; ks++) {
-        bf16x8_t pf[TI], qf[TJ];
-#pragma unroll
-        for (int a = 0; a < TI; a++) {
-          u32x4 v = *(const u32x4*)(ps + (wa[a] ^ (unsigned)(ks * 32)));
-          pf[a] = __builtin_bit_cast(bf16x8_t, v);
-        }
-#pragma unroll
-        for (int b = 0; b < TJ; b++) {
-          u32x4 v = *(const u32x4*)(smem + (qa[b] ^ (unsigned)(ks * 32)));
-          if (RELU && !p.skip_norelu) v = relu16<bf16_t>(v);
-          qf[b] = __builtin_bit_cast(bf16x8_t, v);
-        }
-#pragma unroll
-        for (int a = 0; a < TI; a++)
-#pragma unroll
-          for (int b = 0; b < TJ; b++)
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf[a], qf[b], acc[a][b], 0, 0, 0);
-      }
+      for (int ks = 0; ks < 2; ks++) ht32_kstep<RELU>(acc, ps, wa, smem, qa, ks, !p.skip_norelu);
       slot ^= 1;
     }
   }
@@ -387,10 +317,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPMIN > 0 ?
   float al = epi.alpha;
   if (epi.alpha_ptr) al *= *epi.alpha_ptr;
   if (pool) {
-    sg_conv_epilogue<BI, BJ, NW, TI, TJ>(acc, smem, sbias, epi, i0, j0, 0, wj0, al, true, 0, 0, p.stats, p.I, tJ);
+    sg_conv_epilogue<BI, BJ, NW, TI, TJ>(acc, smem, sbias, epi, i0, j0, 0, wj0, al, 0, 0, p.stats, p.I, tJ);
   } else {
     // UP: output / mask / residual rows go through the view of this workgroup's phase
-    sg_conv_epilogue<BI, BJ, NW, TI, TJ, true>(acc, smem, sbias, epi, i0, j0, 0, wj0, al, true, p.wlog, (ph >> 1) * 2 * p.Wl + (ph & 1),
+    sg_conv_epilogue<BI, BJ, NW, TI, TJ, true>(acc, smem, sbias, epi, i0, j0, 0, wj0, al, p.wlog, (ph >> 1) * 2 * p.Wl + (ph & 1),
                                                p.stats, p.I, tJ * nph + ph);
   }
 }
@@ -398,16 +328,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPMIN > 0 ?
 // LDS need (bytes) of a configuration
 static inline int sg_conv_q_lds(int NB, int BJ, int npx, bool skip, bool db, int* wgt_off, int* zero_off, int* bias_off) {
   const int BI = 32 * NB;
-  const int woff = npx * 64 * (db ? 2 : 1);
-  const int ops = woff + 4 * BI * 64;
-  const int stage = BJ * (BI * 2 + 16);
   const int skp = skip ? 2 * BJ * 64 + 2 * BI * 64 : 0;      // two staging slots of the fused skip (patch + weights each)
-  int body = ops > stage ? ops : stage;
-  if (skp > body) body = skp;
-  if (wgt_off) *wgt_off = woff;
-  if (zero_off) *zero_off = body;
-  if (bias_off) *bias_off = body + 128;
-  return body + 128 + BI * 4;
+  return ht32_lds(BI, BJ, npx * 64 * (db ? 2 : 1), 4, skp, wgt_off, zero_off, bias_off);
 }
 template <int NB, bool RELU, int TJW, bool SKIP, int NPMIN>
 static inline int sg_launch_conv_qr(const ConvQParams& p0, const Epilogue<bf16_t>& e, hipStream_t st) {
@@ -417,10 +339,7 @@ static inline int sg_launch_conv_qr(const ConvQParams& p0, const Epilogue<bf16_t
   const int lds = sg_conv_q_lds(NB, BJ, p.npx, SKIP, NPMIN > 0, &p.wgt_off, &p.zero_off, &p.bias_off);
   if (lds > 80 * 1024) return -1;
   static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute((const void*)sg_conv_q_kernel<NB, RELU, TJW, SKIP, NPMIN>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess) return -1;
-    attr_done = true;
-  }
+  if (!ht_allow_lds(attr_done, sg_conv_q_kernel<NB, RELU, TJW, SKIP, NPMIN>, 80 * 1024)) return -1;
   const int tilesI = (p.I + BI - 1) / BI, tilesJ = (p.J + BJ - 1) / BJ, nph = p.form == 0 ? 1 : 4;
   hipLaunchKernelGGL((sg_conv_q_kernel<NB, RELU, TJW, SKIP, NPMIN>), dim3(tilesI * tilesJ * nph), dim3(256), lds, st, p, e, tilesI, tilesJ, nph);
   return 0;

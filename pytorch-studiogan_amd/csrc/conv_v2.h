@@ -42,15 +42,12 @@ typedef __attribute__((address_space(3))) void* sg_lptr_t;
 // view of the tensor at twice the resolution: global row of tile row jg = ((jg >> vlog) << (vlog + 2)) + ((jg & (2^vlog - 1)) << 1) + vadd.
 template <int BI, int BJ, int NW, int TI, int TJ, bool VMAP = false, bool NOSTORE = false>      // NOSTORE: ablation only (conv_v4.h ABL bit 5)
 __device__ __forceinline__ void sg_conv_epilogue(f32x16 (&acc)[TI][TJ], char* smem, const float* sbias, const Epilogue<bf16_t>& epi,
-                                                 int i0, int j0, int wi0, int wj0, float al, bool active = true, int vlog = 0, int vadd = 0,
+                                                 int i0, int j0, int wi0, int wj0, float al, int vlog = 0, int vadd = 0,
                                                  float* stats = nullptr, int stats_C = 0, int stats_row = 0) {
   auto grow = [&](int jg) -> long long {
     if (VMAP) return (long long)(((jg >> vlog) << (vlog + 2)) + ((jg & ((1 << vlog) - 1)) << 1) + vadd);
     return (long long)jg;
   };
-  // active (wave-uniform): this wave's accumulators belong to the BJ rows staged by this call. A tile larger than its staging area is
-  // stored in several calls (conv_v4.h, 512-pixel tiles: two calls of 256 rows, two of the four waves active in each); every thread
-  // takes part in the operand pre-load and in the store loop of every call.
   const int tid = threadIdx.x, lane = tid & 63;
   // bf16 output tile: staged through LDS (the operand buffers are dead now) so that the global stores are 16 bytes per lane with
   // consecutive lanes on consecutive addresses of a row. The direct form (8 bytes per lane, 32 different rows per instruction)
@@ -88,24 +85,22 @@ __device__ __forceinline__ void sg_conv_epilogue(f32x16 (&acc)[TI][TJ], char* sm
   if (pre_both) {
     stage_tile(epi.mask, epi.ldm);
     __syncthreads();
-    if (active) {
 #pragma unroll
-      for (int ta = 0; ta < TI; ta++)
+    for (int ta = 0; ta < TI; ta++)
 #pragma unroll
-        for (int tb = 0; tb < TJ; tb++) {
-          const int jl = wj0 + tb * 32 + (lane & 31);
-          const int jo = pool ? (jl >> 2) : jl;
-          uint32_t bits = 0u;
+      for (int tb = 0; tb < TJ; tb++) {
+        const int jl = wj0 + tb * 32 + (lane & 31);
+        const int jo = pool ? (jl >> 2) : jl;
+        uint32_t bits = 0u;
 #pragma unroll
-          for (int g4 = 0; g4 < 4; g4++) {
-            const int il = wi0 + ta * 32 + 8 * g4 + 4 * (lane >> 5);
-            const u32x2 m = *(const u32x2*)(smem + jo * CP + il * 2);
+        for (int g4 = 0; g4 < 4; g4++) {
+          const int il = wi0 + ta * 32 + 8 * g4 + 4 * (lane >> 5);
+          const u32x2 m = *(const u32x2*)(smem + jo * CP + il * 2);
 #pragma unroll
-            for (int e = 0; e < 4; e++) { const bf16_t h = (bf16_t)((m[e >> 1] >> (16 * (e & 1))) & 0xffffu); if (bf2f(h) > 0.f) bits |= 1u << (4 * g4 + e); }
-          }
-          mbits[ta * TJ + tb] = bits;
+          for (int e = 0; e < 4; e++) { const bf16_t h = (bf16_t)((m[e >> 1] >> (16 * (e & 1))) & 0xffffu); if (bf2f(h) > 0.f) bits |= 1u << (4 * g4 + e); }
         }
-    }
+        mbits[ta * TJ + tb] = bits;
+      }
     __syncthreads();
     stage_tile((const bf16_t*)epi.res, epi.ldr);
     __syncthreads();
@@ -114,7 +109,6 @@ __device__ __forceinline__ void sg_conv_epilogue(f32x16 (&acc)[TI][TJ], char* sm
     __syncthreads();
   }
   const bool relu_out = (epi.flags & SG_EPI_RELU) != 0;
-  if (active) {
 #pragma unroll
   for (int ta = 0; ta < TI; ta++)
 #pragma unroll
@@ -165,7 +159,6 @@ __device__ __forceinline__ void sg_conv_epilogue(f32x16 (&acc)[TI][TJ], char* sm
         }
       }
     }
-  }
   __syncthreads();
   if (stats) {
     // Batch-norm statistics of the layer behind this convolution, taken from the staged tile (the bf16 values the BN kernels would read back
@@ -233,12 +226,7 @@ __global__ __launch_bounds__(64 * WJ * WI) void sg_conv_v2_kernel(ConvV2Params p
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // provably uniform: LDS-DMA destinations (M0) stay in SGPRs
-  const int nt = tilesI * tilesJ;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nt >> 3, r = nt & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int bid = sg_xcd_tile(blockIdx.x, tilesI * tilesJ);
   const int tI = bid % tilesI, tJ = bid / tilesI;
   const int i0 = tI * BI, j0 = tJ * BJ;
   // bias of this cout tile: fetched once per workgroup into its own LDS region (behind the operand buffers), visible after the

@@ -15,10 +15,10 @@
 //   * nearest x2 upsample on load: the patch holds SOURCE pixels (4x fewer); row = base + ((ph+tr-1)>>1)*Ws + ((pw+ts-1)>>1)
 //   * fragment addresses: (row << 7) | ((chunk ^ (row >> 1 & 7)) << 4): any 16 rows with distinct residues mod 16 are
 //     conflict-free for ds_read_b128, so every shift is as good as the unshifted read
-//   * epilogue: sg_conv_epilogue (conv_v2.h)
+//   * epilogue: sg_conv_epilogue (conv_v2.h); pixel decode, border masks and the other pieces shared with conv_v4.h / conv_q.h: halo_tile.h
 #pragma once
 #include <type_traits>
-#include "conv_v2.h"
+#include "halo_tile.h"
 
 struct ConvV3Params {
   const bf16_t* x; const bf16_t* w;
@@ -62,21 +62,14 @@ __global__ __launch_bounds__(64 * WJ * WI) void sg_conv_v3_kernel(ConvV3Params p
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nt = tilesI * tilesJ;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nt >> 3, r = nt & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int bid = sg_xcd_tile(blockIdx.x, tilesI * tilesJ);
   const int tI = bid % tilesI, tJ = bid / tilesI;
   const int i0 = tI * BI, j0 = tJ * BJ;
   const int patch_bytes = p.npx * 128;
-  char* const pbufs = smem + (PB2 ? 2 : 1) * patch_bytes;      // the two weight buffers sit behind the patch buffer(s)
+  char* const pbufs = smem + (PB2 ? 2 : 1) * patch_bytes;      // the weight buffers sit behind the patch buffer(s)
   float* sbias = (float*)(smem + p.bias_off);
-  if (epi.bias) {
-    for (int i = tid; i < BI; i += 64 * NW) sbias[i] = (i0 + i < epi.I) ? epi.bias[i0 + i] : 0.f;
-  }
-  if (tid < 32) ((unsigned*)(smem + p.zero_off))[tid] = 0u;
+  ht_stage_bias<BI, 64 * NW, false>(sbias, epi, nullptr, i0, tid);
+  ht_zero_line(smem, p.zero_off, tid);
 
   const auto rsx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.xbytes, 0x00020000);
   const auto rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (int)p.wbytes, 0x00020000);
@@ -138,44 +131,19 @@ __global__ __launch_bounds__(64 * WJ * WI) void sg_conv_v3_kernel(ConvV3Params p
   for (int b = 0; b < TJ; b++) {
     const int row = j0 + wj0 + b * 32 + frow;
     int n, ho, wo;
-    if (p.flags & SG_PIX_QUAD) {
-      const int q = row >> 2, dy = (row >> 1) & 1, dx = row & 1;
-      const int wq = q & ((p.Wo >> 1) - 1);
-      const int t = q >> (p.wshift - 1);
-      const int hq = t & ((p.Ho >> 1) - 1);
-      n = t >> (p.hshift - 1);
-      ho = 2 * hq + dy; wo = 2 * wq + dx;
-    } else {
-      wo = row & (p.Wo - 1); const int t = row >> p.wshift; ho = t & (p.Ho - 1); n = t >> p.hshift;
-    }
-    unsigned m = 0;
-    if (row < p.J) {
-#pragma unroll
-      for (int rr = 0; rr < 3; rr++)
-#pragma unroll
-        for (int ss = 0; ss < 3; ss++)
-          if ((unsigned)(ho - 1 + rr) < (unsigned)p.Ho && (unsigned)(wo - 1 + ss) < (unsigned)p.Wo) m |= 1u << (rr * 3 + ss);
-    }
-    qinv[b] = ~m;
+    ht_decode_pixel(p, row, n, ho, wo);
+    qinv[b] = ~ht_border_mask(ho, wo, p.Ho, p.Wo, row < p.J);
+    rb[b] = ht_patch_row<UP>(p, n, ho, wo, P0);
     if (UP) {
-      const int Hs = p.Ho >> 1;
-      const int spc = ((n * Hs + (ho >> 1)) << p.wlog) + (wo >> 1);
-      rb[b] = spc - P0;
       rs0[b] = (ho & 1) ? 0 : -p.W; rs2[b] = (ho & 1) ? p.W : 0;
       cs0[b] = (wo & 1) ? 0 : -1;  cs2[b] = (wo & 1) ? 1 : 0;
     } else {
-      rb[b] = (((n << p.hshift) + ho) << p.wshift) + wo - P0;
       rs0[b] = -p.W; rs2[b] = p.W; cs0[b] = -1; cs2[b] = 1;
     }
   }
 
   f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int a = 0; a < TI; a++)
-#pragma unroll
-    for (int b = 0; b < TJ; b++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
+  ht_zero_acc(acc);
 
   const int nslice = p.nslice;
   // sub-steps of the last slice when NKL == 0 (run-time): a 96-channel layer's second slice is half empty, and running its zero
@@ -183,172 +151,91 @@ __global__ __launch_bounds__(64 * WJ * WI) void sg_conv_v3_kernel(ConvV3Params p
   const int crem_last = p.C - (nslice - 1) * 64;
   const int nks_last_rt = crem_last >= 64 ? 4 : ((crem_last + 15) >> 4);
 
-  if constexpr (W3) {
-    // ---- three weight buffers: buffer of step (9 s + t) = t % 3; DMA runs two taps ahead; fragments one sub-step ahead ACROSS taps --
-    for (int i = 0; i < npw; i++) patch_piece(0, 0, i, true);
-    weight_tile(0, 0, 0);
-    weight_tile(1, 0, 1);
-    __syncthreads();
-    const int ppt8 = (npw + 7) >> 3;                 // patch pieces of the next slice per tap, taps 0..7 (<= 2: launcher)
-    bf16x8_t pf[2][TI], qf[2][TJ];
-    unsigned qa[TJ];                                 // fragment byte offsets (from smem) of the tap whose sub-step 0 is loaded next
-    auto make_qa = [&](int t, int poff) {            // t: compile-time tap; poff: byte offset of the slice's patch buffer
-      const int tr = t / 3, ts = t % 3;
+  // Two weight-buffer schemes share the tap below. What differs:
+  //   two buffers (!W3):  buffer of step (9 s + t) = step & 1; the DMA runs ONE tap ahead; a tap loads its own sub-step 0 at its head;
+  //   three buffers (W3): buffer of tap t = t % 3; the DMA runs TWO taps ahead; sub-step 0 of tap t + 1 is loaded in front of the barrier that ends tap t
+  //                       (fragments one sub-step ahead ACROSS taps; its weights were complete at the PREVIOUS barrier, the next slice's patch at barrier 7).
+  constexpr int LA = W3 ? 2 : 1;                   // taps of weight lookahead
+  constexpr int NPT = W3 ? 8 : 9;                  // taps of a slice that carry a share of the next slice's patch
+  struct Frags {
+    bf16x8_t pf[2][TI], qf[2][TJ];                 // register double buffer of the fragments, one sub-step ahead
+    unsigned qa[TJ];                               // pixel-fragment byte offsets (from smem) of the tap whose sub-step 0 is loaded next
+  };
+  auto tap_addresses = [&](Frags& f, int t, int poff) {      // t: compile-time tap; poff: byte offset of the slice's patch buffer
+    const int tr = t / 3, ts = t % 3;
 #pragma unroll
-      for (int b = 0; b < TJ; b++) {
-        int row = rb[b];
-        asm volatile("" : "+v"(row));   // keeps the nine taps' address arithmetic inside their taps (hoisted out of the slice loop it spilled)
-        if (tr == 0) row += rs0[b];
-        if (tr == 2) row += rs2[b];
-        if (ts == 0) row += cs0[b];
-        if (ts == 2) row += cs2[b];
-        const int ipar = ((row + P0) >> p.psh) & p.pm4;
-        unsigned a = (unsigned)poff + (((unsigned)row << 7) | ((unsigned)((fhi ^ (row >> 1) ^ ipar) & 7) << 4));
-        a = ((qinv[b] >> t) & 1u) ? (unsigned)p.zero_off : a;
-        qa[b] = a;
-      }
-    };
-    auto load = [&](int ks, int slot, const char* ps) {
-#pragma unroll
-      for (int a = 0; a < TI; a++) {
-        const int row = wi0 + a * 32 + frow;
-        const int ch = (ks * 2 + fhi) ^ ((row >> 1) & 7);
-        u32x4 v = *(const u32x4*)(ps + row * 128 + ch * 16);
-        pf[slot][a] = __builtin_bit_cast(bf16x8_t, v);
-      }
-#pragma unroll
-      for (int b = 0; b < TJ; b++) {
-        u32x4 v = *(const u32x4*)(smem + (qa[b] ^ (unsigned)(ks * 32)));
-        if (RELU) v = relu16<bf16_t>(v);
-        qf[slot][b] = __builtin_bit_cast(bf16x8_t, v);
-      }
-    };
-    make_qa(0, 0);
-    load(0, 0, pbufs);
-    auto run_slice = [&](int s, auto nkc) __attribute__((always_inline)) {
-      constexpr int NKC = decltype(nkc)::value;      // sub-steps of this slice; 0: run-time
-      const int nks = NKC ? NKC : nks_last_rt;
-      const bool next_slice = s + 1 < nslice;
-      const int poff_cur = (s & 1) * patch_bytes, poff_nxt = ((s + 1) & 1) * patch_bytes;
-#pragma unroll
-      for (int t = 0; t < 9; t++) {
-        const char* ps = pbufs + (t % 3) * PB;
-        auto dma_piece = [&](int k) {                // piece k of this tap: weights two taps ahead, then a share of the next slice's patch
-          if (k < NPI) {
-            if (t + 2 < 9) weight_piece((t + 2) % 3, s, t + 2, k, true);
-            else weight_piece((t + 2) % 3, s + 1, t + 2 - 9, k, next_slice);
-          } else if (t < 8) {
-            const int i = t * ppt8 + (k - NPI);
-            patch_piece((s + 1) & 1, s + 1, i, next_slice && (k - NPI) < ppt8 && i < npw);
-          }
-        };
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) {
-          if (ks < 3 && ks + 1 < nks) load(ks + 1, (ks + 1) & 1, ps);
-          if (ks < nks) {
-#pragma unroll
-            for (int a = 0; a < TI; a++)
-#pragma unroll
-              for (int b = 0; b < TJ; b++) {
-                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf[ks & 1][a], qf[ks & 1][b], acc[a][b], 0, 0, 0);
-                // a piece costs 60-180 issue cycles: one behind each of the first sub-step's MFMAs, where the matrix pipe is busy anyway
-                if (ks == 0 && a * TJ + b < NPI + 2) {
-                  __builtin_amdgcn_sched_barrier(0);
-                  dma_piece(a * TJ + b);
-                  __builtin_amdgcn_sched_barrier(0);
-                }
-              }
-            if (ks == 0) {
-#pragma unroll
-              for (int k = TI * TJ; k < NPI + 2; k++) dma_piece(k);
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);       // the scheduler keeps the software pipeline as written: fragments of sub-step k + 1, then the MFMAs
-                                                   // of sub-step k (left alone it pulls the loads of several sub-steps to the tap's head and spills)
-        }
-        // sub-step 0 of the next tap (its weights were complete at the PREVIOUS barrier; the patch of the next slice at barrier 7)
-        if (t < 8) { make_qa(t + 1, poff_cur); load(0, 0, pbufs + ((t + 1) % 3) * PB); }
-        else if (next_slice) { make_qa(0, poff_nxt); load(0, 0, pbufs); }
-        __syncthreads();
-      }
-    };
-    if constexpr (NKL == 4) {
-      for (int s = 0; s < nslice; s++) run_slice(s, std::integral_constant<int, 4>{});
-    } else {                                         // last slice peeled (an if / else of the two bodies inside one loop spilled registers)
-      for (int s = 0; s + 1 < nslice; s++) run_slice(s, std::integral_constant<int, 4>{});
-      run_slice(nslice - 1, std::integral_constant<int, NKL>{});
+    for (int b = 0; b < TJ; b++) {
+      int row = rb[b];
+      asm volatile("" : "+v"(row));   // keeps the nine taps' address arithmetic inside their taps (hoisted out of the slice loop it spilled)
+      if (tr == 0) row += rs0[b];
+      if (tr == 2) row += rs2[b];
+      if (ts == 0) row += cs0[b];
+      if (ts == 2) row += cs2[b];
+      const int ipar = ((row + P0) >> p.psh) & p.pm4;
+      unsigned a = (unsigned)poff + (((unsigned)row << 7) | ((unsigned)((fhi ^ (row >> 1) ^ ipar) & 7) << 4));
+      a = ((qinv[b] >> t) & 1u) ? (unsigned)p.zero_off : a;
+      f.qa[b] = a;
     }
-  } else {
-  // ---- prologue: patch of slice 0 and the weights of (slice 0, tap 0) ------------------------------------------------------------
+  };
+  auto load = [&](Frags& f, int ks, int slot, const char* ps) {
+#pragma unroll
+    for (int a = 0; a < TI; a++) {
+      const int row = wi0 + a * 32 + frow;
+      const int ch = (ks * 2 + fhi) ^ ((row >> 1) & 7);
+      u32x4 v = *(const u32x4*)(ps + row * 128 + ch * 16);
+      f.pf[slot][a] = __builtin_bit_cast(bf16x8_t, v);
+    }
+#pragma unroll
+    for (int b = 0; b < TJ; b++) {
+      u32x4 v = *(const u32x4*)(smem + (f.qa[b] ^ (unsigned)(ks * 32)));
+      if (RELU) v = relu16<bf16_t>(v);
+      f.qf[slot][b] = __builtin_bit_cast(bf16x8_t, v);
+    }
+  };
+
+  // ---- prologue: patch of slice 0 and the weights of the first LA taps -------------------------------------------------------------
   for (int i = 0; i < npw; i++) patch_piece(0, 0, i, true);
   weight_tile(0, 0, 0);
+  if constexpr (W3) weight_tile(1, 0, 1);
   __syncthreads();
-
-  const int ppt = (npw + 8) / 9;                   // patch pieces of the next slice issued per tap (PB2; <= 2: launcher)
+  Frags carried;                                   // W3: fragments live across the tap boundary
+  if constexpr (W3) { tap_addresses(carried, 0, 0); load(carried, 0, 0, pbufs); }
+  const int ppt = W3 ? (npw + 7) >> 3 : (npw + 8) / 9;   // patch pieces of the next slice issued per tap (PB2; <= 2: launcher)
   auto run_slice = [&](int s, auto nkc) __attribute__((always_inline)) {
     constexpr int NKC = decltype(nkc)::value;      // sub-steps of this slice; 0: run-time
     const int nks = NKC ? NKC : nks_last_rt;
-    const char* patch = smem + (PB2 ? (s & 1) : 0) * patch_bytes;
     const bool next_slice = s + 1 < nslice;
+    const int poff_cur = (PB2 ? (s & 1) : 0) * patch_bytes, poff_nxt = ((s + 1) & 1) * patch_bytes;
     const int step0 = 9 * s;
 #pragma unroll
     for (int t = 0; t < 9; t++) {
-      const int step = step0 + t;
-      // prefetch: weights of the next (slice, tap); a share (<= 2 pieces: launcher) of the next slice's patch. DMA piece k of this
-      // tap: k < NPI = weight piece k, k = NPI, NPI + 1 = patch pieces. A piece costs 60-180 issue cycles: one piece behind each of
-      // the first sub-step's MFMAs, where the matrix pipe is busy anyway.
+      const int wb = W3 ? t % 3 : (step0 + t) & 1;                   // weight buffer of this tap
+      const int wbn = W3 ? (t + LA) % 3 : (step0 + t + 1) & 1;       // ... and of the tap LA ahead (as wb ^ 1 the two-buffer kernels took 2-4 registers more)
+      const char* ps = pbufs + wb * PB;
+      // prefetch: DMA piece k of this tap: k < NPI = piece k of the weights LA taps ahead; k = NPI, NPI + 1 = a share (<= 2 pieces: launcher) of the
+      // next slice's patch
       auto dma_piece = [&](int k) {
         if (k < NPI) {
-          if (t < 8) weight_piece((step + 1) & 1, s, t + 1, k, true);
-          else weight_piece((step + 1) & 1, s + 1, 0, k, next_slice);
-        } else if (PB2) {
+          if (t + LA < 9) weight_piece(wbn, s, t + LA, k, true);
+          else weight_piece(wbn, s + 1, t + LA - 9, k, next_slice);
+        } else if (PB2 && t < NPT) {
           const int i = t * ppt + (k - NPI);
           patch_piece((s + 1) & 1, s + 1, i, next_slice && (k - NPI) < ppt && i < npw);
         }
       };
-      const char* ps = pbufs + (step & 1) * PB;
-      // fragment base addresses of this tap
-      const int tr = t / 3, ts = t % 3;            // compile-time after unrolling
-      unsigned qa[TJ];
-#pragma unroll
-      for (int b = 0; b < TJ; b++) {
-        int row = rb[b];
-        asm volatile("" : "+v"(row));   // keeps the nine taps' address arithmetic inside their taps (hoisted out of the slice loop it spilled)
-        if (tr == 0) row += rs0[b];
-        if (tr == 2) row += rs2[b];
-        if (ts == 0) row += cs0[b];
-        if (ts == 2) row += cs2[b];
-        const int ipar = ((row + P0) >> p.psh) & p.pm4;
-        unsigned a = ((unsigned)row << 7) | ((unsigned)((fhi ^ (row >> 1) ^ ipar) & 7) << 4);
-        a = ((qinv[b] >> t) & 1u) ? (unsigned)(p.zero_off - (PB2 ? (s & 1) : 0) * patch_bytes) : a;
-        qa[b] = a;
-      }
-      bf16x8_t pf[2][TI], qf[2][TJ];
-      auto load = [&](int ks, int slot) {
-#pragma unroll
-        for (int a = 0; a < TI; a++) {
-          const int row = wi0 + a * 32 + frow;
-          const int ch = (ks * 2 + fhi) ^ ((row >> 1) & 7);
-          u32x4 v = *(const u32x4*)(ps + row * 128 + ch * 16);
-          pf[slot][a] = __builtin_bit_cast(bf16x8_t, v);
-        }
-#pragma unroll
-        for (int b = 0; b < TJ; b++) {
-          u32x4 v = *(const u32x4*)(patch + (qa[b] ^ (unsigned)(ks * 32)));
-          if (RELU) v = relu16<bf16_t>(v);
-          qf[slot][b] = __builtin_bit_cast(bf16x8_t, v);
-        }
-      };
-      load(0, 0);
+      Frags own;                                 // two buffers: a tap's fragments live inside the tap (declared outside it they cost 20 registers)
+      Frags& f = W3 ? carried : own;
+      if constexpr (!W3) { tap_addresses(f, t, poff_cur); load(f, 0, 0, ps); }
 #pragma unroll
       for (int ks = 0; ks < 4; ks++) {
-        if (ks < 3 && ks + 1 < nks) load(ks + 1, (ks + 1) & 1);
+        if (ks < 3 && ks + 1 < nks) load(f, ks + 1, (ks + 1) & 1, ps);
         if (ks < nks) {
 #pragma unroll
           for (int a = 0; a < TI; a++)
 #pragma unroll
             for (int b = 0; b < TJ; b++) {
-              acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf[ks & 1][a], qf[ks & 1][b], acc[a][b], 0, 0, 0);
+              acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.pf[ks & 1][a], f.qf[ks & 1][b], acc[a][b], 0, 0, 0);
+              // a piece costs 60-180 issue cycles: one behind each of the first sub-step's MFMAs, where the matrix pipe is busy anyway
               if (ks == 0 && a * TJ + b < NPI + 2) {
                 __builtin_amdgcn_sched_barrier(0);
                 dma_piece(a * TJ + b);
@@ -360,7 +247,12 @@ __global__ __launch_bounds__(64 * WJ * WI) void sg_conv_v3_kernel(ConvV3Params p
             for (int k = TI * TJ; k < NPI + 2; k++) dma_piece(k);
           }
         }
-        __builtin_amdgcn_sched_barrier(0);         // (see the three-buffer path)
+        __builtin_amdgcn_sched_barrier(0);       // the scheduler keeps the software pipeline as written: fragments of sub-step k + 1, then the MFMAs
+                                                 // of sub-step k (left alone it pulls the loads of several sub-steps to the tap's head and spills)
+      }
+      if constexpr (W3) {                        // sub-step 0 of the next tap
+        if (t < 8) { tap_addresses(f, t + 1, poff_cur); load(f, 0, 0, pbufs + ((t + 1) % 3) * PB); }
+        else if (next_slice) { tap_addresses(f, 0, poff_nxt); load(f, 0, 0, pbufs); }
       }
       __syncthreads();
     }
@@ -371,43 +263,37 @@ __global__ __launch_bounds__(64 * WJ * WI) void sg_conv_v3_kernel(ConvV3Params p
   };
   if constexpr (NKL == 4) {
     for (int s = 0; s < nslice; s++) run_slice(s, std::integral_constant<int, 4>{});
-  } else {
+  } else {                                         // last slice peeled (an if / else of the two bodies inside one loop spilled registers)
     for (int s = 0; s + 1 < nslice; s++) run_slice(s, std::integral_constant<int, 4>{});
     run_slice(nslice - 1, std::integral_constant<int, NKL>{});
   }
-
-  }   // !W3
 
   float al = epi.alpha;
   if (epi.alpha_ptr) al *= *epi.alpha_ptr;
   sg_conv_epilogue<BI, BJ, NW, TI, TJ>(acc, smem, sbias, epi, i0, j0, wi0, wj0, al);
 }
 
-template <int BI, int WJ, int WI, int BJ, bool RELU, bool UP, bool PB2, bool W3, int NKL>
-static inline int sg_launch_conv_v3r(ConvV3Params p, const Epilogue<bf16_t>& e, hipStream_t st) {
-  const int patch_bytes = p.npx * 128;
-  int body = (PB2 ? 2 : 1) * patch_bytes + (W3 ? 3 : 2) * BI * 128;
-  const int stage = BJ * (BI * 2 + 16);
-  if (stage > body) body = stage;
-  p.zero_off = body; p.bias_off = body + 128; p.dump_off = body + 128 + BI * 4;
-  const int lds = body + 128 + BI * 4 + 1024;
-  if (lds > 160 * 1024) return -1;
-  static int attr_lds = 0;
-  if (lds > attr_lds) {
-    if (hipFuncSetAttribute((const void*)sg_conv_v3_kernel<BI, WJ, WI, BJ, RELU, UP, PB2, W3, NKL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -1;
-    attr_lds = 160 * 1024;
-  }
-  const int tilesI = (p.I + BI - 1) / BI, tilesJ = (p.J + BJ - 1) / BJ;
-  hipLaunchKernelGGL((sg_conv_v3_kernel<BI, WJ, WI, BJ, RELU, UP, PB2, W3, NKL>), dim3(tilesI * tilesJ), dim3(64 * WJ * WI), lds, st, p, e, tilesI, tilesJ);
-  return 0;
-}
-// LDS need of a configuration (bytes), or -1 when it does not fit
-static inline int sg_conv_v3_lds(int BI, int BJ, int npx, bool pb2, bool w3 = false) {
+// LDS layout and need (bytes) of a configuration, or -1 when it does not fit: [patch(es) | weight buffers], overlaid by the staged output tile; behind it
+// the zero line, the bias vector and the DMA dump area
+static inline int sg_conv_v3_lds(int BI, int BJ, int npx, bool pb2, bool w3 = false, int* zero_off = nullptr, int* bias_off = nullptr, int* dump_off = nullptr) {
   int body = (pb2 ? 2 : 1) * npx * 128 + (w3 ? 3 : 2) * BI * 128;
   const int stage = BJ * (BI * 2 + 16);
   if (stage > body) body = stage;
+  if (zero_off) *zero_off = body;
+  if (bias_off) *bias_off = body + 128;
+  if (dump_off) *dump_off = body + 128 + BI * 4;
   const int lds = body + 128 + BI * 4 + 1024;
   return lds <= 160 * 1024 ? lds : -1;
+}
+template <int BI, int WJ, int WI, int BJ, bool RELU, bool UP, bool PB2, bool W3, int NKL>
+static inline int sg_launch_conv_v3r(ConvV3Params p, const Epilogue<bf16_t>& e, hipStream_t st) {
+  const int lds = sg_conv_v3_lds(BI, BJ, p.npx, PB2, W3, &p.zero_off, &p.bias_off, &p.dump_off);
+  if (lds < 0) return -1;
+  static bool attr_done = false;
+  if (!ht_allow_lds(attr_done, sg_conv_v3_kernel<BI, WJ, WI, BJ, RELU, UP, PB2, W3, NKL>, 160 * 1024)) return -1;
+  const int tilesI = (p.I + BI - 1) / BI, tilesJ = (p.J + BJ - 1) / BJ;
+  hipLaunchKernelGGL((sg_conv_v3_kernel<BI, WJ, WI, BJ, RELU, UP, PB2, W3, NKL>), dim3(tilesI * tilesJ), dim3(64 * WJ * WI), lds, st, p, e, tilesI, tilesJ);
+  return 0;
 }
 template <int BI, int WJ, int WI, int BJ, int NKL>
 static inline int sg_launch_conv_v3(const ConvV3Params& p, const Epilogue<bf16_t>& e, hipStream_t st) {

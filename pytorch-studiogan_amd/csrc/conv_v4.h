@@ -18,10 +18,11 @@
 //     in the fragment addresses; W = 8 / 4 patches are conflict-free as they are (rows r, r + 8 already differ in the key);
 //   * operand LDS 52 KB, staged epilogue 53 KB -> three workgroups per CU (12 waves, 3 per SIMD, from different workgroups: one
 //     computes while another loads its patch or stores its tile). One barrier (4 waves) per tap = per 4 NB MFMAs of a wave.
-// Row bookkeeping (raster / quad order, nearest x2 upsample on load, image-border masks) is conv_v3.h's; epilogue: sg_conv_epilogue.
+// Row bookkeeping (raster / quad order, nearest x2 upsample on load, image-border masks), the 64-byte-row LDS image and its DMA / fragment addressing:
+// halo_tile.h; epilogue: sg_conv_epilogue.
 #pragma once
 #include <type_traits>
-#include "conv_v2.h"
+#include "halo_tile.h"
 
 struct ConvV4Params {
   const bf16_t* x; const bf16_t* w;
@@ -43,8 +44,7 @@ struct ConvV4Params {
   float* stats;           // optional [tilesJ][I][2]: per-tile batch-norm statistics of the result (sg_conv_epilogue), 256-pixel tiles only
 };
 
-// TJW = 32-pixel blocks per wave: 2 (tile 256 pixels, 6 accumulator blocks per wave for NB = 3, three workgroups per CU) or 4 (tile 512 pixels,
-// 12 accumulator blocks: 7 fragment reads per 12 MFMAs instead of 5 per 6, two workgroups per CU; the staged epilogue runs in two halves)
+// TJW = 32-pixel blocks per wave; 2 is the only value built (tile 256 pixels, 6 accumulator blocks per wave for NB = 3, three workgroups per CU)
 //
 // SKIP: the residual block's 1x1 skip convolution rides in the same launch (reference src/models/big_resnet.py:177-192,221-242:
 // `x0 = conv2d0(x0); out = x + x0`). pool(conv3x3(h)) + pool(conv1x1(x)) = pool(conv3x3(h) + conv1x1(x)), and for a generator block
@@ -59,7 +59,7 @@ struct ConvV4Params {
 // are kept alive by a store that never happens), bit 1: no patch reload at the slice boundaries (one barrier instead of the full stop), bit 2: no weight DMA inside
 // the loop (every tap re-reads the prologue's tiles), bit 3: no barrier at the end of a tap, bit 4: no fragment reads (the MFMAs run on the first tap's registers), bit 5: the epilogue without its global stores. Results are wrong by construction; what is read off is the time.
 template <int NB, bool RELU, bool UP, int TJW, bool SKIP = false, int ABL = 0>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TJW == 2 ? 3 : 2, TJW == 2 ? 3 : 2))) void sg_conv_v4_kernel(ConvV4Params p, Epilogue<bf16_t> epi, int tilesI, int tilesJ) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void sg_conv_v4_kernel(ConvV4Params p, Epilogue<bf16_t> epi, int tilesI, int tilesJ) {
   static_assert(TJW == 2, "256-pixel tiles (the 512-pixel instantiation was measured no faster and removed in round 5)");
   static_assert(!SKIP || !UP, "the fused skip is built for the plain tile");
   constexpr int BI = 32 * NB, BJ = 128 * TJW, NW = 4, TI = NB, TJ = TJW;
@@ -69,16 +69,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TJW == 2 ? 
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nt = tilesI * tilesJ;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nt >> 3, r = nt & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int bid = sg_xcd_tile(blockIdx.x, tilesI * tilesJ);
   const int tI = bid % tilesI, tJ = bid / tilesI;
   const int i0 = tI * BI, j0 = tJ * BJ;
   char* const pbufs = smem + p.wgt_off;
   float* sbias = (float*)(smem + p.bias_off);
+  // (= ht_stage_bias + ht_zero_line of halo_tile.h, written out: through the helpers the data gradients of the 96-channel 128^2 layers ran 0.8-3 % slower,
+  // profiles/r11_halo_fold_ab.txt section 3)
   if (epi.bias) {
     for (int i = tid; i < BI; i += 64 * NW) {
       float b = (i0 + i < epi.I) ? epi.bias[i0 + i] : 0.f;
@@ -89,11 +86,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TJW == 2 ? 
   if (tid < 32) ((unsigned*)(smem + p.zero_off))[tid] = 0u;
 
   const auto rsx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.xbytes, 0x00020000);
-  const auto rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (int)p.wbytes, 0x00020000);
-  // DMA piece = 1 KiB = 16 rows x 64 B, LDS linear in lane order: lane -> (row sub = lane >> 2, physical chunk lane & 3); the logical
-  // 16-byte chunk it fetches is the swizzle inverse: lc = (lane & 3) ^ (row >> 2 & 3), and row = 16 g + sub gives (sub >> 2) & 3.
-  const int sub = lane >> 2;
-  const int lc = (lane & 3) ^ ((lane >> 4) & 3);
+  const int sub = ht32_sub(lane), lc = ht32_chunk(lane);              // DMA lane geometry: row of the 16-row piece, logical chunk
   const unsigned ldx2 = 2u * (unsigned)p.ldx;
 
   // ---- patch DMA: groups of 16 consecutive source pixels, group g = wave + 4 i ----------------------------------------------------
@@ -123,21 +116,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TJW == 2 ? 
   };
   // ---- weight DMA: BI rows x 32 channels of (slice s, tap t): per-lane row offsets once per workgroup ---------------------------------
   unsigned wvo[2];
-#pragma unroll
-  for (int i = 0; i < 2; i++) {
-    const int row = i0 + 16 * (wave + NW * i) + sub;
-    wvo[i] = (row < p.I) ? ((unsigned)row * (unsigned)p.K + (unsigned)(lc * 8)) * 2u : 0x80000000u;
-  }
-  auto weight_tile = [&](int buf, int s, int t) {
-    const int so = (t * p.C + s * 32) * 2;
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-      const int g = wave + NW * i;
-      if (g < NWP) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (sg_lptr_t)(pbufs + buf * PB + g * 1024), 16, (int)wvo[i], so, 0, 0);
-    }
-  };
+  ht32_weight_offsets(wvo, i0, wave, sub, lc, p.I, p.K);
+  auto weight_tile = [&](int buf, int s, int t) { ht32_weight_tile<NWP>(p.w, p.wbytes, pbufs + buf * PB, wvo, wave, (t * p.C + s * 32) * 2); };
 
-  // ---- fragment rows of this lane (conv_v3.h's bookkeeping) ------------------------------------------------------------------------
+  // ---- fragment rows of this lane --------------------------------------------------------------------------------------------------
   const int wj0 = wave * (32 * TJ);
   const int frow = lane & 31, fhi = lane >> 5;
   int rb[TJ];             // patch row of the centre pixel
@@ -147,50 +129,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TJW == 2 ? 
   for (int b = 0; b < TJ; b++) {
     const int row = j0 + wj0 + b * 32 + frow;
     int n, ho, wo;
-    if (p.flags & SG_PIX_QUAD) {
-      const int q = row >> 2, dy = (row >> 1) & 1, dx = row & 1;
-      const int wq = q & ((p.Wo >> 1) - 1);
-      const int t = q >> (p.wshift - 1);
-      const int hq = t & ((p.Ho >> 1) - 1);
-      n = t >> (p.hshift - 1);
-      ho = 2 * hq + dy; wo = 2 * wq + dx;
-    } else {
-      wo = row & (p.Wo - 1); const int t = row >> p.wshift; ho = t & (p.Ho - 1); n = t >> p.hshift;
-    }
-    unsigned m = 0;
-    if (row < p.J) {
-#pragma unroll
-      for (int rr = 0; rr < 3; rr++)
-#pragma unroll
-        for (int ss = 0; ss < 3; ss++)
-          if ((unsigned)(ho - 1 + rr) < (unsigned)p.Ho && (unsigned)(wo - 1 + ss) < (unsigned)p.Wo) m |= 1u << (rr * 3 + ss);
-    }
-    qinv[b] = ~m;
-    if (UP) {
-      const int Hs = p.Ho >> 1;
-      const int spc = ((n * Hs + (ho >> 1)) << p.wlog) + (wo >> 1);
-      rb[b] = spc - P0;
-      par[b] = (unsigned)(ho & 1) | ((unsigned)(wo & 1) << 1);
-    } else {
-      rb[b] = (((n << p.hshift) + ho) << p.wshift) + wo - P0;
-      par[b] = 0;
-    }
+    ht_decode_pixel(p, row, n, ho, wo);
+    qinv[b] = ~ht_border_mask(ho, wo, p.Ho, p.Wo, row < p.J);
+    rb[b] = ht_patch_row<UP>(p, n, ho, wo, P0);
+    par[b] = UP ? (unsigned)(ho & 1) | ((unsigned)(wo & 1) << 1) : 0u;
   }
-  // weight fragment addresses: row = cout a * 32 + frow, chunk (ks * 2 + fhi) ^ (row >> 2 & 3); ks = 1 is the address ^ 32
-  unsigned wa[TI];
-#pragma unroll
-  for (int a = 0; a < TI; a++) {
-    const int row = a * 32 + frow;
-    wa[a] = (unsigned)(row * 64 + ((fhi ^ ((row >> 2) & 3)) << 4));
-  }
+  unsigned wa[TI];        // weight fragment addresses inside a weight tile
+  ht32_weight_frag_addr(wa, frow, fhi);
 
   f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int a = 0; a < TI; a++)
-#pragma unroll
-    for (int b = 0; b < TJ; b++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
+  ht_zero_acc(acc);
 
   // Weights run TWO taps ahead through three buffers (buffer of tap t = t % 3, 9 taps per slice): a tap is only 4 NB MFMAs per wave,
   // shorter than the L2 latency of its successor's weights, so the wait in front of the barrier that ends tap t is COUNTED -- it lets
@@ -309,7 +257,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TJW == 2 ? 
   if constexpr (SKIP) {
     // the main loop ended behind vmcnt(0) + barrier: patch area and weight buffers are free
     const auto rsx2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.x2, 0, (int)p.x2bytes, 0x00020000);
-    const auto rsw2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.w2, 0, (int)p.w2bytes, 0x00020000);
     const unsigned ldx2b = 2u * (unsigned)p.ldx2;
     const int Q0 = p.up2 ? (j0 >> 2) : j0;                 // first skip-input pixel (raster) of this tile: the tile covers whole pairs of image rows
     const int ng2 = (p.up2 ? BJ / 4 : BJ) >> 4;            // groups of 16 pixels
@@ -337,12 +284,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TJW == 2 ? 
         off = ((unsigned)pix < (unsigned)p.npix2) ? off : 0x80000000u;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsx2, (sg_lptr_t)(smem + slot * P2B + g * 1024), 16, (int)off, 0, 0, 0);
       }
-      for (int g = wave; g < NWP; g += NW) {
-        const int row = i0 + 16 * g + sub;
-        unsigned off = ((unsigned)row * (unsigned)p.C2 + (unsigned)(s2 * 32 + lc * 8)) * 2u;
-        off = (row < p.I) ? off : 0x80000000u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw2, (sg_lptr_t)(pbufs + slot * PB + g * 1024), 16, (int)off, 0, 0, 0);
-      }
+      ht32_skip_weight_tile<NWP>(pbufs + slot * PB, p, i0, wave, sub, lc, s2);
     };
     const int n2 = p.nslice2;
     for (int i = 0; i < RING - 1 && i < n2; i++) issue2(i, i);
@@ -371,25 +313,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TJW == 2 ? 
         qa[b] = a;
       }
 #pragma unroll
-      for (int ks = 0; ks < 2; ks++) {
-        bf16x8_t pf[TI], qf[TJ];
-#pragma unroll
-        for (int a = 0; a < TI; a++) {
-          u32x4 v = *(const u32x4*)(ps + (wa[a] ^ (unsigned)(ks * 32)));
-          pf[a] = __builtin_bit_cast(bf16x8_t, v);
-        }
-#pragma unroll
-        for (int b = 0; b < TJ; b++) {
-          u32x4 v = *(const u32x4*)(smem + (qa[b] ^ (unsigned)(ks * 32)));
-          if (RELU) v = relu16<bf16_t>(v);
-          qf[b] = __builtin_bit_cast(bf16x8_t, v);
-        }
-#pragma unroll
-        for (int a = 0; a < TI; a++)
-#pragma unroll
-          for (int b = 0; b < TJ; b++)
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf[a], qf[b], acc[a][b], 0, 0, 0);
-      }
+      for (int ks = 0; ks < 2; ks++) ht32_kstep<RELU>(acc, ps, wa, smem, qa, ks);
       slot = slot + 1 == RING ? 0 : slot + 1;
     }
   }
@@ -406,37 +330,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TJW == 2 ? 
         for (int r = 0; r < 16; r++) t += acc[a][b][r];
     if (t == 1234.5f) *(float*)epi.out = t;
   } else if constexpr ((ABL & 32) != 0) {
-    sg_conv_epilogue<BI, BJ, NW, TI, TJ, false, true>(acc, smem, sbias, epi, i0, j0, 0, wj0, al, true, 0, 0, p.stats, p.I, tJ);
-  } else if constexpr (TJW == 2) {
-    sg_conv_epilogue<BI, BJ, NW, TI, TJ>(acc, smem, sbias, epi, i0, j0, 0, wj0, al, true, 0, 0, p.stats, p.I, tJ);
-  } else {   // 512-pixel tile, 256-row staging area: waves 0, 1 then waves 2, 3
-    sg_conv_epilogue<BI, 256, NW, TI, TJ>(acc, smem, sbias, epi, i0, j0, 0, wj0, al, wave < 2);
-    sg_conv_epilogue<BI, 256, NW, TI, TJ>(acc, smem, sbias, epi, i0, j0 + 256, 0, wj0 - 256, al, wave >= 2);
+    sg_conv_epilogue<BI, BJ, NW, TI, TJ, false, true>(acc, smem, sbias, epi, i0, j0, 0, wj0, al, 0, 0, p.stats, p.I, tJ);
+  } else {
+    sg_conv_epilogue<BI, BJ, NW, TI, TJ>(acc, smem, sbias, epi, i0, j0, 0, wj0, al, 0, 0, p.stats, p.I, tJ);
   }
 }
 
 // LDS need (bytes) of a configuration
 static inline int sg_conv_v4_lds(int NB, int npx, int* wgt_off, int* zero_off, int* bias_off, int skip_patch_bytes = 0) {
-  const int BI = 32 * NB;
   // (a fused skip stages its own patches at the start of the operand area: the weight buffers must lie behind them too)
   const int woff = npx * 64 > skip_patch_bytes ? npx * 64 : skip_patch_bytes;
-  const int ops = woff + 3 * BI * 64;
-  const int stage = 256 * (BI * 2 + 16);
-  const int body = ops > stage ? ops : stage;
-  if (wgt_off) *wgt_off = woff;
-  if (zero_off) *zero_off = body;
-  if (bias_off) *bias_off = body + 128;
-  return body + 128 + BI * 4;
+  return ht32_lds(32 * NB, 256, woff, 3, 0, wgt_off, zero_off, bias_off);
 }
 template <int NB, bool RELU, bool UP, int TJW, bool SKIP = false, int ABL = 0>
 static inline int sg_launch_conv_v4r(ConvV4Params p, const Epilogue<bf16_t>& e, hipStream_t st) {
   const int lds = sg_conv_v4_lds(NB, p.npx, &p.wgt_off, &p.zero_off, &p.bias_off, SKIP ? (p.up2 ? 3 * 64 * 64 : 2 * 256 * 64) : 0);
   if (lds > 80 * 1024) return -1;
   static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute((const void*)sg_conv_v4_kernel<NB, RELU, UP, TJW, SKIP, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess) return -1;
-    attr_done = true;
-  }
+  if (!ht_allow_lds(attr_done, sg_conv_v4_kernel<NB, RELU, UP, TJW, SKIP, ABL>, 80 * 1024)) return -1;
   const int BI = 32 * NB, BJ = 128 * TJW;
   const int tilesI = (p.I + BI - 1) / BI, tilesJ = (p.J + BJ - 1) / BJ;
   hipLaunchKernelGGL((sg_conv_v4_kernel<NB, RELU, UP, TJW, SKIP, ABL>), dim3(tilesI * tilesJ), dim3(256), lds, st, p, e, tilesI, tilesJ);

@@ -474,6 +474,14 @@ __device__ __forceinline__ void frag_mc_f32_split3(const char* tile, int pitch, 
   f32x8_split3(x, hi, mid, lo);
 }
 
+// XCD-aware bijective renumbering of the nt workgroups of a launch (guide §5.5 T1): the hardware deals consecutive workgroup ids round-robin to the
+// 8 XCDs; the logical tile index returned here makes consecutive tiles land on ONE XCD, so that neighbours share their operands through its L2.
+// Used by every tile kernel of the library (this file, conv_v2.h, wgrad_v2.h, halo_tile.h's family).
+__device__ __forceinline__ int sg_xcd_tile(int bid, int nt) {
+  const int xcd = bid & 7, q = nt >> 3, r = nt & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // The kernel
 // ---------------------------------------------------------------------------------------------------
@@ -499,13 +507,7 @@ __global__ __launch_bounds__(256) void sg_gemm_kernel(LP lp, LQ lq, Epilogue<T> 
   __shared__ __attribute__((aligned(16))) char smem[2 * (PB + QB)];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // XCD-aware bijective remap: consecutive logical tiles stay on one XCD (shared L2) -- guide §5.5 T1
-  const int nt = tilesI * tilesJ;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nt >> 3, r = nt & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int bid = sg_xcd_tile(blockIdx.x, tilesI * tilesJ);
   const int tI = bid % tilesI, tJ = bid / tilesI;
   const int i0 = tI * BI, j0 = tJ * BJ;
   const int k_begin = blockIdx.y * klen;

@@ -92,12 +92,7 @@ __global__ __launch_bounds__(512) void sg_wgrad_v2_kernel(WgradV2Params p, Epilo
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const auto rsx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.xbytes, 0x00020000);
   const auto rsg = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, (int)p.gbytes, 0x00020000);
-  const int nt = tilesI * tilesJ;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nt >> 3, r = nt & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int bid = sg_xcd_tile(blockIdx.x, tilesI * tilesJ);
   const int tI = bid % tilesI, tJ = bid / tilesI;
   const int i0 = tI * 256, j0 = tJ * BJ;
   const int k_begin = blockIdx.y * p.klen;
