@@ -520,6 +520,23 @@ int sg_chol_lower(double* A, int n, int* flag, sg_stream_t s);          /* in pl
 int sg_dgemm_tn(const double* A, const double* B, double* C, int n, sg_stream_t s);   /* C = A^T B */
 int sg_jacobi_sweep(double* M, int n, double* offd, sg_stream_t s);    /* n even; *offd = max |<r_p, r_q>| / (|r_p| |r_q|) met in the sweep */
 int sg_row_norm_sum(const double* M, int n, double* out, sg_stream_t s);
+/* ---- the Frechet distance of many small sample sets (intra-class FID; csrc/frechet_small.hip). With the centred rows A = (X1 - mu1) / sqrt(n1 - 1),
+ * B = (X2 - mu2) / sqrt(n2 - 1): tr sqrtm(S1 S2) = nuclear norm of A B^T (n1 x n2), tr S = |A|_F^2 -- no d x d matrix. fp32 features [rows][C] with
+ * class-sorted rows, fp64 arithmetic. Segment k = rows seg[k] .. seg[k + 1] (at least 2 each). seg, moff, rows and cols are HOST arrays (the kernels get
+ * them by value); everything else is device memory.
+ * moments: mu[k][c] = mean, tr[k] = sum |x - mu|^2 / (n - 1).
+ * cross_gram: M_k[i][j] = <a_i - mua_k, b_j - mub_k> / sqrt((na - 1)(nb - 1)) at M + moff[k] (doubles), dense [r][c] row-major with the smaller set
+ * along the rows (r = min(na, nb); na == nb: a).
+ * nuclear_norm: per matrix (rows[k] x cols[k] at M + moff[k], read only) one-sided Jacobi sweeps in LDS until the measure of sg_jacobi_sweep is below tol
+ * or max_sweeps are done; nuc[k] = sum of the row norms, offd[k] = the last sweep's measure, sweeps[k] = sweeps run. Only matrices with
+ * sg_seg_nuclear_fits == 1 (everything up to 126 x 126; the budget in bytes: sg_seg_nuclear_lds_budget) may be passed. */
+int sg_seg_moments(const float* f, const long long* seg, int K, int C, double* mu, double* tr, sg_stream_t s);
+int sg_seg_cross_gram(const float* fa, const long long* sega, const double* mua, const float* fb, const long long* segb, const double* mub, int K, int C,
+                      double* M, const long long* moff, sg_stream_t s);
+int sg_seg_nuclear_norm(const double* M, const long long* moff, const int* rows, const int* cols, int K, int max_sweeps, double tol,
+                        double* nuc, double* offd, int* sweeps, sg_stream_t s);
+int sg_seg_nuclear_fits(int rows, int cols);      /* returns 0 / 1 */
+int sg_seg_nuclear_lds_budget(void);              /* returns bytes */
 
 /* ---- StyleGAN2 / StyleGAN3 native operators (the reference's only CUDA code, the .cu files of src/utils/style_ops) ----------------
  * sg_bias_act: y = clamp(gain * act(x + b)) and its gradient evaluators, the contract of the reference's `_plugin.bias_act(x, b, xref, yref,

@@ -225,6 +225,11 @@ _PROTOS = {
     "sg_dgemm_tn": [_vp, _vp, _vp, _i, _vp],
     "sg_jacobi_sweep": [_vp, _i, _vp, _vp],
     "sg_row_norm_sum": [_vp, _i, _vp, _vp],
+    "sg_seg_moments": [_vp, _vp, _i, _i, _vp, _vp, _vp],                                      # seg / moff / rows / cols: HOST arrays
+    "sg_seg_cross_gram": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
+    "sg_seg_nuclear_norm": [_vp, _vp, _vp, _vp, _i, _i, C.c_double, _vp, _vp, _vp, _vp],
+    "sg_seg_nuclear_fits": [_i, _i],                       # returns 0 / 1 (call through lib(), not call())
+    "sg_seg_nuclear_lds_budget": [],                       # returns bytes
     "sg_row_sqnorm": [_vp, _i, _i, _vp, _vp],
     "sg_kth_smallest_rows": [_vp, _ll, _i, _i, _i, _vp, _vp, _vp],
     "sg_prdc_rows": [_vp, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

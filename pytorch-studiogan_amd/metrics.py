@@ -10,6 +10,9 @@ ONE kernel (`sg_quantize_resize_normalize`: bit-exact uint8 quantisation, biline
 NHWC); InceptionV3 runs as 94 fused conv+foldedBN+ReLU launches writing straight into the concat buffers (no cat
 copies), pools and the fc on libsgamd.so; FID moments are accumulated on the device in fp64 instead of gathering
 50k x 2048 features to the host. The matrix square root stays on the host in fp64 like the reference.
+
+  calculate_intra_class_fid / intra_class_frechet       reference src/worker.py:1380-1465 (`-ifid`): all classes' small-sample Frechet distances on the
+                                                        device from the samples themselves (csrc/frechet_small.hip)
 """
 import math
 
@@ -627,7 +630,8 @@ def softmax_rows(logits):
 
 @torch.no_grad()
 def generate_images_and_stack_features(generator, eval_model, num_generate, batch_size, z_dim, num_classes, quantize=True, world_size=1,
-                                       DDP=False, device="cuda", moments=None, z_prior="gaussian", truncation_factor=-1.0, MODEL=None, latent_opt=None, langevin=None):
+                                       DDP=False, device="cuda", moments=None, z_prior="gaussian", truncation_factor=-1.0, MODEL=None, latent_opt=None, langevin=None,
+                                       y_sampler="totally_random"):
     """reference src/metrics/features.py:17-65. Returns (features [n, dim], probs [n, classes], labels list); dim / classes are the backbone's
     (InceptionV3_tf 2048 / 1008, DINO_torch 1536 / 1000).
     moments: optional `FeatureMoments` accumulator fed on the device. It receives exactly the rows the reference keeps
@@ -637,7 +641,8 @@ def generate_images_and_stack_features(generator, eval_model, num_generate, batc
     latent_opt: LOGAN at evaluation time (src/utils/sample.py:96,123-135 with LOSS.lo_steps4eval): dict(discriminator=, lo_rate=, lo_steps=, lo_alpha=, lo_beta=) -- the
     latents take their step along d D(G(z)) / dz (the one place of this function that runs with gradients enabled) before the images are generated.
     langevin: RUN.langevin_sampling (src/utils/sample.py:136-148,195-216): dict(discriminator=, langevin_rate=, langevin_noise_std=, langevin_decay=, langevin_decay_steps=,
-    langevin_steps=) -- losses.langevin_sampling on the drawn latents."""
+    langevin_steps=) -- losses.langevin_sampling on the drawn latents.
+    y_sampler: "totally_random", or an int -- every label is that class and nothing is drawn for the labels (src/utils/sample.py:56-57; intra-class FID)."""
     from .worker import sample_zy, sample_latents
     plain = z_prior == "gaussian" and truncation_factor == -1.0 and getattr(MODEL, "info_type", "N/A") == "N/A" and latent_opt is None and langevin is None
     num_batches = int(math.ceil(float(num_generate) / float(batch_size)))
@@ -653,9 +658,9 @@ def generate_images_and_stack_features(generator, eval_model, num_generate, batc
     feats, probs, labels = [], [], []
     for b in range(num_batches):
         if plain:
-            zs, ys = sample_zy(batch_size, z_dim, num_classes, device)
+            zs, ys = sample_zy(batch_size, z_dim, num_classes, device, y_sampler=y_sampler)
         else:
-            zs, ys = sample_latents(batch_size, z_dim, num_classes, device, z_prior=z_prior, truncation_factor=truncation_factor, MODEL=MODEL)
+            zs, ys = sample_latents(batch_size, z_dim, num_classes, device, z_prior=z_prior, truncation_factor=truncation_factor, MODEL=MODEL, y_sampler=y_sampler)
         if latent_opt is not None:
             from .losses import latent_optimise
             with torch.enable_grad():
@@ -740,6 +745,24 @@ def frechet_inception_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
     return diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * np.trace(covmean)
 
 
+def _nuclear_norm_sweeps(B, ne, max_sweeps, tol):
+    """Sum of the singular values of the [ne][ne] fp64 device matrix B (ne even; B is overwritten): one sg_jacobi_sweep launch train and one read-back of the
+    convergence measure per sweep, then sg_row_norm_sum. Returns (value, sweeps run)."""
+    offd = torch.zeros(1, dtype=torch.float64, device=B.device)
+    sweeps = 0
+    for _ in range(max_sweeps):
+        L.call("sg_jacobi_sweep", L.ptr(B), ne, L.ptr(offd), L.stream())
+        sweeps += 1
+        if float(offd.item()) < tol:
+            break
+    else:
+        if float(offd.item()) > 1e-8:       # (the sum of the singular values is second-order accurate in this measure)
+            raise RuntimeError(f"one-sided Jacobi did not converge in {max_sweeps} sweeps (off-diagonal measure {float(offd.item()):.2e})")
+    nuc = torch.zeros(1, dtype=torch.float64, device=B.device)
+    L.call("sg_row_norm_sum", L.ptr(B), ne, L.ptr(nuc), L.stream())
+    return float(nuc.item()), sweeps
+
+
 def frechet_inception_distance_device(mu1, sigma1, mu2, sigma2, device=None, max_sweeps=40, tol=1e-12):
     """The same distance with tr sqrtm(S1 S2) computed on the GPU in fp64 (csrc/linalg.hip): Cholesky factors, B = L2^T L1, one-sided
     Jacobi sweeps until the rows of B are orthogonal to `tol`, sum of their norms (= sum of sqrt of the eigenvalues of S1 S2).
@@ -763,18 +786,210 @@ def frechet_inception_distance_device(mu1, sigma1, mu2, sigma2, device=None, max
         Bp = torch.zeros((ne, ne), dtype=torch.float64, device=dev)
         Bp[:n, :n] = B
         B = Bp
-    offd = torch.zeros(1, dtype=torch.float64, device=dev)
-    for _ in range(max_sweeps):
-        L.call("sg_jacobi_sweep", L.ptr(B), ne, L.ptr(offd), L.stream())
-        if float(offd.item()) < tol:
-            break
-    else:
-        if float(offd.item()) > 1e-8:       # (the sum of the singular values is second-order accurate in this measure)
-            raise RuntimeError(f"one-sided Jacobi did not converge in {max_sweeps} sweeps (off-diagonal measure {float(offd.item()):.2e})")
-    nuc = torch.zeros(1, dtype=torch.float64, device=dev)
-    L.call("sg_row_norm_sum", L.ptr(B), ne, L.ptr(nuc), L.stream())
+    nuc, _ = _nuclear_norm_sweeps(B, ne, max_sweeps, tol)
     diff = mu1 - mu2
-    return float(diff.dot(diff) + np.trace(s1) + np.trace(s2) - 2.0 * float(nuc.item()))
+    return float(diff.dot(diff) + np.trace(s1) + np.trace(s2) - 2.0 * nuc)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the Frechet distance of small sample sets, many at a time (csrc/frechet_small.hip) -- intra-class FID
+# ---------------------------------------------------------------------------------------------------------
+def _host_ptr(a):
+    return a.ctypes.data
+
+
+SQUARE_ROUTE_MAX = 4096      # largest side of a cross-Gram matrix the padded square route takes: 128 MiB of fp64 and 4095 launches per Jacobi sweep
+
+
+def takes_sample_route(na, nb, dim):
+    """Whether a pair of sets with na and nb samples of width dim goes through the sample route (csrc/frechet_small.hip) in frechet_distance_from_features and
+    intra_class_frechet. It does when (1) min(na, nb) <= dim -- a covariance is singular, the moment route would fall back to the host -- and (2) the
+    min x max cross-Gram matrix either fits the in-LDS kernel (sg_seg_nuclear_fits) or has max(na, nb) <= SQUARE_ROUTE_MAX: beyond the LDS budget the matrix is
+    padded to a max x max square, so a few fakes against a large real set (2000 against 50000) would mean a 20 GB matrix and 49999 launches per sweep; such a
+    pair keeps the moment route (and its ~10 s of host time when a covariance is singular). Runs on the host."""
+    r, c = int(min(na, nb)), int(max(na, nb))
+    return r <= dim and (bool(L.lib().sg_seg_nuclear_fits(r, c)) or c <= SQUARE_ROUTE_MAX)
+
+
+def _frechet_segments(fa, sega, fb, segb, names, max_sweeps, tol, workspace_bytes, stats=None):
+    """Frechet distance of K pairs of row segments (fa rows sega[k]:sega[k+1] against fb rows segb[k]:segb[k+1]; fp32 contiguous device tensors, host int64 offsets)
+    from the samples themselves: |mu_a - mu_b|^2 + tr S_a + tr S_b - 2 |A B^T|_*. Classes are taken in chunks whose workspace (two [k][C] means and the
+    cross-Gram matrices, fp64) stays under workspace_bytes (one class at least). Matrices within sg_seg_nuclear_fits take ONE in-LDS launch per chunk; the others
+    are padded to an even square for sg_jacobi_sweep. names[k]: what to call pair k in an error. stats: optional dict that receives lists `sweeps`, `route`."""
+    K, C = len(sega) - 1, fa.shape[1]
+    dev = fa.device
+    na, nb = np.diff(sega), np.diff(segb)
+    for k in range(K):
+        if na[k] < 2 or nb[k] < 2:
+            raise ValueError(f"{names[k]}: {int(na[k])} and {int(nb[k])} samples; the Frechet distance needs at least 2 on both sides")
+    r, c = np.minimum(na, nb), np.maximum(na, nb)
+    cost = 8 * (2 * C + r * c)
+    fits = L.lib().sg_seg_nuclear_fits
+    out = np.empty(K, dtype=np.float64)
+    k0 = 0
+    while k0 < K:
+        k1, used = k0 + 1, int(cost[k0])
+        while k1 < K and used + int(cost[k1]) <= workspace_bytes:
+            used += int(cost[k1])
+            k1 += 1
+        kc = k1 - k0
+        sa, sb = np.ascontiguousarray(sega[k0:k1 + 1]), np.ascontiguousarray(segb[k0:k1 + 1])
+        moff = np.zeros(kc + 1, dtype=np.int64)
+        moff[1:] = np.cumsum(r[k0:k1] * c[k0:k1])
+        mu = torch.empty((2, kc, C), dtype=torch.float64, device=dev)
+        tr = torch.empty((2, kc), dtype=torch.float64, device=dev)
+        M = torch.empty(int(moff[kc]), dtype=torch.float64, device=dev)
+        st = L.stream()
+        L.call("sg_seg_moments", L.ptr(fa), _host_ptr(sa), kc, C, L.ptr(mu[0]), L.ptr(tr[0]), st)
+        L.call("sg_seg_moments", L.ptr(fb), _host_ptr(sb), kc, C, L.ptr(mu[1]), L.ptr(tr[1]), st)
+        L.call("sg_seg_cross_gram", L.ptr(fa), _host_ptr(sa), L.ptr(mu[0]), L.ptr(fb), _host_ptr(sb), L.ptr(mu[1]), kc, C, L.ptr(M), _host_ptr(moff), st)
+        rows, cols = r[k0:k1].astype(np.int32), c[k0:k1].astype(np.int32)
+        lds = np.array([bool(fits(int(rows[i]), int(cols[i]))) for i in range(kc)])
+        nuc = np.empty(kc, dtype=np.float64)
+        swp = np.zeros(kc, dtype=np.int64)
+        idx = np.nonzero(lds)[0]
+        if len(idx):
+            d_nuc = torch.empty((2, len(idx)), dtype=torch.float64, device=dev)
+            d_swp = torch.empty(len(idx), dtype=torch.int32, device=dev)
+            mo, ro, co = np.ascontiguousarray(moff[idx]), np.ascontiguousarray(rows[idx]), np.ascontiguousarray(cols[idx])
+            L.call("sg_seg_nuclear_norm", L.ptr(M), _host_ptr(mo), _host_ptr(ro), _host_ptr(co), len(idx), max_sweeps, float(tol),
+                   L.ptr(d_nuc[0]), L.ptr(d_nuc[1]), L.ptr(d_swp), st)
+            h = d_nuc.cpu().numpy()
+            nuc[idx], swp[idx] = h[0], d_swp.cpu().numpy()
+            bad = np.nonzero(~(h[1] <= max(tol, 1e-8)))[0]      # (as the square route: a measure between tol and 1e-8 after max_sweeps is accepted)
+            if len(bad):
+                i = int(idx[bad[0]])
+                raise RuntimeError(f"{names[k0 + i]}: one-sided Jacobi did not converge in {max_sweeps} sweeps (off-diagonal measure {float(h[1][bad[0]]):.2e})")
+        for i in np.nonzero(~lds)[0]:
+            ri, ci = int(rows[i]), int(cols[i])
+            ne = ci + (ci & 1)
+            B = torch.zeros((ne, ne), dtype=torch.float64, device=dev)
+            B[:ri, :ci] = M[int(moff[i]):int(moff[i + 1])].view(ri, ci)
+            nuc[i], swp[i] = _nuclear_norm_sweeps(B, ne, max_sweeps, tol)
+        d2 = ((mu[0] - mu[1]) ** 2).sum(1)
+        out[k0:k1] = (d2 + tr[0] + tr[1]).cpu().numpy() - 2.0 * nuc
+        if stats is not None:
+            stats.setdefault("sweeps", []).extend(int(v) for v in swp)
+            stats.setdefault("route", []).extend("lds" if v else "square" for v in lds)
+        k0 = k1
+    return out
+
+
+def _device_features(f, dev=None):
+    """fp32 contiguous [n, dim] on `dev` (default: where f lives if that is a GPU, else the current GPU)"""
+    f = torch.as_tensor(f)
+    if dev is None:
+        dev = f.device if f.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    f = f.to(device=torch.device(dev), dtype=torch.float32).contiguous()
+    if f.dim() != 2:
+        raise ValueError(f"features: a [n, dim] matrix expected, got {tuple(f.shape)}")
+    return f
+
+
+@torch.no_grad()
+def frechet_distance_from_features(fa, fb, max_sweeps=40, tol=1e-12, device=None):
+    """Frechet distance between the Gaussians fitted to two feature sets [na, dim], [nb, dim] (np.mean / np.cov of each, reference src/metrics/fid.py:94-98, then
+    fid.py:34-62). min(na, nb) <= dim -- at least one covariance is singular, where the moment route below falls back to the host --: the sample route, from the
+    centred rows themselves (csrc/frechet_small.hip), unless the larger set has more than SQUARE_ROUTE_MAX = 4096 rows and the cross-Gram matrix is beyond the
+    LDS budget (takes_sample_route says which). Otherwise: the moments on the device and frechet_inception_distance_device. Returns a python float."""
+    fa = _device_features(fa, device)
+    fb = _device_features(fb, fa.device)
+    na, nb, dim = fa.shape[0], fb.shape[0], fa.shape[1]
+    if fb.shape[1] != dim:
+        raise ValueError(f"feature widths differ: {dim} and {fb.shape[1]}")
+    if takes_sample_route(na, nb, dim):
+        seg = lambda n: np.array([0, n], dtype=np.int64)
+        return float(_frechet_segments(fa, seg(na), fb, seg(nb), ["the pair of sets"], max_sweeps, tol, 1 << 62)[0])
+    m1, s1 = calculate_moments(fa)
+    m2, s2 = calculate_moments(fb)
+    return frechet_inception_distance_device(m1, s1, m2, s2, device=fa.device, max_sweeps=max_sweeps, tol=tol)
+
+
+def _class_counts(labels, n_rows, num_classes, what):
+    """host labels [n] (int64) and the per-class counts; nothing here touches the device unless the labels live there"""
+    lab = torch.as_tensor(labels).reshape(-1).cpu().numpy().astype(np.int64)
+    if lab.shape[0] != n_rows:
+        raise ValueError(f"{what}: {n_rows} feature rows and {lab.shape[0]} labels")
+    if lab.size and (lab.min() < 0 or lab.max() >= num_classes):
+        raise ValueError(f"{what}: labels outside [0, {num_classes})")
+    return lab, np.bincount(lab, minlength=num_classes).astype(np.int64)
+
+
+def _class_sorted(feats, lab, counts):
+    """rows sorted by class (stable) and the int64 row offsets [num_classes + 1] of the classes"""
+    order = torch.from_numpy(np.argsort(lab, kind="stable")).to(feats.device)
+    seg = np.zeros(len(counts) + 1, dtype=np.int64)
+    seg[1:] = np.cumsum(counts)
+    return feats.index_select(0, order).contiguous(), seg
+
+
+@torch.no_grad()
+def intra_class_frechet(real_feats, real_labels, fake_feats, fake_labels, num_classes, max_sweeps=40, tol=1e-12, workspace_bytes=1 << 30, stats=None, device=None):
+    """Per class the Frechet distance between that class's real and fake features (what reference src/worker.py:1380-1465 computes class by class with np.cov and
+    scipy.linalg.sqrtm): float64 array [num_classes]. The rows are sorted by class once; all classes with min(n_real, n_fake) <= dim and at most
+    SQUARE_ROUTE_MAX = 4096 samples a side (takes_sample_route) -- every class of every dataset the reference evaluates -- go through the batched sample route in chunks of at most workspace_bytes of fp64 workspace, the others through the moment
+    route one by one. A class with fewer than 2 samples on either side raises ValueError naming it; a Jacobi measure above 1e-8 after max_sweeps raises
+    RuntimeError. stats: optional dict, receives the sweeps and the route ("lds" / "square") of every sample-route class. device: where to compute (default: the
+    features' GPU, else the current one)."""
+    real_feats, fake_feats = torch.as_tensor(real_feats), torch.as_tensor(fake_feats)
+    if real_feats.dim() != 2 or fake_feats.dim() != 2 or real_feats.shape[1] != fake_feats.shape[1]:
+        raise ValueError(f"features: [n, dim] matrices of one width expected, got {tuple(real_feats.shape)} and {tuple(fake_feats.shape)}")
+    dim = real_feats.shape[1]
+    la, na = _class_counts(real_labels, real_feats.shape[0], num_classes, "real")
+    lb, nb = _class_counts(fake_labels, fake_feats.shape[0], num_classes, "fake")
+    for k in range(num_classes):
+        if na[k] < 2 or nb[k] < 2:
+            raise ValueError(f"class {k}: {int(na[k])} real and {int(nb[k])} fake samples; intra-class FID needs at least 2 of each")
+    fa = _device_features(real_feats, device)
+    fb = _device_features(fake_feats, fa.device)
+    fa, sega = _class_sorted(fa, la, na)
+    fb, segb = _class_sorted(fb, lb, nb)
+    out = np.empty(num_classes, dtype=np.float64)
+    small = np.array([takes_sample_route(na[k], nb[k], dim) for k in range(num_classes)])
+    if small.all():
+        out[:] = _frechet_segments(fa, sega, fb, segb, [f"class {k}" for k in range(num_classes)], max_sweeps, tol, workspace_bytes, stats)
+    else:
+        for k in range(num_classes):        # (some class keeps the moment route: class by class, each on its own route)
+            a, b = fa[sega[k]:sega[k + 1]], fb[segb[k]:segb[k + 1]]
+            if small[k]:
+                out[k] = _frechet_segments(a, np.array([0, na[k]], dtype=np.int64), b, np.array([0, nb[k]], dtype=np.int64), [f"class {k}"], max_sweeps, tol,
+                                           workspace_bytes, stats)[0]
+            else:
+                out[k] = frechet_distance_from_features(a, b, max_sweeps, tol, device=fa.device)
+    return out
+
+
+def calculate_intra_class_fid(generator, eval_model, real_feats, real_labels, num_classes, batch_size, z_dim, quantize=True, trim_last_batch=False,
+                              world_size=1, DDP=False, device="cuda", z_prior="gaussian", truncation_factor=-1.0, MODEL=None, latent_opt=None, langevin=None,
+                              max_sweeps=40, tol=1e-12, workspace_bytes=1 << 30):
+    """reference src/worker.py:1380-1465 (`-ifid`): for every class c, n_c = that class's real samples; ceil(n_c / batch_size) batches of fakes with every label c
+    (y_sampler=c), the first n_c rows kept; FID between the two; the mean over the classes. real_feats / real_labels: the eval model's features of the real
+    images and their class labels (the reference recomputes them class by class from a per-class sampler: the same rows). Returns (mean, per_class float64
+    [num_classes]). The feature extraction is the reference's loop (generate_images_and_stack_features and its sampling keywords); all the distances are then
+    taken together on the device (intra_class_frechet).
+    trim_last_batch: generate only the n_c % batch_size rows that are kept in the last batch, instead of a full batch whose tail is dropped (draws fewer latents
+    than the reference, so a seeded run differs from it).
+    Single process: world_size > 1 raises NotImplementedError (the reference gathers the ranks' features; here one process generates every class)."""
+    if world_size > 1 or DDP:
+        raise NotImplementedError("calculate_intra_class_fid runs in one process (world_size 1)")
+    _, counts = _class_counts(real_labels, torch.as_tensor(real_feats).shape[0], num_classes, "real")
+    for c in range(num_classes):
+        if counts[c] < 2:
+            raise ValueError(f"class {c}: {int(counts[c])} real samples; intra-class FID needs at least 2")
+    kw = dict(quantize=quantize, device=device, z_prior=z_prior, truncation_factor=truncation_factor, MODEL=MODEL, latent_opt=latent_opt, langevin=langevin)
+    feats, labels = [], []
+    for c in range(num_classes):
+        n = int(counts[c])
+        full = (n // batch_size) * batch_size if trim_last_batch else n
+        if full:
+            f, _, _ = generate_images_and_stack_features(generator, eval_model, full, batch_size, z_dim, num_classes, y_sampler=c, **kw)
+            feats.append(f[:full])
+        if n - full:
+            f, _, _ = generate_images_and_stack_features(generator, eval_model, n - full, n - full, z_dim, num_classes, y_sampler=c, **kw)
+            feats.append(f)
+        labels.append(torch.full((n,), c, dtype=torch.long))
+    per_class = intra_class_frechet(real_feats, real_labels, torch.cat(feats, 0), torch.cat(labels, 0), num_classes, max_sweeps, tol, workspace_bytes)
+    return float(per_class.mean()), per_class
 
 
 def calculate_kl_div(ps, splits):

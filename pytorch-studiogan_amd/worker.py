@@ -6,6 +6,7 @@ bench.py, __graft_entry__.smoke() and the step-parity tests run this; on a Studi
 (INTEGRATION.md).
 """
 import copy
+import numbers
 
 import torch
 
@@ -79,11 +80,21 @@ def reset_bn_statistics(m):
         m.reset_running_stats()
 
 
-def sample_latents(batch_size, z_dim, num_classes, device, z_prior="gaussian", truncation_factor=-1.0, MODEL=None):
-    """(zs, fake_labels) of one evaluation / standing-statistics batch in the reference's draw order (src/utils/sample.py:69-118 with y_sampler "totally_random"):
+def sample_y(y_sampler, batch_size, num_classes, device, generator=None):
+    """reference src/utils/sample.py:43-66 for the two samplers of the evaluation loops: "totally_random" draws the labels on the device; an int fixes the label of the
+    whole batch and draws NOTHING (sample.py:56-57: intra-class FID generates one class at a time)."""
+    if isinstance(y_sampler, numbers.Integral) and not isinstance(y_sampler, bool):
+        return torch.full((batch_size,), int(y_sampler), dtype=torch.long, device=device)
+    if y_sampler != "totally_random":
+        raise NotImplementedError(f"y_sampler {y_sampler!r}: 'totally_random' or an int (one fixed class)")
+    return torch.randint(low=0, high=max(num_classes, 1), size=(batch_size,), dtype=torch.long, device=device, generator=generator)
+
+
+def sample_latents(batch_size, z_dim, num_classes, device, z_prior="gaussian", truncation_factor=-1.0, MODEL=None, y_sampler="totally_random"):
+    """(zs, fake_labels) of one evaluation / standing-statistics batch in the reference's draw order (src/utils/sample.py:69-118; y_sampler: sample_y above):
     labels on the device; latents -- N(0, I) on the device, the truncated normal of scipy on the host when truncation_factor > 0 (sample.py:27-40), U(-1, 1) on the
     host for the uniform prior; then InfoGAN's discrete (one-hot) and continuous codes behind z."""
-    ys = torch.randint(low=0, high=max(num_classes, 1), size=(batch_size,), dtype=torch.long, device=device)
+    ys = sample_y(y_sampler, batch_size, num_classes, device)
     if z_prior == "gaussian":
         if truncation_factor == -1.0:
             zs = torch.randn(batch_size, z_dim, device=device)
@@ -153,10 +164,10 @@ class GeneratorController:
         return self.generator, None, None          # (generator, generator_mapping, generator_synthesis): the StyleGAN halves do not exist here
 
 
-def sample_zy(batch_size, z_dim, num_classes, device, generator=None, z_prior="gaussian"):
-    """reference src/utils/sample.py:69-76 ('totally_random' labels): the LABELS are drawn first, then the latents -- N(0, I) on the device, U(-1, 1) on the
-    host generator for the uniform prior (nothing else is drawn for it) -- so a seeded run consumes the generators in the reference's order."""
-    ys = torch.randint(low=0, high=max(num_classes, 1), size=(batch_size,), dtype=torch.long, device=device, generator=generator)
+def sample_zy(batch_size, z_dim, num_classes, device, generator=None, z_prior="gaussian", y_sampler="totally_random"):
+    """reference src/utils/sample.py:69-76: the LABELS come first ('totally_random': drawn; an int: that class, nothing drawn -- sample_y), then the latents -- N(0, I)
+    on the device, U(-1, 1) on the host generator for the uniform prior (nothing else is drawn for it) -- so a seeded run consumes the generators in the reference's order."""
+    ys = sample_y(y_sampler, batch_size, num_classes, device, generator=generator)
     if z_prior == "gaussian":
         zs = torch.randn(batch_size, z_dim, device=device, generator=generator)
     elif z_prior == "uniform":
