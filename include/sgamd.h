@@ -326,6 +326,23 @@ int sg_bn_bwd2_apply(int dtype, const void* x, const void* dy, const void* u, vo
                      const float* mean, const float* invstd, const float* gain, const float* bias, int relu, const double* chan,
                      double count, int use_batch_stats, sg_stream_t s);
 
+/* the same for a batch norm with PER-SAMPLE affine rows (conditional batch norm; latent optimisation through a class-conditional
+ * generator, reference utils/losses.py:278-298): gain / bias rows of pitch gb_stride_n as in sg_bn_bwd_reduce (either may be NULL: 1 / 0).
+ * The first-order operator has three outputs (dx, dgain rows, dbias rows); u, A, B are their cotangents (A, B: fp32 rows of pitch
+ * gb_stride_n, either may be NULL = 0). sums[N][C][5] fp32 as above (caller zeroes) -> chan[C][7] fp64 = {sum u, sum u*xhat,
+ * sum gain*dy', sum gain*dy'*xhat, sum gain*u*dy', sum A*dy', sum A*dy'*xhat} -> g_dy, g_x (either may be NULL) and
+ * dgain[n][c] += dL/dgain_n (rows of pitch gb_stride_n). The bias rows get no gradient. Single rank: no cross-rank reduction. */
+int sg_cbn_bwd2_reduce(int dtype, const void* x, const void* dy, const void* u, int N, long long HW, int C, const float* mean,
+                       const float* invstd, const float* gain, const float* bias, int gb_stride_n, int relu, float* sums,
+                       sg_stream_t s);
+int sg_cbn_bwd2_finalize(const float* sums, int N, int C, const float* gain, const float* A, int gb_stride_n, double* chan,
+                         sg_stream_t s);
+int sg_cbn_bwd2_dgain(const float* sums, const double* chan, double count, const float* invstd, int N, int C, int gb_stride_n,
+                      int use_batch_stats, float* dgain, sg_stream_t s);
+int sg_cbn_bwd2_apply(int dtype, const void* x, const void* dy, const void* u, void* g_dy, void* g_x, int N, long long HW, int C,
+                      const float* mean, const float* invstd, const float* gain, const float* bias, const float* A, const float* B,
+                      int gb_stride_n, int relu, const double* chan, double count, int use_batch_stats, sg_stream_t s);
+
 /* ---- spectral norm (torch.nn.utils.spectral_norm, eps 1e-6, one power iteration per forward) -------------- */
 typedef struct {
   const float* w;     /* weight_orig viewed as [rows][cols] (OIHW flattened; [num_embeddings][dim] for embeddings) */

@@ -171,6 +171,10 @@ _PROTOS = {
     "sg_bn_bwd2_finalize": [_vp, _i, _i, _vp, _vp],
     "sg_bn_bwd2_dgain": [_vp, _vp, C.c_double, _vp, _i, _i, _vp, _vp],
     "sg_bn_bwd2_apply": [_i, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp, _i, _vp, C.c_double, _i, _vp],
+    "sg_cbn_bwd2_reduce": [_i, _vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
+    "sg_cbn_bwd2_finalize": [_vp, _i, _i, _vp, _vp, _i, _vp, _vp],
+    "sg_cbn_bwd2_dgain": [_vp, _vp, C.c_double, _vp, _i, _i, _i, _i, _vp, _vp],
+    "sg_cbn_bwd2_apply": [_i, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, C.c_double, _i, _vp],
     "sg_attn_fwd_flash_ok": [_i, _i, _i, _i, _i],
     "sg_attn_fwd_fused": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "sg_attn_bwd_fused_ok": [_i, _i, _i, _i, _i],

@@ -637,3 +637,178 @@ extern "C" int sg_bn_bwd2_apply(int dtype, const void* x, const void* dy, const 
   SG_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- second-order backward with per-sample affine rows (conditional batch norm: latent optimisation through a class-conditional generator) ----
+// First order (per channel; sample n has the rows gam_n, bet_n; r = invstd, M = count, s = 1 with batch statistics else 0; g = dy' after the
+// ReLU mask [gam_n xhat + bet_n > 0], h = gam_n g):
+//     dx     = r ( h - s mean(h) - s xhat mean(h xhat) )        dgam_n = sum_p g xhat        dbet_n = sum_p g
+// Given the cotangents u (of dx), A_n (of dgam_n), B_n (of dbet_n), with  ub = mean(u), a = mean(u xhat), hb = mean(h), ch = mean(h xhat),
+// mh = mean(u h), w = A_n g, wb = mean(w), wx = mean(w xhat):
+//     dL/d(dy)   = mask * ( gam_n r (u - s ub - s xhat a) + A_n xhat + B_n )
+//     dL/dgam_n  = r ( sum_p g u - s ub sum_p g - s a sum_p g xhat )
+//     dL/dx      = s r^2 ( -ch (u - ub) - a (h - hb) + xhat (3 a ch - mh + ub hb) ) + r ( w - s wb - s xhat wx )
+//     dL/dbet_n  = 0                                              (the bias enters through the mask only)
+// With gam_n = g_c for every n and A = B = 0 these are the per-channel formulas above. Same launch structure: reduce -> finalize -> apply (+ gain rows).
+// stage 1: sums[n][c][5] = {sum u, sum u xhat, sum g, sum g xhat, sum u g} (the per-channel pass's five; only the mask reads the rows); caller zeroes sums
+template <typename T> __global__ __launch_bounds__(256) void k_cbn_bwd2_reduce(const T* x, const T* dy, const T* u, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, int gsn, int relu, float* sums, long long rpb) {
+  __shared__ float sm[5][4][64];
+  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + cx;
+  const int n = blockIdx.z;
+  long long r0 = blockIdx.y * rpb, r1 = r0 + rpb; if (r1 > HW) r1 = HW;
+  float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  if (c < C) {
+    const float mu = mean[c], is = invstd[c];
+    const float ga = gain ? gain[(long long)n * gsn + c] : 1.f;
+    const float bi = bias ? bias[(long long)n * gsn + c] : 0.f;
+    const long long base = (long long)n * HW * C + c;
+    for (long long r = r0 + ry; r < r1; r += 4) {
+      const float xh = (to_f<T>(x[base + r * C]) - mu) * is;
+      float g = to_f<T>(dy[base + r * C]);
+      if (relu && !(xh * ga + bi > 0.f)) g = 0.f;
+      const float uu = to_f<T>(u[base + r * C]);
+      s[0] += uu; s[1] += uu * xh; s[2] += g; s[3] += g * xh; s[4] += uu * g;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 5; k++) sm[k][ry][cx] = s[k];
+  __syncthreads();
+  if (ry == 0 && c < C) {
+    float* o = sums + ((long long)n * C + c) * 5;
+#pragma unroll
+    for (int k = 0; k < 5; k++) unsafeAtomicAdd(o + k, sm[k][0][cx] + sm[k][1][cx] + sm[k][2][cx] + sm[k][3][cx]);
+  }
+}
+extern "C" int sg_cbn_bwd2_reduce(int dtype, const void* x, const void* dy, const void* u, int N, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, int gb_stride_n, int relu, float* sums, sg_stream_t s) {
+  SG_CHECK(x && dy && u && mean && invstd && sums && N > 0 && HW > 0 && C > 0, "sg_cbn_bwd2_reduce: bad args");
+  SG_CHECK(N <= 65535, "sg_cbn_bwd2_reduce: batch too large for grid.z");
+  SG_CHECK((!gain && !bias) || gb_stride_n >= C, "sg_cbn_bwd2_reduce: row pitch below C");
+  int ct = (C + 63) / 64;
+  long long want = 2048 / ((long long)ct * N); if (want < 1) want = 1;
+  long long rpb = (HW + want - 1) / want; if (rpb < 16) rpb = 16;
+  int gy = (int)((HW + rpb - 1) / rpb);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(k_cbn_bwd2_reduce<T>, dim3(ct, gy, N), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (const T*)u, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, sums, rpb));
+  SG_LAUNCH_CHECK();
+  return 0;
+}
+// stage 2: chan[c][7] (fp64) = {sum_n S0, sum_n S1, sum_n gam_n S2, sum_n gam_n S3, sum_n gam_n S4, sum_n A_n S2, sum_n A_n S3}; block = 64 channels x 4 sample
+// groups, combined in a fixed order (deterministic). A (cotangent of the gain rows, pitch gsn as the rows themselves) may be null
+__global__ __launch_bounds__(256) void k_cbn_bwd2_finalize(const float* sums, int N, int C, const float* gain, const float* A, int gsn, double* chan) {
+  __shared__ double sa[7][4][64];
+  const int cl = threadIdx.x & 63, grp = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + cl;
+  double a[7] = {0, 0, 0, 0, 0, 0, 0};
+  if (c < C) {
+    for (int n = grp; n < N; n += 4) {
+      const float* sp = sums + ((long long)n * C + c) * 5;
+      const double ga = gain ? (double)gain[(long long)n * gsn + c] : 1.0;
+      const double an = A ? (double)A[(long long)n * gsn + c] : 0.0;
+      a[0] += (double)sp[0]; a[1] += (double)sp[1];
+      a[2] += ga * sp[2]; a[3] += ga * sp[3]; a[4] += ga * sp[4];
+      a[5] += an * sp[2]; a[6] += an * sp[3];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 7; k++) sa[k][grp][cl] = a[k];
+  __syncthreads();
+  if (grp == 0 && c < C) {
+#pragma unroll
+    for (int k = 0; k < 7; k++) chan[7 * c + k] = (sa[k][0][cl] + sa[k][1][cl]) + (sa[k][2][cl] + sa[k][3][cl]);
+  }
+}
+extern "C" int sg_cbn_bwd2_finalize(const float* sums, int N, int C, const float* gain, const float* A, int gb_stride_n, double* chan, sg_stream_t s) {
+  SG_CHECK(sums && chan && N > 0 && C > 0, "sg_cbn_bwd2_finalize: bad args");
+  SG_CHECK((!gain && !A) || gb_stride_n >= C, "sg_cbn_bwd2_finalize: row pitch below C");
+  hipLaunchKernelGGL(k_cbn_bwd2_finalize, dim3((C + 63) / 64), dim3(256), 0, (hipStream_t)s, sums, N, C, gain, A, gb_stride_n, chan);
+  SG_LAUNCH_CHECK();
+  return 0;
+}
+// gradient of the gain rows: dgain[n][c] += r ( S4 - s ub S2 - s a S3 ), rows of pitch gsn
+__global__ __launch_bounds__(256) void k_cbn_bwd2_dgain(const float* sums, const double* chan, double count, const float* invstd, int N, int C, int gsn, int use_batch, float* dgain) {
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  if (i >= (long long)N * C) return;
+  const int c = (int)(i % C); const long long n = i / C;
+  const float* sp = sums + i * 5;
+  double v = (double)sp[4];
+  if (use_batch) v -= (chan[7 * c] / count) * (double)sp[2] + (chan[7 * c + 1] / count) * (double)sp[3];
+  dgain[n * gsn + c] += (float)((double)invstd[c] * v);
+}
+extern "C" int sg_cbn_bwd2_dgain(const float* sums, const double* chan, double count, const float* invstd, int N, int C, int gb_stride_n, int use_batch_stats, float* dgain, sg_stream_t s) {
+  SG_CHECK(sums && chan && invstd && dgain && count > 0 && N > 0 && C > 0 && gb_stride_n >= C, "sg_cbn_bwd2_dgain: bad args");
+  hipLaunchKernelGGL(k_cbn_bwd2_dgain, dim3((unsigned)(((long long)N * C + 255) / 256)), dim3(256), 0, (hipStream_t)s, sums, chan, count, invstd, N, C, gb_stride_n, use_batch_stats, dgain);
+  SG_LAUNCH_CHECK();
+  return 0;
+}
+// stage 3: streaming pass over x, dy, u -> g_dy and / or g_x. Grid (pixel chunks, N, tiles of `cvt` channel vectors): a thread owns ONE channel vector (16 bytes
+// with VECP, else one element) of ONE sample and folds the per-channel terms and its sample's rows into 7 coefficients per channel once, in fp64:
+//     g_dy = mask (P u + Q xhat + R)                 P = gam r,  Q = A - s P a,  R = B - s P ub
+//     g_x  = E1 u + E2 g + E3 xhat + E4              E1 = -s r^2 ch,  E2 = r A - s r^2 a gam,  E3 = s r^2 (3 a ch - mh + ub hb) - s r wx,  E4 = s r^2 (ch ub + a hb) - s r wb
+// so that the loop body is 3 loads -> ~10 flops per element -> 2 stores.
+template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_cbn_bwd2_apply(const T* x, const T* dy, const T* u, T* g_dy, T* g_x, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, const float* A, const float* Bc, int gsn, int relu, const double* chan, double count, int use_batch, int ppb, int cvt) {
+  constexpr int V = VECP ? ET<T>::VEC : 1;
+  const int CV = C / V;
+  const int n = blockIdx.y;
+  const int lanes_p = 256 / cvt;
+  const int pl = threadIdx.x / cvt;
+  const int cv = blockIdx.z * cvt + threadIdx.x % cvt;
+  if (pl >= lanes_p || cv >= CV) return;
+  float mu[V], is[V], ga[V], bi[V], P[V], Q[V], R[V], E1[V], E2[V], E3[V], E4[V];
+#pragma unroll
+  for (int e = 0; e < V; e++) {
+    const int c = cv * V + e;
+    mu[e] = mean[c]; is[e] = invstd[c];
+    ga[e] = gain ? gain[(long long)n * gsn + c] : 1.f;
+    bi[e] = bias ? bias[(long long)n * gsn + c] : 0.f;
+    const double r = is[e], gm = ga[e];
+    const double an = A ? (double)A[(long long)n * gsn + c] : 0.0, bn = Bc ? (double)Bc[(long long)n * gsn + c] : 0.0;
+    double p = gm * r, q = an, rr = bn, e1 = 0.0, e2 = r * an, e3 = 0.0, e4 = 0.0;
+    if (use_batch) {
+      const double* ch = chan + 7 * c;
+      const double ub = ch[0] / count, a = ch[1] / count, hb = ch[2] / count, chh = ch[3] / count, mh = ch[4] / count, wb = ch[5] / count, wx = ch[6] / count;
+      q -= p * a; rr -= p * ub;
+      e1 = -r * r * chh; e2 -= r * r * a * gm;
+      e3 = r * r * (3.0 * a * chh - mh + ub * hb) - r * wx;
+      e4 = r * r * (chh * ub + a * hb) - r * wb;
+    }
+    P[e] = (float)p; Q[e] = (float)q; R[e] = (float)rr; E1[e] = (float)e1; E2[e] = (float)e2; E3[e] = (float)e3; E4[e] = (float)e4;
+  }
+  const long long p0 = (long long)blockIdx.x * ppb;
+  long long p1 = p0 + ppb; if (p1 > HW) p1 = HW;
+  const long long base = (long long)n * HW * C + (long long)cv * V;
+#pragma unroll 2
+  for (long long pix = p0 + pl; pix < p1; pix += lanes_p) {
+    const long long o = base + pix * C;
+    float xv[V], gv[V], uv[V], o1[V], o2[V];
+    if (VECP) { unpack16<T>(*(const u32x4*)(x + o), xv); unpack16<T>(*(const u32x4*)(dy + o), gv); unpack16<T>(*(const u32x4*)(u + o), uv); }
+    else { xv[0] = to_f<T>(x[o]); gv[0] = to_f<T>(dy[o]); uv[0] = to_f<T>(u[o]); }
+#pragma unroll
+    for (int e = 0; e < V; e++) {
+      const float xh = (xv[e] - mu[e]) * is[e];
+      const bool on = !(relu && !(xh * ga[e] + bi[e] > 0.f));
+      const float g = on ? gv[e] : 0.f;
+      o1[e] = on ? (P[e] * uv[e] + Q[e] * xh + R[e]) : 0.f;
+      o2[e] = E1[e] * uv[e] + E2[e] * g + E3[e] * xh + E4[e];
+    }
+    if (VECP) { if (g_dy) *(u32x4*)(g_dy + o) = pack16<T>(o1); if (g_x) *(u32x4*)(g_x + o) = pack16<T>(o2); }
+    else { if (g_dy) g_dy[o] = from_f<T>(o1[0]); if (g_x) g_x[o] = from_f<T>(o2[0]); }
+  }
+}
+extern "C" int sg_cbn_bwd2_apply(int dtype, const void* x, const void* dy, const void* u, void* g_dy, void* g_x, int N, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, const float* A, const float* B, int gb_stride_n, int relu, const double* chan, double count, int use_batch_stats, sg_stream_t s) {
+  SG_CHECK(x && dy && u && mean && invstd && chan && count > 0 && (g_dy || g_x) && N > 0 && HW > 0 && C > 0, "sg_cbn_bwd2_apply: bad args");
+  SG_CHECK(N <= 65535, "sg_cbn_bwd2_apply: batch too large for grid.y");
+  SG_CHECK((!gain && !bias && !A && !B) || gb_stride_n >= C, "sg_cbn_bwd2_apply: row pitch below C");
+  DISPATCH_T(dtype, {
+    const bool vec = vec_ok<T>(x, dy, C) && (((((uintptr_t)u) | ((uintptr_t)g_dy) | ((uintptr_t)g_x)) & 15) == 0);
+    const int CV = vec ? C / ET<T>::VEC : C;
+    const int cvt = CV < 256 ? CV : 256;
+    const int gz = (CV + cvt - 1) / cvt;
+    const int lanes_p = 256 / cvt;
+    long long chunks = 2048 / ((long long)N * gz); if (chunks < 1) chunks = 1;
+    long long ppb = (HW + chunks - 1) / chunks; if (ppb < 4 * lanes_p) ppb = 4 * lanes_p;
+    const int gx = (int)((HW + ppb - 1) / ppb);
+    if (vec) hipLaunchKernelGGL((k_cbn_bwd2_apply<T, true>), dim3(gx, N, gz), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (const T*)u, (T*)g_dy, (T*)g_x, HW, C, mean, invstd, gain, bias, A, B, gb_stride_n, relu, chan, count, use_batch_stats, (int)ppb, cvt);
+    else hipLaunchKernelGGL((k_cbn_bwd2_apply<T, false>), dim3(gx, N, gz), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (const T*)u, (T*)g_dy, (T*)g_x, HW, C, mean, invstd, gain, bias, A, B, gb_stride_n, relu, chan, count, use_batch_stats, (int)ppb, cvt);
+  });
+  SG_LAUNCH_CHECK();
+  return 0;
+}

@@ -12,8 +12,9 @@ from ..bank import ensure_grad
 def _first_order_only(name):
     """Functions without a differentiable backward refuse create_graph=True instead of silently cutting the graph."""
     if torch.is_grad_enabled():
-        raise NotImplementedError(name + ": second-order gradients (create_graph=True) are implemented for the discriminator's "
-                                         "conv / BN / pooling / self-attention / head path only (gradient penalties, R1)")
+        raise NotImplementedError(name + ": no differentiable backward (create_graph=True). Second-order passes exist for the discriminator's conv / BN / pooling / "
+                                         "self-attention / head path (gradient penalties, R1) and for the ResNet / BigGAN / BigGAN-Deep generators incl. conditional "
+                                         "batch norm (latent optimisation); not for third order, nor for the DCGAN generator's transposed convolutions")
 
 
 def _param_grad_wanted(*params):

@@ -345,8 +345,9 @@ class SliceUpFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        _first_order_only("SliceUpFn")
         N, Hs, Ws, ld, C, up = ctx.dims
+        if torch.is_grad_enabled():      # create_graph=True (latent optimisation): the gradient as a differentiable operator, handed to autograd itself (no GradLink)
+            return (dy if (C == ld and up == 1) else SliceUpBwdFn.apply(dy, ctx.dims)), None, None, None
         dy = _c(dy)
         if C == ld and up == 1:
             dx = dy
@@ -471,6 +472,28 @@ class ConvTransposeFn(torch.autograd.Function):
         return dx, None, None, None, None, None
 
 
+class SliceUpBwdFn(torch.autograd.Function):
+    """SliceUpFn's gradient dx = zero_pad_channels(sum_2x2?(dy)) as a differentiable operator: linear in dy, its adjoint is SliceUpFn's forward launch."""
+
+    @staticmethod
+    def forward(ctx, dy, dims):
+        N, Hs, Ws, ld, C, up = dims
+        dy = _c(dy)
+        ctx.dims = dims
+        dx = torch.empty((N, Hs, Ws, ld), dtype=dy.dtype, device=dy.device)
+        L.call("sg_slice_up_bwd", L.dt(dy), L.ptr(dy), L.ptr(dx), N, Hs, Ws, ld, C, up, L.stream())
+        return dx
+
+    @staticmethod
+    def backward(ctx, t):
+        _first_order_only("SliceUpBwdFn")
+        N, Hs, Ws, ld, C, up = ctx.dims
+        t = _c(t)
+        g = torch.empty((N, Hs * up, Ws * up, C), dtype=t.dtype, device=t.device)
+        L.call("sg_slice_up_fwd", L.dt(t), L.ptr(t), L.ptr(g), N, Hs, Ws, ld, C, up, L.stream())
+        return g, None
+
+
 class LinearFn(torch.autograd.Function):
     """y = x W_sn^T + b in fp32 (nn.Linear, reference src/utils/ops.py:187-188,219-220). const_bias: non-trainable bias
     vector (the '1 +' of ConditionalBatchNorm2d's gain, reference src/utils/ops.py:25)."""
@@ -573,11 +596,16 @@ class CbnAffineFn(torch.autograd.Function):
             gemm_raw(L.F32, pb, 0, K, y, 0, K, out.data_ptr() + 4 * C, 2 * C, C, B, K)
         ctx.save_for_backward(y)
         ctx.rt_g, ctx.rt_b, ctx.slot = rt_g, rt_b, slot
+        ctx.wg, ctx.wb = wg, wb      # the master parameters: only handed on to CbnAffineDgradFn so the second-order graph reaches them
         return out
 
     @staticmethod
     def backward(ctx, dgb):
-        _first_order_only("CbnAffineFn")
+        if torch.is_grad_enabled():      # create_graph=True: the data gradient as a differentiable operator; parameter gradients of this first pass are not wanted
+            if _param_grad_wanted(ctx.wg, ctx.wb):
+                raise NotImplementedError("create_graph=True is supported for input gradients only (latent optimisation)")
+            dy = CbnAffineDgradFn.apply(dgb, ctx.wg, ctx.wb, ctx.rt_g, ctx.rt_b, ctx.slot, ctx.adjacent) if ctx.needs_input_grad[0] else None
+            return dy, None, None, None, None, None, None
         (y,) = ctx.saved_tensors
         dy = _cbn_affine_backward(y, dgb, ctx.rt_g, ctx.rt_b, ctx.slot, ctx.adjacent, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2])
         return dy, None, None, None, None, None, None
@@ -603,14 +631,69 @@ def _cbn_affine_backward(y, dgb, rt_g, rt_b, slot, fwd_adjacent, need_y, need_g,
         else:
             gemm_raw(L.F32, pg, 1, K, dgb, 0, 2 * C, dy, K, K, B, C)
             gemm_raw(L.F32, pb, 1, K, dgb.data_ptr() + 4 * C, 0, 2 * C, dy, K, K, B, C, res=dy, ldr=K)
-    if both and adjacent:      # dW[o][k] = sum_b dgb[b][o] y[b][k], o over the 2 C rows
-        gemm_raw(L.F32, y, 1, K, dgb, 1, 2 * C, dg, K, K, 2 * C, B)
+    # (accumulated into the slot's zero-initialised scratch, as LinearFn's: in a pass that follows a create_graph pass through the same forward -- latent
+    # optimisation -- CbnAffineDgradFn.backward has already put its share there)
+    if both and adjacent:      # dW[o][k] += sum_b dgb[b][o] y[b][k], o over the 2 C rows
+        gemm_raw(L.F32, y, 1, K, dgb, 1, 2 * C, dg, K, K, 2 * C, B, res=dg, ldr=K)
     else:
         if dg is not None:
-            gemm_raw(L.F32, y, 1, K, dgb, 1, 2 * C, dg, K, K, C, B)
+            gemm_raw(L.F32, y, 1, K, dgb, 1, 2 * C, dg, K, K, C, B, res=dg, ldr=K)
         if db is not None:
-            gemm_raw(L.F32, y, 1, K, dgb.data_ptr() + 4 * C, 1, 2 * C, db, K, K, C, B)
+            gemm_raw(L.F32, y, 1, K, dgb.data_ptr() + 4 * C, 1, 2 * C, db, K, K, C, B, res=db, ldr=K)
     return dy
+
+
+class CbnAffineDgradFn(torch.autograd.Function):
+    """dy = dgb [W_gain ; W_bias]: the data gradient of a conditional batch norm's [1 + gain(y) | bias(y)] product as a differentiable operator (second-order pass
+    through a class-conditional generator: latent optimisation, reference src/utils/losses.py:278-298), on the pattern of LinearDgradFn. Linear in dgb and in the
+    two (spectrally normalised) weights: d/d(dgb) = t W^T (the forward GEMM without its constant), d/dW += dgb^T t into the bank's scratch, from where the
+    normalisation's backward carries it to the master weights."""
+
+    @staticmethod
+    def forward(ctx, dgb, wg, wb, rt_g, rt_b, slot, adjacent):
+        bank = rt_g.bank()
+        dgb = _c(dgb.float())
+        B, C, K = dgb.shape[0], rt_g.rows, rt_g.cols
+        assert dgb.shape[1] == 2 * C
+        pg, pb = bank.w_f32(slot, rt_g), bank.w_f32(slot, rt_b)
+        dy = torch.empty((B, K), dtype=torch.float32, device=dgb.device)
+        if adjacent:      # dy[b][k] = sum over the 2 C rows of dgb[b][o] W[o][k]
+            gemm_dgrad_rows(pg, dgb, dy, B, K, 2 * C)
+        else:
+            gemm_raw(L.F32, pg, 1, K, dgb, 0, 2 * C, dy, K, K, B, C)
+            gemm_raw(L.F32, pb, 1, K, dgb.data_ptr() + 4 * C, 0, 2 * C, dy, K, K, B, C, res=dy, ldr=K)
+        ctx.save_for_backward(dgb)
+        ctx.rt_g, ctx.rt_b, ctx.slot, ctx.adjacent = rt_g, rt_b, slot, adjacent
+        return dy
+
+    @staticmethod
+    def backward(ctx, t):
+        _first_order_only("CbnAffineDgradFn")
+        (dgb,) = ctx.saved_tensors
+        rt_g, rt_b, slot = ctx.rt_g, ctx.rt_b, ctx.slot
+        bank = rt_g.bank()
+        t = _c(t.float())
+        B, K = t.shape
+        C = rt_g.rows
+        pg, pb = bank.w_f32(slot, rt_g), bank.w_f32(slot, rt_b)
+        g_dgb = None
+        if ctx.needs_input_grad[0]:
+            g_dgb = torch.empty((B, 2 * C), dtype=torch.float32, device=t.device)
+            if ctx.adjacent:
+                gemm_raw(L.F32, pg, 0, K, t, 0, K, g_dgb, 2 * C, 2 * C, B, K)
+            else:
+                gemm_raw(L.F32, pg, 0, K, t, 0, K, g_dgb, 2 * C, C, B, K)
+                gemm_raw(L.F32, pb, 0, K, t, 0, K, g_dgb.data_ptr() + 4 * C, 2 * C, C, B, K)
+        dg = bank.dwt(slot, rt_g) if ctx.needs_input_grad[1] else None
+        db = bank.dwt(slot, rt_b) if ctx.needs_input_grad[2] else None
+        if dg is not None and db is not None and ctx.adjacent and db == dg + 4 * C * K:      # dW[o][k] += sum_b dgb[b][o] t[b][k], o over the 2 C rows
+            gemm_raw(L.F32, t, 1, K, dgb, 1, 2 * C, dg, K, K, 2 * C, B, res=dg, ldr=K)
+        else:
+            if dg is not None:
+                gemm_raw(L.F32, t, 1, K, dgb, 1, 2 * C, dg, K, K, C, B, res=dg, ldr=K)
+            if db is not None:
+                gemm_raw(L.F32, t, 1, K, dgb.data_ptr() + 4 * C, 1, 2 * C, db, K, K, C, B, res=db, ldr=K)
+        return g_dgb, None, None, None, None, None, None
 
 
 class CbnAffineGroupFn(torch.autograd.Function):
@@ -659,15 +742,25 @@ class CbnAffineGroupFn(torch.autograd.Function):
         L.call("sg_linear_group", tab.data_ptr(), arr, k, B, L.stream())
         ctx.save_for_backward(*ys)
         ctx.metas, ctx.yidx, ctx.slot, ctx.adj, ctx.G = metas, yidx, slot, adj, G
+        ctx.ws = tensors[G:]      # the master parameters: only handed on to CbnAffineDgradFn so the second-order graph reaches them
         ctx._keep = out_all
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *dgbs):
-        _first_order_only("CbnAffineGroupFn")
-        ys = ctx.saved_tensors
         G, n = ctx.G, len(ctx.metas)
         dys = [None] * G
+        if torch.is_grad_enabled():      # create_graph=True: layer by layer through the single layer's differentiable operator
+            if _param_grad_wanted(*ctx.ws):
+                raise NotImplementedError("create_graph=True is supported for input gradients only (latent optimisation)")
+            for i, ((rt_g, rt_b, _), dgb) in enumerate(zip(ctx.metas, dgbs)):
+                g = ctx.yidx[i]
+                if dgb is None or not ctx.needs_input_grad[3 + g]:
+                    continue
+                dy = CbnAffineDgradFn.apply(dgb, ctx.ws[2 * i], ctx.ws[2 * i + 1], rt_g, rt_b, ctx.slot, ctx.adj[i])
+                dys[g] = dy if dys[g] is None else dys[g] + dy
+            return (None, None, None) + tuple(dys) + (None,) * (2 * n)
+        ys = ctx.saved_tensors
         for i, ((rt_g, rt_b, _), dgb) in enumerate(zip(ctx.metas, dgbs)):
             if dgb is None:
                 continue
@@ -767,4 +860,4 @@ class SNEmbeddingFn(torch.autograd.Function):
         return None, None, None, None
 
 
-__all__ = ['CatConvDgradFn', 'CatConvFn', 'CbnAffineFn', 'CbnAffineGroupFn', 'cbn_prefetch', '_CBN_GROUP', 'ConvCfg', 'ConvDgradFn', 'ConvFn', 'ConvSkipFn', 'ConvTransposeFn', 'EmbeddingFn', 'GradLink', 'LinearDgradFn', 'LinearFn', 'SNEmbeddingFn', 'SliceUpFn', '_GRAD_LINK', '_QUAD', '_SKIP_FUSION', '_conv_dgrad', '_conv_fwd', '_conv_wgrad', '_quad_form']
+__all__ = ['CatConvDgradFn', 'CatConvFn', 'CbnAffineDgradFn', 'CbnAffineFn', 'CbnAffineGroupFn', 'cbn_prefetch', '_CBN_GROUP', 'ConvCfg', 'ConvDgradFn', 'ConvFn', 'ConvSkipFn', 'ConvTransposeFn', 'EmbeddingFn', 'GradLink', 'LinearDgradFn', 'LinearFn', 'SNEmbeddingFn', 'SliceUpBwdFn', 'SliceUpFn', '_GRAD_LINK', '_QUAD', '_SKIP_FUSION', '_conv_dgrad', '_conv_fwd', '_conv_wgrad', '_quad_form']

@@ -117,8 +117,26 @@ class BNFn(torch.autograd.Function):
         x, gain, bias, mean, invstd = ctx.saved_tensors
         cfg, gsn = ctx.cfg, ctx.gsn
         if torch.is_grad_enabled():
-            if gsn or _param_grad_wanted(gain, bias):
-                raise NotImplementedError("create_graph=True is supported for the input gradient of per-channel BN only (WGAN-GP path)")
+            if gsn:
+                # per-sample rows (conditional batch norm): dx AND the row gradients as one differentiable operator (latent optimisation through a
+                # class-conditional generator). No GradLink is armed in a create_graph pass (ConvSkipFn / SliceUpFn return their gradients themselves).
+                if cfg.packed:
+                    rows = gain
+                else:      # separate per-sample gain / bias tensors: packed here, so that the operator below has ONE layout
+                    Cc = x.shape[3]
+                    z = torch.zeros((x.shape[0], Cc), dtype=torch.float32, device=x.device)
+                    rows = torch.cat([gain if gain is not None else z + 1.0, bias if bias is not None else z], dim=1)
+                dx, drows = CBNBwdFn.apply(dy, x, rows, mean, invstd, cfg, ctx.count)
+                if not ctx.needs_input_grad[0]:
+                    dx = None
+                if cfg.packed:
+                    return (dx, drows if ctx.needs_input_grad[1] else None, None, None, None, None) + (None,) * ctx.nopt
+                Cc = x.shape[3]
+                return (dx, drows[:, :Cc] if (gain is not None and ctx.needs_input_grad[1]) else None,
+                        drows[:, Cc:] if (bias is not None and ctx.needs_input_grad[2]) else None, None, None, None) + (None,) * ctx.nopt
+            if _param_grad_wanted(gain, bias):
+                raise NotImplementedError("create_graph=True through a per-channel affine BN is supported for its input gradient only (WGAN-GP path); "
+                                          "per-sample rows (conditional batch norm) have the full second-order pass")
             dx = BNBwdFn.apply(dy, x, gain, bias, mean, invstd, cfg, ctx.count) if ctx.needs_input_grad[0] else None
             return (dx, None, None, None, None, None) + (None,) * ctx.nopt
         dy = _c(dy)
@@ -201,4 +219,67 @@ class BNBwdFn(torch.autograd.Function):
         return g_dy, g_x, dgain, None, None, None, None, None
 
 
-__all__ = ['BNBwdFn', 'BNCfg', 'BNFn', '_allreduce_sum', '_world']
+class CBNBwdFn(torch.autograd.Function):
+    """The backward of a batch norm with PER-SAMPLE affine rows (conditional batch norm; rows = packed [N][gain(C) | bias(C)]) as a differentiable operator:
+    (dy, x, rows) -> (dx, drows), statistics being functions of x. Its own backward takes the cotangents of dx and of the row gradients and returns the gradients
+    w.r.t. dy, x and the gain rows (the bias rows enter through the ReLU mask only): LOGAN's latent optimisation through a class-conditional generator (reference
+    src/utils/losses.py:278-298). Formulas and kernels: csrc/norm.hip "second-order backward with per-sample affine rows"."""
+
+    @staticmethod
+    def forward(ctx, dy, x, rows, mean, invstd, cfg, count):
+        if _world(cfg.group) > 1:
+            raise NotImplementedError("CBNBwdFn: create_graph=True through a SYNCHRONISED conditional batch norm (world size > 1) is not implemented -- the per-channel "
+                                      "pass's all-reduce of the fp64 channel terms would carry over, but no multi-rank LOGAN run exists to check it against")
+        dy, rows = _c(dy), _c(rows.float())
+        N, H, W, Cc = x.shape
+        HW = H * W
+        dev = x.device
+        assert rows.shape == (N, 2 * Cc)
+        relu = 1 if cfg.relu else 0
+        gptr, bptr = L.ptr(rows), L.ptr(rows) + 4 * Cc
+        sums = zeros_small((N, Cc, 2), torch.float32, dev)
+        L.call("sg_bn_bwd_reduce", L.dt(x), L.ptr(x), L.ptr(dy), N, HW, Cc, L.ptr(mean), L.ptr(invstd), gptr, bptr, 2 * Cc, relu, L.ptr(sums), L.stream())
+        chan = torch.empty(2 * Cc, dtype=torch.float64, device=dev)
+        drows = torch.zeros_like(rows)          # (an output of this operator: a tensor of its own, not a piece of the shared zero block)
+        L.call("sg_bn_bwd_finalize", L.ptr(sums), N, Cc, gptr, 2 * Cc, L.ptr(drows), L.ptr(drows) + 4 * Cc, L.ptr(chan), L.stream())
+        dx = torch.empty_like(x)
+        L.call("sg_bn_bwd_apply", L.dt(x), L.ptr(x), L.ptr(dy), L.ptr(dx), N, HW, Cc, L.ptr(mean), L.ptr(invstd), gptr, bptr, 2 * Cc, relu, L.ptr(chan), count,
+               1 if cfg.batch_stats else 0, L.stream())
+        ctx.save_for_backward(dy, x, rows, mean, invstd)
+        ctx.cfg, ctx.count = cfg, count
+        ctx.set_materialize_grads(False)
+        return dx, drows
+
+    @staticmethod
+    def backward(ctx, u, ab):
+        _first_order_only("CBNBwdFn")        # (third order: not a path of the reference)
+        dy, x, rows, mean, invstd = ctx.saved_tensors
+        cfg = ctx.cfg
+        N, H, W, Cc = x.shape
+        HW = H * W
+        dev = x.device
+        if u is None and ab is None:
+            return (None,) * 7
+        u = _c(u) if u is not None else torch.zeros_like(x)
+        ab = _c(ab.float()) if ab is not None else None
+        relu, use_batch = 1 if cfg.relu else 0, 1 if cfg.batch_stats else 0
+        gptr, bptr = L.ptr(rows), L.ptr(rows) + 4 * Cc
+        aptr = L.ptr(ab) if ab is not None else None
+        bcot = (L.ptr(ab) + 4 * Cc) if ab is not None else None
+        sums = zeros_small((N, Cc, 5), torch.float32, dev)
+        L.call("sg_cbn_bwd2_reduce", L.dt(x), L.ptr(x), L.ptr(dy), L.ptr(u), N, HW, Cc, L.ptr(mean), L.ptr(invstd), gptr, bptr, 2 * Cc, relu, L.ptr(sums), L.stream())
+        chan = torch.empty(7 * Cc, dtype=torch.float64, device=dev)
+        L.call("sg_cbn_bwd2_finalize", L.ptr(sums), N, Cc, gptr, aptr, 2 * Cc, L.ptr(chan), L.stream())
+        g_dy = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        g_x = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        if g_dy is not None or g_x is not None:
+            L.call("sg_cbn_bwd2_apply", L.dt(x), L.ptr(x), L.ptr(dy), L.ptr(u), L.ptr(g_dy), L.ptr(g_x), N, HW, Cc, L.ptr(mean), L.ptr(invstd), gptr, bptr, aptr, bcot,
+                   2 * Cc, relu, L.ptr(chan), ctx.count, use_batch, L.stream())
+        g_rows = None
+        if ctx.needs_input_grad[2]:
+            g_rows = zeros_like_small(rows)          # (the bias half stays zero)
+            L.call("sg_cbn_bwd2_dgain", L.ptr(sums), L.ptr(chan), ctx.count, L.ptr(invstd), N, Cc, 2 * Cc, use_batch, L.ptr(g_rows), L.stream())
+        return g_dy, g_x, g_rows, None, None, None, None
+
+
+__all__ = ['BNBwdFn', 'BNCfg', 'BNFn', 'CBNBwdFn', '_allreduce_sum', '_world']

@@ -55,7 +55,7 @@ def latent_optimise(zs, fake_labels, generator, discriminator, batch_size, lo_ra
     """Latent optimisation of LOGAN, reference src/utils/losses.py:278-298 (called from src/utils/sample.py:123-135 when LOSS.apply_lo): one natural-gradient-like
     step of z along d D(G(z)) / dz, taken WITH a graph (cal_deriv: create_graph=True) so that the transport cost and the images of the moved latents back-propagate
     through it -- the create_graph pass runs through the generator's and the discriminator's differentiable data-gradient operators (functional.LinearDgradFn,
-    ConvDgradFn, BNBwdFn, TanhGradFn, ...). The arithmetic on the [B, z_dim] latents is torch's, as in the reference. Like the reference, the function returns from
+    ConvDgradFn, BNBwdFn, CBNBwdFn for conditional batch norm, TanhGradFn, ...). The arithmetic on the [B, z_dim] latents is torch's, as in the reference. Like the reference, the function returns from
     inside its loop: one step is taken whatever lo_steps says (>= 2)."""
     for step in range(lo_steps - 1):
         drop_mask = (torch.FloatTensor(batch_size, 1).uniform_() > 1 - lo_rate).to(device)
@@ -76,7 +76,7 @@ def langevin_sampling(zs, z_dim, fake_labels, generator, discriminator, batch_si
     """Langevin dynamics on the latents at evaluation time, reference src/utils/sample.py:195-216 (RUN.langevin_sampling): `langevin_steps` steps down the energy
     -log N(z; 0, I) - D(G(z)) with Gaussian noise of covariance langevin_noise_std * I, the rate (and the noise scale) decayed every `langevin_decay_steps` steps. The
     gradient runs through the generator and the discriminator in eval mode (the reference takes it with cal_deriv, i.e. with a graph nothing ever differentiates: here
-    it is a plain first-order gradient, so conditional generators -- whose batch norm has no second-order pass -- work too); the prior and the noise come from the same
+    it is a plain first-order gradient: no second-order operator runs); the prior and the noise come from the same
     torch.distributions objects as in the reference, so a seeded run consumes the generator identically."""
     from torch.distributions import multivariate_normal as MN
     scaler = 1.0
