@@ -111,6 +111,33 @@ int sg_conv2d_fwd_skip_ok(const sg_conv_skip_desc* d);
  * bf16 images -- the RGB layers of the 128 x 128 configurations). Introspection for tests and benchmarks: which engine took a shape. */
 long long sg_conv_rs_launches(void);
 
+/* ---- StyleGAN2 modulated convolution (csrc/modconv.hip; reference src/models/stylegan2.py:28-98) ------------------------------------------
+ * out[n,p,o] = post[n,o] * alpha * conv(w, pre[n,c] * x)[n,p,o] + noise[n,p] + bias[o]   in ONE launch with ONE weight image shared by all samples
+ * (the reference's fused route materialises [N,Cout,Cin,k,k] weights for a grouped convolution). pre: fp32 [N][C]; post: fp32 [N][Cout]; noise: fp32,
+ * sample n's [Ho][Wo] plane at noise + n * noise_stride (0 = one plane for all samples); each of the three may be NULL. fp32 (exact fp32 MFMA, whatever
+ * the f32 mode) and bf16 (pre * x rounded to bf16 once for the MFMA; post, noise, bias on the fp32 accumulator, one rounding on store).
+ * Geometry (R == S): 1x1 or 3x3 at stride 1 / pad k/2; 3x3 stride 2 with SG_PIX_TRANSPOSED (Ho = 2 (Hs - 1) + 3 - 2 pad: the up = 2 layer); the plain 3x3
+ * stride-2 convolution (its data gradient). Any C, Cout, map size. No mask / residual / epilogue flags. */
+typedef struct {
+  sg_conv_fwd_desc conv;
+  const float* pre; const float* post; const float* noise;
+  long long noise_stride;
+} sg_modconv_desc;
+int sg_modconv2d_fwd(const sg_modconv_desc* d, sg_stream_t stream);
+int sg_modconv2d_ok(const sg_modconv_desc* d);             /* 1 when the kernel takes the problem, else 0 */
+long long sg_modconv_launches(void);                       /* launches so far (tests: which kernel ran) */
+/* Q[o][c] = sum_{r,s} w[o][c][r][s]^2 from the fp32 [Cout][C][RS] weight; with styles s (fp32 [N][C]) also the demodulation coefficients
+ * d[n][o] = (sum_c s[n][c]^2 Q[o][c] + 1e-8)^(-1/2). s and d both NULL: Q only. Always fp32, as the reference computes them. */
+int sg_modconv_dcoef(const float* w, const float* s, float* Q, float* d, int N, int C, int Cout, int RS, sg_stream_t stream);
+/* The operator's backward reductions, one pass over a pair of [N][P][C] tensors (pixel pitches lda / ldb), deterministic (no float atomics):
+ *   out[n,p,c] = scale[n,c] * a[n,p,c] (dtype of a, dense);  part[n,k,c] = sum over the pixels p of slab k of a * (b - rowsub[n,p]) (fp32);
+ *   rowsum[n,p] = sum_c a[n,p,c] (fp32). scale / out and b / part are optional pairs, rowsub (stride as noise_stride) and rowsum optional.
+ * part is [N][slabs of P][C]: the caller adds the slabs. (gy, y, noise, d) gives d * gy, d * (gradient of d) and the noise gradient;
+ * (gxs, x, -, styles) gives dx and the direct part of the style gradient. C <= 4096. */
+int sg_modconv_reduce_slabs(int P);
+int sg_modconv_reduce(int dtype, const void* a, const void* b, const float* rowsub, long long rowsub_stride, const float* scale, void* out, float* part,
+                      float* rowsum, int N, int P, int C, int lda, int ldb, sg_stream_t stream);
+
 /* ---- "quad" convolutions: a 3x3 / pad-1 convolution next to a 2x resampling, through the exact filter identity (csrc/conv_q.h) -------
  * SG_Q_POOL: out[N,Hl,Wl,Cout] = epilogue( alpha * avgpool2(conv3x3(relu?(x); w)) + bias ),  x: [N,2Hl,2Wl,C]
  *            = conv4x4 / stride 2 / pad 1 with the pooled filter: replaces `conv2d2` + `average_pooling` of the reference's discriminator

@@ -35,6 +35,10 @@ class ConvSkipDesc(C.Structure):
     _fields_ = [("main", ConvFwdDesc), ("x2", _vp), ("w2", _vp), ("bias2", _vp), ("C2", _i), ("ldx2", _i), ("x2_up", _i), ("stats", _vp)]
 
 
+class ModConvDesc(C.Structure):
+    _fields_ = [("conv", ConvFwdDesc), ("pre", _vp), ("post", _vp), ("noise", _vp), ("noise_stride", _ll)]
+
+
 class ConvWgradDesc(C.Structure):
     _fields_ = [("dtype", _i), ("N", _i), ("xHs", _i), ("xWs", _i), ("C", _i), ("ldx", _i), ("x_flags", _i), ("gHs", _i), ("gWs", _i),
                 ("Cout", _i), ("ldg", _i), ("g_flags", _i), ("Ho", _i), ("Wo", _i), ("R", _i), ("S", _i), ("stride", _i),
@@ -110,6 +114,12 @@ _PROTOS = {
     "sg_conv2d_fwd_skip": [C.POINTER(ConvSkipDesc), _vp],
     "sg_conv2d_fwd_skip_ok": [C.POINTER(ConvSkipDesc)],
     "sg_conv_rs_launches": [],
+    "sg_modconv2d_fwd": [C.POINTER(ModConvDesc), _vp],
+    "sg_modconv2d_ok": [C.POINTER(ModConvDesc)],
+    "sg_modconv_launches": [],                             # returns a count
+    "sg_modconv_dcoef": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "sg_modconv_reduce_slabs": [_i],                       # returns a count (call through lib(), not call())
+    "sg_modconv_reduce": [_i, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "sg_conv2d_q": [C.POINTER(ConvQDesc), _vp],
     "sg_conv2d_q_ok": [C.POINTER(ConvQDesc)],
     "sg_conv2d_q_stat_rows": [C.POINTER(ConvQDesc)],
@@ -296,6 +306,7 @@ def lib():
             fn.argtypes = args
             fn.restype = _i
         l.sg_conv_rs_launches.restype = _ll
+        l.sg_modconv_launches.restype = _ll
         l.sg_tok_gemm_launches.restype = _ll
         l.sg_mha_launches.restype = _ll
         l.sg_f32_split_launches.restype = _ll

@@ -20,13 +20,6 @@ extern "C" long long sg_f32_split_launches(int mode) {
   return __atomic_load_n(&g_sg_f32_split_launches[mode == 6], __ATOMIC_RELAXED);
 }
 
-template <typename T, class LP, class LQ, int SPLIT>
-static void conv_fwd_tiles(const LP& lp, const LQ& lq, const Epilogue<T>& e, int I, int J, int K, hipStream_t st) {
-  if (I <= 32) sg_launch_gemm<T, LP, LQ, 32, 256, 1, 4, true, SPLIT>(lp, lq, e, I, J, K, 1, 1, st);
-  else if (I % 128 != 0 && (I % 96 == 0 || (I < 128 && I > 64))) sg_launch_gemm<T, LP, LQ, 96, 256, 1, 4, true, SPLIT>(lp, lq, e, I, J, K, 1, 1, st);
-  else sg_launch_gemm<T, LP, LQ, 128, 128, 2, 2, true, SPLIT>(lp, lq, e, I, J, K, 1, 1, st);
-}
-
 template <typename T, bool FAST>
 static void conv_fwd_launch(const sg_conv_fwd_desc* d, const Epilogue<T>& e, int I, int J, int K, int pflags, hipStream_t st) {
   typedef StridedKC<T, FAST> LP;

@@ -52,6 +52,14 @@ static inline int cout_tile_search(int I, int tj, int& best_tiles) {
   return best;
 }
 
+// tile table of the generic engine's forward / data-gradient launches (conv.hip, modconv.hip): I = couts, J = output pixels
+template <typename T, class LP, class LQ, int SPLIT, class EPI = Epilogue<T>>
+static void conv_fwd_tiles(const LP& lp, const LQ& lq, const EPI& e, int I, int J, int K, hipStream_t st) {
+  if (I <= 32) sg_launch_gemm<T, LP, LQ, 32, 256, 1, 4, true, SPLIT, EPI>(lp, lq, e, I, J, K, 1, 1, st);
+  else if (I % 128 != 0 && (I % 96 == 0 || (I < 128 && I > 64))) sg_launch_gemm<T, LP, LQ, 96, 256, 1, 4, true, SPLIT, EPI>(lp, lq, e, I, J, K, 1, 1, st);
+  else sg_launch_gemm<T, LP, LQ, 128, 128, 2, 2, true, SPLIT, EPI>(lp, lq, e, I, J, K, 1, 1, st);
+}
+
 // D: sg_conv_fwd_desc or sg_convq_desc
 template <typename T, typename D> static Epilogue<T> make_epilogue(const D* d, int I, int J) {
   Epilogue<T> e;

@@ -491,8 +491,9 @@ __device__ __forceinline__ int sg_xcd_tile(int bid, int nt) {
 // product with random sign -- 60x finer than the TF32 convolutions (10-bit mantissa) torch runs the reference's "fp32" evaluation with on its usual hardware.
 // 6 = "bf16x6": three bf16 terms per element (exact: x == h + m + l) and SIX MFMAs per k-tile, smallest products first: h*l, l*h, m*m, m*h, h*m, h*h = 192 cycles.
 // Dropped: m*l, l*m, l*l, at most 2^-25 of the product -- below the fp32 rounding of the product itself; what remains is the fp32 accumulation, as in mode 0.
-template <typename T, class LP, class LQ, int BI, int BJ, int WI, int WJ, bool TR, int SPLIT = 0>
-__global__ __launch_bounds__(256) void sg_gemm_kernel(LP lp, LQ lq, Epilogue<T> epi, int I, int J, int K,
+// EPI: Epilogue<T>, or a type derived from it whose store() does more per (row j, columns i0..i0+3) before Epilogue<T>::store (modconv.hip)
+template <typename T, class LP, class LQ, int BI, int BJ, int WI, int WJ, bool TR, int SPLIT = 0, class EPI = Epilogue<T>>
+__global__ __launch_bounds__(256) void sg_gemm_kernel(LP lp, LQ lq, EPI epi, int I, int J, int K,
                                                        int klen, int tilesI, int tilesJ) {
   constexpr int VEC = ET<T>::VEC, BK = ET<T>::BK, ES = sizeof(T);
   constexpr int P_PITCH = LP::KC ? SG_KC_STRIDE : sg_mc_stride(BI, ES);
@@ -671,8 +672,8 @@ __global__ __launch_bounds__(256) void sg_gemm_kernel(LP lp, LQ lq, Epilogue<T> 
 // host-side launch helper -------------------------------------------------------------------------
 struct SgTileCfg { int BI, BJ; };
 
-template <typename T, class LP, class LQ, int BI, int BJ, int WI, int WJ, bool TR = true, int SPLIT = 0>
-static inline void sg_launch_gemm(const LP& lp, const LQ& lq, const Epilogue<T>& epi, int I, int J, int K,
+template <typename T, class LP, class LQ, int BI, int BJ, int WI, int WJ, bool TR = true, int SPLIT = 0, class EPI = Epilogue<T>>
+static inline void sg_launch_gemm(const LP& lp, const LQ& lq, const EPI& epi, int I, int J, int K,
                                   int splits, int batch, hipStream_t stream) {
   constexpr int BK = ET<T>::BK;
   const int tilesI = (I + BI - 1) / BI, tilesJ = (J + BJ - 1) / BJ;
@@ -683,6 +684,6 @@ static inline void sg_launch_gemm(const LP& lp, const LQ& lq, const Epilogue<T>&
     splits = (K + klen - 1) / klen;
   } else splits = 1;
   dim3 grid(tilesI * tilesJ, splits, batch);
-  hipLaunchKernelGGL((sg_gemm_kernel<T, LP, LQ, BI, BJ, WI, WJ, TR, SPLIT>), grid, dim3(256), 0, stream, lp, lq, epi, I, J, K, klen,
+  hipLaunchKernelGGL((sg_gemm_kernel<T, LP, LQ, BI, BJ, WI, WJ, TR, SPLIT, EPI>), grid, dim3(256), 0, stream, lp, lq, epi, I, J, K, klen,
                      tilesI, tilesJ);
 }

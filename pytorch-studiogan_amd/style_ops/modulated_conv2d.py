@@ -1,0 +1,199 @@
+"""modulated_conv2d: StyleGAN2's modulated, demodulated convolution (reference src/models/stylegan2.py:28-98) with its first-order gradients.
+
+The reference builds per-sample weights [N, Cout, Cin, k, k] and runs a grouped convolution with groups = N (or, with fused_modconv=False, three passes
+over the activation). Both compute
+
+    y[n,o,p] = d[n,o] * sum_{r,s,c} W[o,c,r,s] * ( s[n,c] * x[n,c,tap(p,r,s)] ) + noise[n,p],     d[n,o] = ( sum_c s[n,c]^2 Q[o,c] + 1e-8 )^(-1/2),
+    Q[o,c] = sum_{r,s} W[o,c,r,s]^2
+
+which is a convolution with ONE weight image and two per-sample scale tables: csrc/modconv.hip runs it in one launch (sg_modconv2d_fwd), the styles on the
+activation operand as it is loaded, d and the noise on the fp32 accumulator. No per-sample weight exists at any point.
+
+Gradients (gy = dL/dy; u = the convolution before demodulation, so y = d u + noise):
+    gu = d gy;   gxs = conv^T(W, gu);   dx = s gxs
+    ds = sum_p x gxs  -  s * ( (gd d^3) @ Q ),            gd[n,o] = sum_p gy u
+    dW = wgrad(s x, gu)  -  W * ( (gd d^3)^T @ s^2 )[:, :, None, None]
+    dnoise = sum_o gy  (summed over n as well when the noise is one shared plane)
+The backward keeps y, not u: sum_p gy (y - noise) = d gd, so gd d^3 = d^2 sum_p gy (y - noise) and nothing is ever divided by a style or a coefficient
+(styles may be exactly zero). The data gradient runs through the same kernel (pre-scale d on gy), the weight gradient through sg_conv2d_wgrad on the
+materialised s x and gu; the two demodulation terms are [N x Cout]^T [N x C]-sized products in plain torch."""
+import torch
+
+from .. import _lib as L
+from ..functional._base import _first_order_only, conv2d_wgrad_raw
+from . import upfirdn2d as _upfirdn2d
+
+
+def _validate(x, weight, styles, noise, up, down, padding, resample_filter):
+    """every refusal of the operator, before any device work; -> (N, C, H, W, Cout, k)"""
+    if not (isinstance(x, torch.Tensor) and x.dim() == 4):
+        raise AssertionError("modulated_conv2d: x must be a 4-D NCHW tensor")
+    if not (isinstance(weight, torch.Tensor) and weight.dim() == 4):
+        raise AssertionError("modulated_conv2d: weight must be [out_channels, in_channels, kh, kw]")
+    N, C, H, W = x.shape
+    Cout, Cw, kh, kw = weight.shape
+    if Cw != C or not (isinstance(styles, torch.Tensor) and tuple(styles.shape) == (N, C)):
+        raise AssertionError("modulated_conv2d: weight [O, I, kh, kw], x [N, I, H, W] and styles [N, I] do not agree")
+    if x.dtype not in (torch.float32, torch.bfloat16):      # float16 included: the reference's pre-normalisation for it is not carried over
+        raise NotImplementedError(f"modulated_conv2d: x of dtype {x.dtype} is not supported (float32 / bfloat16)")
+    if down != 1:
+        raise NotImplementedError(f"modulated_conv2d: down={down} is not supported (down=1 only)")
+    if up not in (1, 2):
+        raise NotImplementedError(f"modulated_conv2d: up={up} is not supported (up=1 or up=2)")
+    if kh != kw or kh not in (1, 3):
+        raise NotImplementedError(f"modulated_conv2d: weight with a {kh} x {kw} kernel is not supported (square 1 x 1 or 3 x 3)")
+    if up == 2 and kh == 1:
+        raise NotImplementedError("modulated_conv2d: up=2 with a 1 x 1 weight is not supported")
+    if padding != kh // 2:
+        raise NotImplementedError(f"modulated_conv2d: padding={padding} is not supported (padding = kernel_size // 2 = {kh // 2})")
+    if resample_filter is not None and not (isinstance(resample_filter, torch.Tensor) and resample_filter.dim() in (1, 2) and resample_filter.dtype == torch.float32):
+        raise AssertionError("modulated_conv2d: resample_filter must be None (no low-pass) or a float32 vector / matrix from upfirdn2d.setup_filter")
+    if noise is not None:
+        Ho, Wo = H * up, W * up
+        if not (isinstance(noise, torch.Tensor) and (tuple(noise.shape) == (N, 1, Ho, Wo) or tuple(noise.shape) == (Ho, Wo))):
+            raise NotImplementedError(f"modulated_conv2d: noise of shape {tuple(noise.shape) if isinstance(noise, torch.Tensor) else noise!r} is not supported "
+                                      f"([N, 1, {Ho}, {Wo}] per sample or one shared [{Ho}, {Wo}] plane)")
+    return N, C, H, W, Cout, kh
+
+
+def _modconv_raw(x, wimg, Cout, k, mode, pre=None, post=None, noise=None, noise_stride=0):
+    """one sg_modconv2d_fwd launch. x: dense [N,Hs,Ws,C] NHWC; wimg: [Cout][k*k*C] of x.dtype. mode 'same' (stride 1, pad k//2), 'up2' (transposed stride-2
+    gather, [N,2Hs+1,2Ws+1,Cout]) or 'down2' (plain stride 2, pad 0). Returns the NHWC result."""
+    N, Hs, Ws, C = x.shape
+    d = L.ModConvDesc()
+    c = d.conv
+    c.dtype = L.dt(x)
+    c.N, c.Hs, c.Ws, c.C, c.ldx = N, Hs, Ws, C, C
+    c.R = c.S = k
+    if mode == "same":
+        Ho, Wo, c.stride, c.pad_h, c.pad_w, c.pix_flags = Hs, Ws, 1, k // 2, k // 2, 0
+    elif mode == "up2":
+        Ho, Wo, c.stride, c.pad_h, c.pad_w, c.pix_flags = 2 * Hs + 1, 2 * Ws + 1, 2, 0, 0, L.PIX_TRANSPOSED
+    else:
+        Ho, Wo, c.stride, c.pad_h, c.pad_w, c.pix_flags = (Hs - 3) // 2 + 1, (Ws - 3) // 2 + 1, 2, 0, 0, 0
+    c.Ho, c.Wo, c.Cout = Ho, Wo, Cout
+    c.epi_flags, c.alpha, c.beta = 0, 1.0, 1.0
+    out = torch.empty((N, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
+    c.x, c.w, c.out, c.ldo = L.ptr(x), L.ptr(wimg), L.ptr(out), Cout
+    d.pre, d.post, d.noise, d.noise_stride = L.ptr(pre), L.ptr(post), L.ptr(noise), noise_stride
+    if L.lib().sg_modconv2d_ok(L.C.byref(d)) != 1:
+        raise RuntimeError("modulated_conv2d: sg_modconv2d_ok refused the problem (there is no other path)")
+    L.call("sg_modconv2d_fwd", d, L.stream())
+    return out
+
+
+def _reduce_raw(a, b=None, rowsub=None, rowsub_stride=0, scale=None, want_rowsum=False):
+    """sg_modconv_reduce over dense NHWC a (and b): -> (scale * a or None, sum_p a (b - rowsub) [N, C] or None, sum_c a [N, P] or None)"""
+    N, C = a.shape[0], a.shape[3]
+    P = a.shape[1] * a.shape[2]
+    out = torch.empty_like(a) if scale is not None else None
+    part = None
+    if b is not None:
+        part = torch.empty((N, L.lib().sg_modconv_reduce_slabs(P), C), dtype=torch.float32, device=a.device)
+    rowsum = torch.empty((N, P), dtype=torch.float32, device=a.device) if want_rowsum else None
+    L.call("sg_modconv_reduce", L.dt(a), L.ptr(a), L.ptr(b), L.ptr(rowsub), rowsub_stride, L.ptr(scale), L.ptr(out), L.ptr(part), L.ptr(rowsum),
+           N, P, C, C, C, L.stream())
+    return out, (part.sum(dim=1) if part is not None else None), rowsum
+
+
+class _ModConvFn(torch.autograd.Function):
+    """the kernel's part of the operator: y = d * conv(W, s * x) (+ noise at up = 1) as a channels_last NCHW tensor; at up = 2 the [2H+1, 2W+1] result of the
+    transposed convolution, in front of the FIR"""
+
+    @staticmethod
+    def forward(ctx, x, weight, styles, noise, up, demodulate, flip_weight):
+        N, C, H, W = x.shape
+        Cout, k = weight.shape[0], weight.shape[2]
+        xh = x.permute(0, 2, 3, 1).contiguous()                 # NHWC in memory: free for a channels_last x
+        w32 = weight.detach().to(torch.float32).contiguous()
+        s32 = styles.detach().to(torch.float32).contiguous()
+        Q = torch.empty((Cout, C), dtype=torch.float32, device=x.device)
+        dco = torch.empty((N, Cout), dtype=torch.float32, device=x.device) if demodulate else None
+        # d always from the fp32 values the caller passed, whatever the activation dtype (reference :52-59)
+        L.call("sg_modconv_dcoef", L.ptr(w32), L.ptr(s32) if demodulate else None, L.ptr(Q), L.ptr(dco), N, C, Cout, k * k, L.stream())
+        # taps of the image the kernel reads: correlation at up = 1, the gather of the transposed convolution at up = 2 (conv2d_resample.py:124 passes
+        # `not flip_weight` on, and conv_transpose2d scatters with the taps as given)
+        flipped = (k > 1) and ((up == 1) != bool(flip_weight))
+        weff = w32.flip(2, 3) if flipped else w32
+        wimg = weff.permute(0, 2, 3, 1).contiguous().to(x.dtype)         # [Cout][r][s][C]
+        nz, nstride = None, 0
+        if noise is not None:
+            nz = noise.detach().to(torch.float32).contiguous()
+            nstride = H * W if nz.dim() == 4 else 0
+        y = _modconv_raw(xh, wimg, Cout, k, "same" if up == 1 else "up2", pre=s32, post=dco, noise=nz, noise_stride=nstride)
+        ctx.save_for_backward(xh, w32, s32, Q, dco, y, nz)
+        ctx.cfg = (up, demodulate, flipped, k, weight.dtype, styles.dtype, None if noise is None else (noise.dtype, tuple(noise.shape)))
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        _first_order_only("modulated_conv2d")
+        xh, w32, s32, Q, dco, y, nz = ctx.saved_tensors
+        up, demodulate, flipped, k, w_dtype, s_dtype, noise_info = ctx.cfg
+        N, H, W, C = xh.shape
+        Cout = w32.shape[0]
+        T = xh.dtype
+        gyh = gy.to(T).permute(0, 2, 3, 1).contiguous()
+        need_noise = nz is not None and ctx.needs_input_grad[3]
+        weff = w32.flip(2, 3) if flipped else w32
+        # gu = d gy, d gd = sum_p gy (y - noise), dnoise = sum_o gy: one pass over gy and y
+        gu, dgd, gnoise = gyh, None, None
+        if demodulate:
+            gu, dgd, gnoise = _reduce_raw(gyh, b=y, rowsub=nz, rowsub_stride=(H * W if (nz is not None and nz.dim() == 4) else 0), scale=dco,
+                                          want_rowsum=need_noise)
+        elif need_noise:
+            _, _, gnoise = _reduce_raw(gyh, want_rowsum=True)
+        # unscaled data gradient through the same kernel (d rides on gy as its pre-scale: fp32 product, one rounding), then dx = s gxs, sum_p x gxs
+        if up == 1:
+            wd = weff.flip(2, 3).permute(1, 2, 3, 0).contiguous().to(T)          # [C][2-r][2-s][Cout]
+            gxs = _modconv_raw(gyh, wd, C, k, "same", pre=dco)
+        else:
+            wd = weff.permute(1, 2, 3, 0).contiguous().to(T)                     # [C][r][s][Cout]: gxs[h,w] = sum gu[2h+r, 2w+s] W[r,s]
+            gxs = _modconv_raw(gyh, wd, C, k, "down2", pre=dco)
+        dx, ds, _ = _reduce_raw(gxs, b=xh, scale=s32)
+        t = None
+        if demodulate:
+            t = dgd * dco * dco                                                  # gd d^3
+            ds = ds - s32 * (t @ Q)
+        dw = None
+        if ctx.needs_input_grad[1]:
+            xs, _, _ = _reduce_raw(xh, scale=s32)                                # s x, materialised for the weight-gradient kernel
+            if up == 1:
+                dwi = torch.zeros((Cout, k, k, C), dtype=torch.float32, device=xh.device)
+                conv2d_wgrad_raw(xs, gu, L.ptr(dwi), C, Cout, k, k, H, W, 1, k // 2, k // 2)
+                dw = dwi.permute(0, 3, 1, 2)
+            else:   # transposed: the roles swap (the stride-2 convolution gu -> gxs has the weight image [C][r][s][Cout])
+                dwi = torch.zeros((C, k, k, Cout), dtype=torch.float32, device=xh.device)
+                conv2d_wgrad_raw(gu, xs, L.ptr(dwi), Cout, C, k, k, H, W, 2, 0, 0)
+                dw = dwi.permute(3, 0, 1, 2)
+            if flipped:
+                dw = dw.flip(2, 3)
+            if demodulate:
+                dw = dw - w32 * (t.t() @ (s32 * s32))[:, :, None, None]
+            dw = dw.to(w_dtype)
+        dn = None
+        if need_noise:
+            dn = gnoise.reshape(N, 1, H, W) if len(noise_info[1]) == 4 else gnoise.sum(dim=0).reshape(H, W)
+            dn = dn.to(noise_info[0])
+        return dx.permute(0, 3, 1, 2), dw, ds.to(s_dtype), dn, None, None, None
+
+
+def modulated_conv2d(x, weight, styles, noise=None, up=1, down=1, padding=0, resample_filter=None, demodulate=True, flip_weight=True, fused_modconv=True):
+    """The reference's signature (stylegan2.py:28-40). x: NCHW, contiguous or channels_last, float32 or bfloat16; weight [O, I, k, k] and styles [N, I] may be
+    float32 next to a bfloat16 x; noise: [N, 1, Ho, Wo] or one shared [Ho, Wo] plane. The result is channels_last. fused_modconv is accepted and has no
+    effect: there is one route here. Supported: k = 1 or 3 with padding = k // 2, down = 1, up = 1, and up = 2 for k = 3 (transposed stride-2 convolution in
+    the kernel, then upfirdn2d with gain 4, then the noise: conv2d_resample.py:81-125; resample_filter=None is the identity filter, plain zero insertion).
+    First-order gradients only."""
+    N, C, H, W, Cout, k = _validate(x, weight, styles, noise, up, down, padding, resample_filter)
+    L.require_gpu(x.device)
+    if up == 1:
+        return _ModConvFn.apply(x, weight, styles, noise, 1, bool(demodulate), bool(flip_weight))
+    # d commutes with the per-channel FIR, so it stays in the kernel's epilogue; the noise comes after the FIR
+    core = _ModConvFn.apply(x, weight, styles, None, 2, bool(demodulate), bool(flip_weight))
+    fw, fh = _upfirdn2d._get_filter_size(resample_filter)
+    px0, px1, py0, py1 = (padding + (fw + up - 1) // 2 - (k - 1), padding + (fw - up) // 2 - (k - up),
+                          padding + (fh + up - 1) // 2 - (k - 1), padding + (fh - up) // 2 - (k - up))
+    y = _upfirdn2d.upfirdn2d(core, resample_filter, padding=[px0, px1, py0, py1], gain=up ** 2)
+    if noise is not None:
+        y = y + noise.to(y.dtype)
+    return y.contiguous(memory_format=torch.channels_last)
