@@ -90,6 +90,10 @@ int sg_get_f32_mode(void);
 /* number of launches so far that took the split path of `mode` (3 or 6; -1 for any other value): a relaxed atomic counter, for tests that have to
  * prove which arithmetic ran */
 long long sg_f32_split_launches(int mode);
+/* number of launches so far that took the 16-byte (bf16, 8 channels per thread) instantiation of an elementwise kernel that also has a scalar one:
+ * sg_avgpool2_fwd / _bwd, sg_maxpool2_fwd / _bwd, sg_relu_mask, sg_slice_up_fwd / _bwd, sg_copy_channels. Both instantiations give the same bytes; a
+ * relaxed atomic counter, for tests that have to prove which one ran */
+long long sg_ew_vec_launches(void);
 
 /* Residual-block tail in ONE launch (bf16): out = epilogue( alpha * [ conv3x3(x; w) + conv1x1(up2?(x2); w2) ] + bias + bias2 ).
  * Replaces `x0 = conv2d0(x0); out = x + x0` of the reference's blocks (src/models/big_resnet.py:28-42 GenBlock with nearest x2 on the

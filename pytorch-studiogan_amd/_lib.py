@@ -162,6 +162,7 @@ _PROTOS = {
     "sg_set_f32_mode": [_i],
     "sg_get_f32_mode": [],
     "sg_f32_split_launches": [_i],                         # returns a count
+    "sg_ew_vec_launches": [],                              # returns a count
     "sg_reduce_scatter_flat": [_vp, _vp, _ll, _vp],
     "sg_allgather_flat": [_vp, _vp, _ll, _vp],
     "sg_p2p_create": [_i, _i, _ll, C.POINTER(_vp), _vp],
@@ -310,6 +311,7 @@ def lib():
         l.sg_tok_gemm_launches.restype = _ll
         l.sg_mha_launches.restype = _ll
         l.sg_f32_split_launches.restype = _ll
+        l.sg_ew_vec_launches.restype = _ll
         # SG_F32_MODE=bf16x3 | bf16x6: the generic engine's fp32 contractions process-wide on a split-precision path (functional.f32_mode is the scoped
         # form and says what each mode covers); default = exact fp32 MFMA
         f32_mode = {"bf16x3": 3, "bf16x6": 6}.get(os.environ.get("SG_F32_MODE", "exact"), 0)

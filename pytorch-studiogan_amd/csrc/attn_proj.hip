@@ -12,7 +12,7 @@
 // row >> 2), a lane fetches its own MFMA B fragments (pixel lane & 31, k-half lane >> 5) with 16-byte buffer loads that return zeros out of range,
 // the loads of the next row block are issued before the MFMAs of this one, and the epilogue runs on a wave-private staging tile.
 // Numerics of the forward: the contraction over C is the same v_mfma_f32_32x32x16_bf16 sequence in ascending k from a zero accumulator as
-// sg_conv_sk_kernel's, and each projection is rounded to bf16 BEFORE the maximum is taken by the code of k_maxpool2_fwd_v8 (first maximum in
+// sg_conv_sk_kernel's, and each projection is rounded to bf16 BEFORE the maximum is taken by the code of k_maxpool2_fwd<bf16_t, true> (elementwise.hip) (first maximum in
 // (dy, dx) row-major order wins), so theta, the pooled values and the argmax planes are bit-identical to the three-launch path's.
 // The data gradient rounds once (fp32 sum of the residual and all three products) where the chained launches rounded three times.
 #include <stdlib.h>
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(64 * NW) void k_attn_proj_fwd(ApFwdParams p) {
       const u32x4 v = *(const u32x4*)(stg + (r & 31) * SP + c * 16);
       __builtin_amdgcn_raw_buffer_store_b128(v, rst, (int)off, 0, 0);
     }
-    // phi and g: a lane owns 8 channels of one window -- the four rows of the window, maximum and argmax as k_maxpool2_fwd_v8 takes them
+    // phi and g: a lane owns 8 channels of one window -- the four rows of the window, maximum and argmax as k_maxpool2_fwd takes them
 #pragma unroll
     for (int it = 0; it < NITP; it++) {
       const int idx = lane + 64 * it;
@@ -261,7 +261,7 @@ __global__ __launch_bounds__(64 * NW) void k_attn_proj_bwd(ApBwdParams p) {
     }
   };
 
-  // un-pool on load: the pooled gradient where the window's argmax is this pixel's position, zero elsewhere (k_maxpool2_bwd_v8's select)
+  // un-pool on load: the pooled gradient where the window's argmax is this pixel's position, zero elsewhere (k_maxpool2_bwd's select)
   auto unpool = [](u32x4 g, u32x2 av, uint32_t pos) {
     u32x4 o;
 #pragma unroll

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 typedef uint16_t bf16_t;  // raw bf16 storage (torch.bfloat16 bit pattern)
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
@@ -78,7 +79,32 @@ template <> __device__ __forceinline__ u32x4 pack16<bf16_t>(const float* o) {
   for (int i = 0; i < 4; i++) v[i] = (uint32_t)f2bf(o[2 * i]) | ((uint32_t)f2bf(o[2 * i + 1]) << 16);
   return v;
 }
-
+// V elements of T as ONE value, vec_t<T, V>: the element itself (V == 1) or the 16-byte vector (V == ET<T>::VEC, at a 16-byte aligned address). load_f: V
+// elements at p as fp32 lanes; pack_f: fp32 lanes as the value to store; copy_raw: V elements moved as stored. Stores are written
+// `*(vec_t<T, V>*)(address) = pack_f<T, V>(lanes)`: an assignment evaluates its value before its address, and that order is what the instruction scheduler sees.
+template <typename T, int V> using vec_t = std::conditional_t<V == 1, T, u32x4>;
+template <typename T, int V> __device__ __forceinline__ void load_f(const T* p, float* o) {
+  if constexpr (V == 1) o[0] = to_f<T>(p[0]); else unpack16<T>(*(const u32x4*)p, o);
+}
+template <typename T, int V> __device__ __forceinline__ vec_t<T, V> pack_f(const float* o) {
+  if constexpr (V == 1) return from_f<T>(o[0]); else return pack16<T>(o);
+}
+template <typename T, int V> __device__ __forceinline__ void copy_raw(T* d, const T* s) { *(vec_t<T, V>*)d = *(const vec_t<T, V>*)s; }
+// keep[e] ? g[e] : +0 for the V elements at g, on the stored bits: no float in between, so a NaN payload, a signalling NaN or -0 passes untouched. bf16 vectors
+// as masks on the packed dwords (two v_cndmask and one v_or per pair).
+template <typename T, int V> __device__ __forceinline__ vec_t<T, V> select_raw(const T* g, const bool* keep) {
+  if constexpr (V == 1) return keep[0] ? g[0] : (T)0;
+  else {
+    const u32x4 r = *(const u32x4*)g;
+    u32x4 o;
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+      if constexpr (sizeof(T) == 4) o[d] = keep[d] ? r[d] : 0u;
+      else o[d] = (keep[2 * d] ? (r[d] & 0xffffu) : 0u) | (keep[2 * d + 1] ? (r[d] & 0xffff0000u) : 0u);
+    }
+    return o;
+  }
+}
 
 template <typename T> __device__ __forceinline__ u32x4 relu16(u32x4 v);
 template <> __device__ __forceinline__ u32x4 relu16<float>(u32x4 v) {
@@ -176,6 +202,11 @@ struct SgProfScope {
   do {                                                        \
     if (!(cond)) { sg_set_error(msg); return -1; }            \
   } while (0)
+// runs the statement(s) with `T` bound to the element type of a dtype code; any other code fails the entry point
+#define DISPATCH_T(dtype, ...)                                          \
+  if ((dtype) == SG_DTYPE_F32) { typedef float T; __VA_ARGS__; }        \
+  else if ((dtype) == SG_DTYPE_BF16) { typedef bf16_t T; __VA_ARGS__; } \
+  else { sg_set_error("bad dtype"); return -1; }
 #define SG_LAUNCH_CHECK()                                     \
   do {                                                        \
     hipError_t e__ = hipGetLastError();                       \

@@ -1,6 +1,7 @@
 // elementwise.hip -- HBM-bound glue of the hot path: layout changes at the NCHW boundary, pooling, softmax,
 // reductions, embedding gather/scatter, the projection-discriminator head and the adversarial losses.
 // All kernels are coalesced along the channel (fastest NHWC) dimension; wave = 64.
+#include <initializer_list>
 #include "common.h"
 #include "../../include/sgamd.h"
 
@@ -10,10 +11,38 @@ static inline int nblk(long long n, int bs) {
   if (b < 1) b = 1;
   return (int)b;
 }
-#define DISPATCH_T(dtype, ...)                                          \
-  if ((dtype) == SG_DTYPE_F32) { typedef float T; __VA_ARGS__; }        \
-  else if ((dtype) == SG_DTYPE_BF16) { typedef bf16_t T; __VA_ARGS__; } \
-  else { sg_set_error("bad dtype"); return -1; }
+
+// ---- one body for the scalar and the 16-byte path (pooling, relu_mask, slice_up, copy_channels) -------------------------------------------------------------
+// k_<op><T, VECP>: a thread owns V consecutive channels of one pixel (V consecutive elements for relu_mask), V = VECP ? ET<T>::VEC : 1. Both V run the same
+// arithmetic in the same order on every element -- the lanes of one #pragma unroll loop -- so a problem gives the same bytes on either path.
+// Why the 16-byte path exists: with 2 bytes per thread behind three or four 64-bit divisions these kernels were 20 % of BigGAN-deep's kernel time (k_relu_mask
+// 10.6 %, k_avgpool2_bwd 3.9 %, k_slice_up_fwd 2.9 %, k_avgpool2_fwd 1.3 %: round 2, session O) and 2.5 ms of the C3 step (max-pool: 0.9 + 1.6 ms).
+// VECP: 32-bit unsigned item indices (the gate demands fewer than 2^31 vector items); scalar: long long.
+template <bool VECP> using ew_index_t = std::conditional_t<VECP, unsigned, long long>;
+#define EW_ITEMS(i, total) for (I i = blockIdx.x * (I)256 + threadIdx.x; i < (total); i += gridDim.x * (I)256)
+// The gate: bf16, the channel count and every pitch a multiple of V, every pointer that gets 16-byte accesses aligned, the max-pool index plane (V-byte
+// accesses; may be null) aligned to V, fewer than 2^31 vector items. fp32 always takes the scalar instantiation: V = 4 for fp32 would change fp32 timings
+// and is a change of its own.
+static bool ew_vec_ok(int dtype, long long C, std::initializer_list<int> pitches, std::initializer_list<const void*> p16, const void* idx, long long items) {
+  constexpr int V = ET<bf16_t>::VEC;
+  long long rem = C % V;
+  for (int ld : pitches) rem |= ld % V;
+  uintptr_t low = 0;
+  for (const void* p : p16) low |= (uintptr_t)p;
+  return dtype == SG_DTYPE_BF16 && rem == 0 && (low & 15) == 0 && ((uintptr_t)idx & (V - 1)) == 0 && items < (1ll << 31);
+}
+static long long g_ew_vec_launches = 0;
+extern "C" long long sg_ew_vec_launches(void) { return __atomic_load_n(&g_ew_vec_launches, __ATOMIC_RELAXED); }
+// launches kern<T, vec> over `total` elements (vec: total / V items of bf16) and checks the launch; the kernel arguments may name T
+#define EW_LAUNCH(kern, dtype, vec, total, s, ...)                                                                                                              \
+  do {                                                                                                                                                          \
+    if (vec) {                                                                                                                                                  \
+      typedef bf16_t T;                                                                                                                                         \
+      __atomic_fetch_add(&g_ew_vec_launches, 1, __ATOMIC_RELAXED);                                                                                              \
+      hipLaunchKernelGGL((kern<T, true>), dim3(nblk((total) / ET<T>::VEC, 256)), dim3(256), 0, (hipStream_t)(s), __VA_ARGS__);                                  \
+    } else DISPATCH_T(dtype, hipLaunchKernelGGL((kern<T, false>), dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)(s), __VA_ARGS__))                         \
+    SG_LAUNCH_CHECK();                                                                                                                                          \
+  } while (0)
 
 // ---- layout -------------------------------------------------------------------------------------------
 template <typename T> __global__ void k_nchw_to_nhwc(const float* src, T* dst, int N, int C, int HW, int ldo) {
@@ -89,184 +118,118 @@ extern "C" int sg_nchw_grad_to_nhwc(int dtype, const float* dy, const float* y, 
 }
 
 // ---- 2x2 pooling ---------------------------------------------------------------------------------------
-template <typename T> __global__ void k_avgpool2_fwd(const T* x, T* y, int N, int H, int W, int C) {
-  const int H2 = H / 2, W2 = W / 2;
-  long long total = (long long)N * H2 * W2 * C;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    int c = (int)(i % C); long long t = i / C; int w2 = (int)(t % W2); t /= W2; int h2 = (int)(t % H2); int n = (int)(t / H2);
-    const T* p = x + (((long long)n * H + 2 * h2) * W + 2 * w2) * C + c;
-    float v = to_f<T>(p[0]) + to_f<T>(p[C]) + to_f<T>(p[(long long)W * C]) + to_f<T>(p[(long long)W * C + C]);
-    y[i] = from_f<T>(0.25f * v);
-  }
-}
-// ---- 16-byte bf16 variants of the elementwise layout kernels (round 2) ------------------------------------------------------------------
-// The scalar kernels move 2 bytes per thread behind three or four 64-bit divisions; they were 20 % of BigGAN-deep's kernel time
-// (k_relu_mask 10.6 %, k_avgpool2_bwd 3.9 %, k_slice_up_fwd 2.9 %, k_avgpool2_fwd 1.3 %: gpurun session O) and 2.5 ms of the C3 step (max-pool).
-// A thread owns 8 channels of one pixel; same arithmetic in the same order as the scalar kernels -> identical results.
-static inline bool ew_v8_ok(int dtype, const void* a, const void* b, int C, int lda, int ldb, long long total_vec) {
-  return dtype == SG_DTYPE_BF16 && C % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0 && total_vec > 0 && total_vec < (1ll << 31);
-}
-__global__ __launch_bounds__(256) void k_avgpool2_fwd_v8(const bf16_t* x, bf16_t* y, int N, int H, int W, int C) {
-  const int H2 = H / 2, W2 = W / 2, CV = C / 8;
-  const unsigned total = (unsigned)N * H2 * W2 * CV;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned q = i / CV, cv = i - q * CV;
-    const unsigned w2 = q % W2, t = q / W2, h2 = t % H2, n = t / H2;
-    const bf16_t* p = x + (((long long)n * H + 2 * h2) * W + 2 * w2) * C + cv * 8;
-    float a[8], b[8], c[8], d[8];
-    unpack16<bf16_t>(*(const u32x4*)p, a); unpack16<bf16_t>(*(const u32x4*)(p + C), b);
-    unpack16<bf16_t>(*(const u32x4*)(p + (long long)W * C), c); unpack16<bf16_t>(*(const u32x4*)(p + (long long)W * C + C), d);
+template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_avgpool2_fwd(const T* x, T* y, int N, int H, int W, int C) {
+  constexpr int V = VECP ? ET<T>::VEC : 1;
+  typedef ew_index_t<VECP> I;
+  const int H2 = H / 2, W2 = W / 2, CV = C / V;
+  const I total = (I)N * H2 * W2 * CV;
+  EW_ITEMS(i, total) {
+    const I q = i / CV, cv = i - q * CV, w2 = q % W2, t = q / W2, h2 = t % H2, n = t / H2;
+    const T* p = x + (((long long)n * H + 2 * h2) * W + 2 * w2) * C + cv * V;
+    float a[V], b[V], c[V], d[V];
+    load_f<T, V>(p, a); load_f<T, V>(p + C, b); load_f<T, V>(p + (long long)W * C, c); load_f<T, V>(p + (long long)W * C + C, d);
 #pragma unroll
-    for (int e = 0; e < 8; e++) a[e] = 0.25f * (((a[e] + b[e]) + c[e]) + d[e]);
-    *(u32x4*)(y + (long long)q * C + cv * 8) = pack16<bf16_t>(a);
-  }
-}
-__global__ __launch_bounds__(256) void k_avgpool2_bwd_v8(const bf16_t* dy, bf16_t* dx, int N, int H, int W, int C) {
-  const int H2 = H / 2, W2 = W / 2, CV = C / 8;
-  const unsigned total = (unsigned)N * H * W * CV;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned pix = i / CV, cv = i - pix * CV;
-    const unsigned w = pix % W, t = pix / W, h = t % H, n = t / H;
-    float g[8];
-    unpack16<bf16_t>(*(const u32x4*)(dy + (((long long)n * H2 + (h >> 1)) * W2 + (w >> 1)) * C + cv * 8), g);
-#pragma unroll
-    for (int e = 0; e < 8; e++) g[e] = 0.25f * g[e];
-    *(u32x4*)(dx + (long long)pix * C + cv * 8) = pack16<bf16_t>(g);
+    for (int e = 0; e < V; e++) a[e] = 0.25f * (((a[e] + b[e]) + c[e]) + d[e]);
+    *(vec_t<T, V>*)(y + (long long)q * C + cv * V) = pack_f<T, V>(a);
   }
 }
 extern "C" int sg_avgpool2_fwd(int dtype, const void* x, void* y, int N, int H, int W, int C, sg_stream_t s) {
   SG_CHECK(x && y && H % 2 == 0 && W % 2 == 0, "sg_avgpool2_fwd: bad args");
-  long long total = (long long)N * (H / 2) * (W / 2) * C;
-  if (ew_v8_ok(dtype, x, y, C, 8, 8, total / 8)) {
-    hipLaunchKernelGGL(k_avgpool2_fwd_v8, dim3(nblk(total / 8, 256)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, (bf16_t*)y, N, H, W, C);
-    SG_LAUNCH_CHECK();
-    return 0;
-  }
-  DISPATCH_T(dtype, hipLaunchKernelGGL(k_avgpool2_fwd<T>, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)s, (const T*)x, (T*)y, N, H, W, C));
-  SG_LAUNCH_CHECK();
+  const long long total = (long long)N * (H / 2) * (W / 2) * C;
+  const bool vec = ew_vec_ok(dtype, C, {}, {x, y}, nullptr, total / 8);
+  EW_LAUNCH(k_avgpool2_fwd, dtype, vec, total, s, (const T*)x, (T*)y, N, H, W, C);
   return 0;
 }
-template <typename T> __global__ void k_avgpool2_bwd(const T* dy, T* dx, int N, int H, int W, int C) {
-  // H, W are the dims of dx
-  const int H2 = H / 2, W2 = W / 2;
-  long long total = (long long)N * H * W * C;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    int c = (int)(i % C); long long t = i / C; int w = (int)(t % W); t /= W; int h = (int)(t % H); int n = (int)(t / H);
-    float g = to_f<T>(dy[(((long long)n * H2 + (h >> 1)) * W2 + (w >> 1)) * C + c]);
-    dx[i] = from_f<T>(0.25f * g);
+// H, W are the dims of dx
+template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_avgpool2_bwd(const T* dy, T* dx, int N, int H, int W, int C) {
+  constexpr int V = VECP ? ET<T>::VEC : 1;
+  typedef ew_index_t<VECP> I;
+  const int H2 = H / 2, W2 = W / 2, CV = C / V;
+  const I total = (I)N * H * W * CV;
+  EW_ITEMS(i, total) {
+    const I pix = i / CV, cv = i - pix * CV, w = pix % W, t = pix / W, h = t % H, n = t / H;
+    float g[V];
+    load_f<T, V>(dy + (((long long)n * H2 + (h >> 1)) * W2 + (w >> 1)) * C + cv * V, g);
+#pragma unroll
+    for (int e = 0; e < V; e++) g[e] = 0.25f * g[e];
+    *(vec_t<T, V>*)(dx + (long long)pix * C + cv * V) = pack_f<T, V>(g);
   }
 }
 extern "C" int sg_avgpool2_bwd(int dtype, const void* dy, void* dx, int N, int H, int W, int C, sg_stream_t s) {
   SG_CHECK(dy && dx && H % 2 == 0 && W % 2 == 0, "sg_avgpool2_bwd: bad args");
-  long long total = (long long)N * H * W * C;
-  if (ew_v8_ok(dtype, dy, dx, C, 8, 8, total / 8)) {
-    hipLaunchKernelGGL(k_avgpool2_bwd_v8, dim3(nblk(total / 8, 256)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)dy, (bf16_t*)dx, N, H, W, C);
-    SG_LAUNCH_CHECK();
-    return 0;
-  }
-  DISPATCH_T(dtype, hipLaunchKernelGGL(k_avgpool2_bwd<T>, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)s, (const T*)dy, (T*)dx, N, H, W, C));
-  SG_LAUNCH_CHECK();
+  const long long total = (long long)N * H * W * C;
+  const bool vec = ew_vec_ok(dtype, C, {}, {dy, dx}, nullptr, total / 8);
+  EW_LAUNCH(k_avgpool2_bwd, dtype, vec, total, s, (const T*)dy, (T*)dx, N, H, W, C);
   return 0;
 }
-template <typename T> __global__ void k_maxpool2_fwd(const T* x, int ldx, T* y, int ldy, uint8_t* idx, int N, int H, int W, int C) {
-  const int H2 = H / 2, W2 = W / 2;
-  long long total = (long long)N * H2 * W2 * C;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    int c = (int)(i % C); long long q = i / C; long long t = q; int w2 = (int)(t % W2); t /= W2; int h2 = (int)(t % H2); int n = (int)(t / H2);
-    const T* p = x + (((long long)n * H + 2 * h2) * W + 2 * w2) * ldx + c;
-    // first maximum in (dy,dx) row-major order wins, like torch's max_pool2d
-    float v0 = to_f<T>(p[0]), v1 = to_f<T>(p[ldx]), v2 = to_f<T>(p[(long long)W * ldx]), v3 = to_f<T>(p[(long long)W * ldx + ldx]);
-    float m = v0; int a = 0;
-    if (v1 > m) { m = v1; a = 1; }
-    if (v2 > m) { m = v2; a = 2; }
-    if (v3 > m) { m = v3; a = 3; }
-    y[q * ldy + c] = from_f<T>(m);
-    if (idx) idx[i] = (uint8_t)a;
-  }
+// The max-pool index plane: one byte per element, a pixel's place in its 2x2 window (2 dy + dx). V places travel as one V-byte access, packed little-endian
+// into w[0] (V <= 4) or w[0], w[1] (V == 8).
+template <int V> __device__ __forceinline__ void store_places(uint8_t* p, const uint32_t* w) {
+  if constexpr (V == 1) p[0] = (uint8_t)w[0];
+  else if constexpr (V == 4) *(uint32_t*)p = w[0];
+  else { u32x2 v = {w[0], w[1]}; *(u32x2*)p = v; }
 }
-// bf16, C % 8 == 0, 16-byte aligned rows: a thread owns 8 channels of one output pixel -- four 16-byte loads, one 16-byte store, 8 index
-// bytes; 32-bit index arithmetic (the scalar kernel: 2 bytes per thread and four 64-bit divisions per element, 0.9 + 1.6 ms per step)
-__global__ __launch_bounds__(256) void k_maxpool2_fwd_v8(const bf16_t* x, int ldx, bf16_t* y, int ldy, uint8_t* idx, int N, int H, int W, int C) {
-  const int H2 = H / 2, W2 = W / 2, CV = C / 8;
-  const unsigned total = (unsigned)N * H2 * W2 * CV;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned q = i / CV, cv = i - q * CV;
-    const unsigned w2 = q % W2, t = q / W2, h2 = t % H2, n = t / H2;
-    const bf16_t* p = x + (((long long)n * H + 2 * h2) * W + 2 * w2) * ldx + cv * 8;
-    const u32x4 r0 = *(const u32x4*)p, r1 = *(const u32x4*)(p + ldx), r2 = *(const u32x4*)(p + (long long)W * ldx), r3 = *(const u32x4*)(p + (long long)W * ldx + ldx);
-    float v0[8], v1[8], v2[8], v3[8], m[8];
-    unpack16<bf16_t>(r0, v0); unpack16<bf16_t>(r1, v1); unpack16<bf16_t>(r2, v2); unpack16<bf16_t>(r3, v3);
-    uint32_t a_lo = 0, a_hi = 0;
+template <int V> __device__ __forceinline__ void load_places(const uint8_t* p, uint32_t* w) {
+  if constexpr (V == 1) w[0] = p[0];
+  else if constexpr (V == 4) w[0] = *(const uint32_t*)p;
+  else { const u32x2 v = *(const u32x2*)p; w[0] = v[0]; w[1] = v[1]; }
+}
+// VECP: four 16-byte loads, one 16-byte store and 8 index bytes per thread
+template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_maxpool2_fwd(const T* x, int ldx, T* y, int ldy, uint8_t* idx, int N, int H, int W, int C) {
+  constexpr int V = VECP ? ET<T>::VEC : 1;
+  typedef ew_index_t<VECP> I;
+  const int H2 = H / 2, W2 = W / 2, CV = C / V;
+  const I total = (I)N * H2 * W2 * CV;
+  EW_ITEMS(i, total) {
+    const I q = i / CV, cv = i - q * CV, w2 = q % W2, t = q / W2, h2 = t % H2, n = t / H2;
+    const T* p = x + (((long long)n * H + 2 * h2) * W + 2 * w2) * ldx + cv * V;
+    float v0[V], v1[V], v2[V], v3[V];
+    load_f<T, V>(p, v0); load_f<T, V>(p + ldx, v1); load_f<T, V>(p + (long long)W * ldx, v2); load_f<T, V>(p + (long long)W * ldx + ldx, v3);
+    uint32_t aw[2] = {0u, 0u};
 #pragma unroll
-    for (int e = 0; e < 8; e++) {
+    for (int e = 0; e < V; e++) {
       // first maximum in (dy,dx) row-major order wins, like torch's max_pool2d
-      float mm = v0[e]; uint32_t a = 0;
-      if (v1[e] > mm) { mm = v1[e]; a = 1; }
-      if (v2[e] > mm) { mm = v2[e]; a = 2; }
-      if (v3[e] > mm) { mm = v3[e]; a = 3; }
-      m[e] = mm;
-      if (e < 4) a_lo |= a << (8 * e); else a_hi |= a << (8 * (e - 4));
+      float m = v0[e]; uint32_t a = 0;
+      if (v1[e] > m) { m = v1[e]; a = 1; }
+      if (v2[e] > m) { m = v2[e]; a = 2; }
+      if (v3[e] > m) { m = v3[e]; a = 3; }
+      v0[e] = m;
+      aw[e / 4] |= a << (8 * (e % 4));
     }
-    *(u32x4*)(y + (long long)q * ldy + cv * 8) = pack16<bf16_t>(m);
-    if (idx) { u32x2 av = {a_lo, a_hi}; *(u32x2*)(idx + (long long)q * C + cv * 8) = av; }
+    *(vec_t<T, V>*)(y + (long long)q * ldy + cv * V) = pack_f<T, V>(v0);
+    if (idx) store_places<V>(idx + (long long)q * C + cv * V, aw);
   }
-}
-__global__ __launch_bounds__(256) void k_maxpool2_bwd_v8(const bf16_t* dy, int ldy, const uint8_t* idx, bf16_t* dx, int ldx, int N, int H, int W, int C) {
-  const int H2 = H / 2, W2 = W / 2, CV = C / 8;
-  const unsigned total = (unsigned)N * H * W * CV;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned pix = i / CV, cv = i - pix * CV;
-    const unsigned w = pix % W, t = pix / W, h = t % H, n = t / H;
-    const long long q = ((long long)n * H2 + (h >> 1)) * W2 + (w >> 1);
-    const uint32_t pos = ((h & 1) << 1) | (w & 1);
-    const u32x2 av = *(const u32x2*)(idx + q * C + cv * 8);
-    const u32x4 g = *(const u32x4*)(dy + q * ldy + cv * 8);
-    u32x4 o;
-#pragma unroll
-    for (int d = 0; d < 4; d++) {
-      const uint32_t a0 = ((d < 2 ? av[0] : av[1]) >> (16 * (d & 1))) & 0xffu, a1 = ((d < 2 ? av[0] : av[1]) >> (16 * (d & 1) + 8)) & 0xffu;
-      o[d] = (a0 == pos ? (g[d] & 0xffffu) : 0u) | (a1 == pos ? (g[d] & 0xffff0000u) : 0u);
-    }
-    *(u32x4*)(dx + (long long)pix * ldx + cv * 8) = o;
-  }
-}
-static inline bool pool_v8_ok(int dtype, const void* a, int lda, const void* b, int ldb, const void* idx, int C, long long total_vec) {
-  return dtype == SG_DTYPE_BF16 && C % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0 && (((uintptr_t)idx) & 7) == 0 &&
-         total_vec < (1ll << 31);
 }
 extern "C" int sg_maxpool2_fwd(int dtype, const void* x, int ldx, void* y, int ldy, uint8_t* idx, int N, int H, int W, int C, sg_stream_t s) {
   SG_CHECK(x && y && H % 2 == 0 && W % 2 == 0, "sg_maxpool2_fwd: bad args");
-  long long total = (long long)N * (H / 2) * (W / 2) * C;
-  if (pool_v8_ok(dtype, x, ldx, y, ldy, idx, C, total / 8)) {
-    hipLaunchKernelGGL(k_maxpool2_fwd_v8, dim3(nblk(total / 8, 256)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, idx, N, H, W, C);
-    SG_LAUNCH_CHECK();
-    return 0;
-  }
-  DISPATCH_T(dtype, hipLaunchKernelGGL(k_maxpool2_fwd<T>, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)s, (const T*)x, ldx, (T*)y, ldy, idx, N, H, W, C));
-  SG_LAUNCH_CHECK();
+  const long long total = (long long)N * (H / 2) * (W / 2) * C;
+  const bool vec = ew_vec_ok(dtype, C, {ldx, ldy}, {x, y}, idx, total / 8);
+  EW_LAUNCH(k_maxpool2_fwd, dtype, vec, total, s, (const T*)x, ldx, (T*)y, ldy, idx, N, H, W, C);
   return 0;
 }
-template <typename T> __global__ void k_maxpool2_bwd(const T* dy, int ldy, const uint8_t* idx, T* dx, int ldx, int N, int H, int W, int C) {
-  const int H2 = H / 2, W2 = W / 2;
-  long long total = (long long)N * H * W * C;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    int c = (int)(i % C); long long pix = i / C; long long t = pix; int w = (int)(t % W); t /= W; int h = (int)(t % H); int n = (int)(t / H);
-    long long q = ((long long)n * H2 + (h >> 1)) * W2 + (w >> 1);
-    int pos = ((h & 1) << 1) | (w & 1);
-    float g = (idx[q * C + c] == pos) ? to_f<T>(dy[q * ldy + c]) : 0.f;
-    dx[pix * ldx + c] = from_f<T>(g);
+// dx = dy where the window's maximum sat at this pixel, +0 elsewhere: a select on the stored bits
+template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_maxpool2_bwd(const T* dy, int ldy, const uint8_t* idx, T* dx, int ldx, int N, int H, int W, int C) {
+  constexpr int V = VECP ? ET<T>::VEC : 1;
+  typedef ew_index_t<VECP> I;
+  const int H2 = H / 2, W2 = W / 2, CV = C / V;
+  const I total = (I)N * H * W * CV;
+  EW_ITEMS(i, total) {
+    const I pix = i / CV, cv = i - pix * CV, w = pix % W, t = pix / W, h = t % H, n = t / H;
+    const long long q = ((long long)n * H2 + (h >> 1)) * W2 + (w >> 1);
+    const uint32_t pos = (uint32_t)(((h & 1) << 1) | (w & 1));
+    uint32_t aw[2];
+    load_places<V>(idx + q * C + cv * V, aw);
+    bool keep[V];
+#pragma unroll
+    for (int e = 0; e < V; e++) keep[e] = ((aw[e / 4] >> (8 * (e % 4))) & 0xffu) == pos;
+    *(vec_t<T, V>*)(dx + (long long)pix * ldx + cv * V) = select_raw<T, V>(dy + q * ldy + cv * V, keep);
   }
 }
 extern "C" int sg_maxpool2_bwd(int dtype, const void* dy, int ldy, const uint8_t* idx, void* dx, int ldx, int N, int H, int W, int C, sg_stream_t s) {
   SG_CHECK(dy && dx && idx, "sg_maxpool2_bwd: null");
-  long long total = (long long)N * H * W * C;
-  if (pool_v8_ok(dtype, dy, ldy, dx, ldx, idx, C, total / 8)) {
-    hipLaunchKernelGGL(k_maxpool2_bwd_v8, dim3(nblk(total / 8, 256)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)dy, ldy, idx, (bf16_t*)dx, ldx, N, H, W, C);
-    SG_LAUNCH_CHECK();
-    return 0;
-  }
-  DISPATCH_T(dtype, hipLaunchKernelGGL(k_maxpool2_bwd<T>, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)s, (const T*)dy, ldy, idx, (T*)dx, ldx, N, H, W, C));
-  SG_LAUNCH_CHECK();
+  const long long total = (long long)N * H * W * C;
+  const bool vec = ew_vec_ok(dtype, C, {ldy, ldx}, {dy, dx}, idx, total / 8);
+  EW_LAUNCH(k_maxpool2_bwd, dtype, vec, total, s, (const T*)dy, ldy, idx, (T*)dx, ldx, N, H, W, C);
   return 0;
 }
 
@@ -698,31 +661,25 @@ extern "C" int sg_add_relu(int dtype, const void* a, const void* x, void* out, l
   SG_LAUNCH_CHECK();
   return 0;
 }
-// dx = dy * (x > 0)
-template <typename T> __global__ void k_relu_mask(const T* dy, const T* x, T* dx, long long n) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) dx[i] = (to_f<T>(x[i]) > 0.f) ? dy[i] : from_f<T>(0.f);
-}
-__global__ __launch_bounds__(256) void k_relu_mask_v8(const bf16_t* dy, const bf16_t* x, bf16_t* dx, unsigned nv) {
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < nv; i += gridDim.x * 256u) {
-    const u32x4 g = *(const u32x4*)(dy + 8ll * i);
-    float xv[8];
-    unpack16<bf16_t>(*(const u32x4*)(x + 8ll * i), xv);
-    u32x4 o;
+// dx = dy * (x > 0): dy where x > 0, +0 elsewhere, a select on the stored bits
+template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_relu_mask(const T* dy, const T* x, T* dx, long long n) {
+  constexpr int V = VECP ? ET<T>::VEC : 1;
+  typedef ew_index_t<VECP> I;
+  const I total = (I)(n / V);
+  EW_ITEMS(i, total) {
+    float xv[V];
+    load_f<T, V>(x + (long long)i * V, xv);
+    bool keep[V];
 #pragma unroll
-    for (int d = 0; d < 4; d++) o[d] = (xv[2 * d] > 0.f ? (g[d] & 0xffffu) : 0u) | (xv[2 * d + 1] > 0.f ? (g[d] & 0xffff0000u) : 0u);
-    *(u32x4*)(dx + 8ll * i) = o;
+    for (int e = 0; e < V; e++) keep[e] = xv[e] > 0.f;
+    *(vec_t<T, V>*)(dx + (long long)i * V) = select_raw<T, V>(dy + (long long)i * V, keep);
   }
 }
 extern "C" int sg_relu_mask(int dtype, const void* dy, const void* x, void* dx, long long n, sg_stream_t s) {
   SG_CHECK(dy && x && dx, "sg_relu_mask: null");
   if (n <= 0) return 0;
-  if (dtype == SG_DTYPE_BF16 && n % 8 == 0 && (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx) & 15) == 0 && n / 8 < (1ll << 31)) {
-    hipLaunchKernelGGL(k_relu_mask_v8, dim3(nblk(n / 8, 256)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)dy, (const bf16_t*)x, (bf16_t*)dx, (unsigned)(n / 8));
-    SG_LAUNCH_CHECK();
-    return 0;
-  }
-  DISPATCH_T(dtype, hipLaunchKernelGGL(k_relu_mask<T>, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)s, (const T*)dy, (const T*)x, (T*)dx, n));
-  SG_LAUNCH_CHECK();
+  const bool vec = ew_vec_ok(dtype, n, {}, {dy, x, dx}, nullptr, n / 8);
+  EW_LAUNCH(k_relu_mask, dtype, vec, n, s, (const T*)dy, (const T*)x, (T*)dx, n);
   return 0;
 }
 
@@ -816,105 +773,69 @@ extern "C" int sg_gp_bwd(int kind, const float* grads, const float* norms, const
 
 // ---- BigGAN-deep skip connections (reference src/models/big_resnet_deep_legacy.py:53-56,74-77,236-238) ------------------------
 // y[n][h][w][c] = x[n][h/up][w/up][c] for c < C: the generator's channel-slice (+ nearest x2) skip
-template <typename T> __global__ void k_slice_up_fwd(const T* x, T* y, int Hs, int Ws, int ldx, int C, int up, long long total) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C); long long t = i / C;
-    const int w = (int)(t % (Ws * up)); t /= (Ws * up);
-    const int h = (int)(t % (Hs * up)); const int n = (int)(t / (Hs * up));
-    y[i] = x[(((long long)n * Hs + h / up) * Ws + w / up) * ldx + c];
-  }
-}
-__global__ __launch_bounds__(256) void k_slice_up_fwd_v8(const bf16_t* x, bf16_t* y, int Hs, int Ws, int ldx, int C, int up, unsigned total) {
-  const int CV = C / 8, Wo = Ws * up, Ho = Hs * up;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned pix = i / CV, cv = i - pix * CV;
-    const unsigned w = pix % Wo, t = pix / Wo, h = t % Ho, n = t / Ho;
-    *(u32x4*)(y + (long long)pix * C + cv * 8) = *(const u32x4*)(x + (((long long)n * Hs + h / up) * Ws + w / up) * ldx + cv * 8);
-  }
-}
-__global__ __launch_bounds__(256) void k_slice_up_bwd_v8(const bf16_t* dy, bf16_t* dx, int Hs, int Ws, int ldx, int C, int up, unsigned total) {
-  const int LV = ldx / 8;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned pix = i / LV, cv = i - pix * LV;
-    const unsigned ws = pix % Ws, t = pix / Ws, hs = t % Hs, n = t / Hs;
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; e++) acc[e] = 0.f;
-    if ((int)cv * 8 < C) {
-      for (int a = 0; a < up; a++)
-        for (int b = 0; b < up; b++) {
-          float v[8];
-          unpack16<bf16_t>(*(const u32x4*)(dy + (((long long)n * Hs * up + hs * up + a) * (Ws * up) + ws * up + b) * C + cv * 8), v);
-#pragma unroll
-          for (int e = 0; e < 8; e++) acc[e] += v[e];
-        }
-    }
-    *(u32x4*)(dx + (long long)pix * ldx + cv * 8) = pack16<bf16_t>(acc);
-  }
-}
-__global__ __launch_bounds__(256) void k_copy_channels_v8(const bf16_t* src, int lds, bf16_t* dst, int ldd, int C, unsigned total) {
-  const int CV = C / 8;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned r = i / CV, cv = i - r * CV;
-    *(u32x4*)(dst + (long long)r * ldd + cv * 8) = *(const u32x4*)(src + (long long)r * lds + cv * 8);
+template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_slice_up_fwd(const T* x, T* y, int N, int Hs, int Ws, int ldx, int C, int up) {
+  constexpr int V = VECP ? ET<T>::VEC : 1;
+  typedef ew_index_t<VECP> I;
+  const int CV = C / V, Wo = Ws * up, Ho = Hs * up;
+  const I total = (I)N * Ho * Wo * CV;
+  EW_ITEMS(i, total) {
+    const I pix = i / CV, cv = i - pix * CV, w = pix % Wo, t = pix / Wo, h = t % Ho, n = t / Ho;
+    copy_raw<T, V>(y + (long long)pix * C + cv * V, x + (((long long)n * Hs + h / up) * Ws + w / up) * ldx + cv * V);
   }
 }
 extern "C" int sg_slice_up_fwd(int dtype, const void* x, void* y, int N, int Hs, int Ws, int ldx, int C, int up, sg_stream_t s) {
   SG_CHECK(x && y && C > 0 && C <= ldx && (up == 1 || up == 2), "sg_slice_up_fwd: bad args");
   const long long total = (long long)N * Hs * up * Ws * up * C;
-  if (ew_v8_ok(dtype, x, y, C, ldx, 8, total / 8)) {
-    hipLaunchKernelGGL(k_slice_up_fwd_v8, dim3(nblk(total / 8, 256)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, (bf16_t*)y, Hs, Ws, ldx, C, up, (unsigned)(total / 8));
-    SG_LAUNCH_CHECK();
-    return 0;
-  }
-  DISPATCH_T(dtype, hipLaunchKernelGGL(k_slice_up_fwd<T>, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)s, (const T*)x, (T*)y, Hs, Ws, ldx, C, up, total));
-  SG_LAUNCH_CHECK();
+  const bool vec = ew_vec_ok(dtype, C, {ldx}, {x, y}, nullptr, total / 8);
+  EW_LAUNCH(k_slice_up_fwd, dtype, vec, total, s, (const T*)x, (T*)y, N, Hs, Ws, ldx, C, up);
   return 0;
 }
-// dx[n][hs][ws][c] = sum over the up x up block of dy (c < C), 0 for the channels the slice dropped
-template <typename T> __global__ void k_slice_up_bwd(const T* dy, T* dx, int Hs, int Ws, int ldx, int C, int up, long long total) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % ldx); long long t = i / ldx;
-    const int ws = (int)(t % Ws); t /= Ws;
-    const int hs = (int)(t % Hs); const int n = (int)(t / Hs);
-    float acc = 0.f;
-    if (c < C) {
+// dx[n][hs][ws][c] = sum over the up x up block of dy (c < C; a outer, b inner, in fp32, rounded once), 0 for the channels the slice dropped
+template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_slice_up_bwd(const T* dy, T* dx, int N, int Hs, int Ws, int ldx, int C, int up) {
+  constexpr int V = VECP ? ET<T>::VEC : 1;
+  typedef ew_index_t<VECP> I;
+  const int LV = ldx / V;
+  const I total = (I)N * Hs * Ws * LV;
+  EW_ITEMS(i, total) {
+    const I pix = i / LV, cv = i - pix * LV, ws = pix % Ws, t = pix / Ws, hs = t % Hs, n = t / Hs;
+    float acc[V];
+#pragma unroll
+    for (int e = 0; e < V; e++) acc[e] = 0.f;
+    if ((int)cv * V < C) {
       for (int a = 0; a < up; a++)
-        for (int b = 0; b < up; b++)
-          acc += to_f<T>(dy[(((long long)n * Hs * up + hs * up + a) * (Ws * up) + ws * up + b) * C + c]);
+        for (int b = 0; b < up; b++) {
+          float v[V];
+          load_f<T, V>(dy + (((long long)n * Hs * up + hs * up + a) * (Ws * up) + ws * up + b) * C + cv * V, v);
+#pragma unroll
+          for (int e = 0; e < V; e++) acc[e] += v[e];
+        }
     }
-    dx[i] = from_f<T>(acc);
+    *(vec_t<T, V>*)(dx + (long long)pix * ldx + cv * V) = pack_f<T, V>(acc);
   }
 }
 extern "C" int sg_slice_up_bwd(int dtype, const void* dy, void* dx, int N, int Hs, int Ws, int ldx, int C, int up, sg_stream_t s) {
   SG_CHECK(dy && dx && C > 0 && C <= ldx && (up == 1 || up == 2), "sg_slice_up_bwd: bad args");
   const long long total = (long long)N * Hs * Ws * ldx;
-  if (ew_v8_ok(dtype, dy, dx, C, ldx, 8, total / 8)) {
-    hipLaunchKernelGGL(k_slice_up_bwd_v8, dim3(nblk(total / 8, 256)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)dy, (bf16_t*)dx, Hs, Ws, ldx, C, up, (unsigned)(total / 8));
-    SG_LAUNCH_CHECK();
-    return 0;
-  }
-  DISPATCH_T(dtype, hipLaunchKernelGGL(k_slice_up_bwd<T>, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)s, (const T*)dy, (T*)dx, Hs, Ws, ldx, C, up, total));
-  SG_LAUNCH_CHECK();
+  const bool vec = ew_vec_ok(dtype, C, {ldx}, {dy, dx}, nullptr, total / 8);
+  EW_LAUNCH(k_slice_up_bwd, dtype, vec, total, s, (const T*)dy, (T*)dx, N, Hs, Ws, ldx, C, up);
   return 0;
 }
 // dst[r][0..C) = src[r][0..C) with independent row pitches (channel-concat skip of the discriminator)
-template <typename T> __global__ void k_copy_channels(const T* src, int lds, T* dst, int ldd, int C, long long total) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C); const long long r = i / C;
-    dst[r * ldd + c] = src[r * lds + c];
+template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_copy_channels(const T* src, int lds, T* dst, int ldd, long long rows, int C) {
+  constexpr int V = VECP ? ET<T>::VEC : 1;
+  typedef ew_index_t<VECP> I;
+  const int CV = C / V;
+  const I total = (I)rows * CV;
+  EW_ITEMS(i, total) {
+    const I r = i / CV, cv = i - r * CV;
+    copy_raw<T, V>(dst + (long long)r * ldd + cv * V, src + (long long)r * lds + cv * V);
   }
 }
 extern "C" int sg_copy_channels(int dtype, const void* src, int ld_src, void* dst, int ld_dst, long long rows, int C, sg_stream_t s) {
   SG_CHECK(src && dst && rows > 0 && C > 0 && C <= ld_src && C <= ld_dst, "sg_copy_channels: bad args");
   const long long total = rows * C;
-  if (ew_v8_ok(dtype, src, dst, C, ld_src, ld_dst, total / 8)) {
-    hipLaunchKernelGGL(k_copy_channels_v8, dim3(nblk(total / 8, 256)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)src, ld_src, (bf16_t*)dst, ld_dst, C, (unsigned)(total / 8));
-    SG_LAUNCH_CHECK();
-    return 0;
-  }
-  DISPATCH_T(dtype, hipLaunchKernelGGL(k_copy_channels<T>, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)s, (const T*)src, ld_src, (T*)dst, ld_dst, C, total));
-  SG_LAUNCH_CHECK();
+  const bool vec = ew_vec_ok(dtype, C, {ld_src, ld_dst}, {src, dst}, nullptr, total / 8);
+  EW_LAUNCH(k_copy_channels, dtype, vec, total, s, (const T*)src, ld_src, (T*)dst, ld_dst, rows, C);
   return 0;
 }
 

@@ -6,11 +6,6 @@
 #include "common.h"
 #include "../../include/sgamd.h"
 
-#define DISPATCH_T(dtype, ...)                                          \
-  if ((dtype) == SG_DTYPE_F32) { typedef float T; __VA_ARGS__; }        \
-  else if ((dtype) == SG_DTYPE_BF16) { typedef bf16_t T; __VA_ARGS__; } \
-  else { sg_set_error("bad dtype"); return -1; }
-
 static inline int grid1d(long long total) { long long b = (total + 255) / 256; if (b > 256 * 32) b = 256 * 32; if (b < 1) b = 1; return (int)b; }
 
 // uint8 quantisation exactly as ops.quantize_images: x=(x+1)/2 ; (255*x+0.5).clamp(0,255) ; astype(uint8) (truncation).

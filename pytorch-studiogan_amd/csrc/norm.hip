@@ -6,11 +6,6 @@
 #include "common.h"
 #include "../../include/sgamd.h"
 
-#define DISPATCH_T(dtype, ...)                                          \
-  if ((dtype) == SG_DTYPE_F32) { typedef float T; __VA_ARGS__; }        \
-  else if ((dtype) == SG_DTYPE_BF16) { typedef bf16_t T; __VA_ARGS__; } \
-  else { sg_set_error("bad dtype"); return -1; }
-
 // ---- statistics ------------------------------------------------------------------------------------------
 template <typename T> __global__ __launch_bounds__(256) void k_bn_partial(const T* x, int ldx, long long rows, int C, double* partial, long long rpb) {
   __shared__ double sm[2][4][64];
