@@ -244,6 +244,12 @@ int sg_gemm(const sg_gemm_desc* d, sg_stream_t stream);
  * memory, items_host: the same table on the host. */
 typedef struct { const float* w; const float* y; const float* bias; float* out; int rows, K, ldy, ldo; } sg_linear_item;
 int sg_linear_group(const sg_linear_item* items_dev, const sg_linear_item* items_host, int n, int B, sg_stream_t stream);
+/* The same launch with three scales per item, applied in the store: out[b][o] = oscale * (wscale * sum_k w[o][k] y[b][k] + bscale * bias[o]).
+ * The style affines of a StyleGAN2 synthesis network: wscale / bscale = FullyConnectedLayer's equalised-learning-rate gains on the stored parameters,
+ * oscale = ToRGBLayer's fan-in gain. Every item reads its [B][K] slice of one ws tensor in place through ldy. */
+typedef struct { const float* w; const float* y; const float* bias; float* out; int rows, K, ldy, ldo; float wscale, bscale, oscale; int pad_; } sg_linear_item_scaled;
+int sg_linear_group_scaled(const sg_linear_item_scaled* items_dev, const sg_linear_item_scaled* items_host, int n, int B, sg_stream_t stream);
+long long sg_linear_group_scaled_launches(void);           /* launches so far (tests: one per synthesis forward) */
 
 /* ---- layout / elementwise ------------------------------------------------------------------------------ */
 /* fp32 NCHW -> T NHWC (ldo = channel pitch of the destination; ldo > C: channels C .. ldo - 1 of every row are written as zeros) */
@@ -610,6 +616,18 @@ int sg_upfirdn2d(int dtype, const void* x, const float* f, void* y, int planes, 
 int sg_filtered_lrelu(int dtype, const void* x, const float* fu, const float* fd, const void* b, void* y, int N, int C, int H, int W,
                       int fu_n, int fd_n, int up, int down, int px0, int px1, int py0, int py1, float gain, float slope, float clamp,
                       int flip_filter, sg_stream_t s);
+/* sg_fir_bias_act_nhwc (csrc/style_fir.hip): a 2-D FIR of at most 4 x 4 taps on a dense channels-last tensor, x [N][Hi][Wi][C] -> y [N][Ho][Wo][C] of the
+ * same dtype (fp32 / bf16), Ho = Hi + pady0 + pady1 - fh + 1, Wo likewise, with the tail of a StyleGAN2 synthesis layer on the fp32 accumulator:
+ *   y = clamp( gain * act( filter_gain * sum F x  + noise[n][oy][ox] + bias[c] ) )
+ * f: fp32 [fh][fw] on the device, applied as a true convolution unless flip_filter (sg_upfirdn2d's convention); pixels outside x are zero, a negative padding
+ * crops. noise: fp32, sample n at noise + n * noise_stride (0 = one shared plane), or NULL. bias: fp32 [C] or NULL. act: 1 linear or 3 lrelu with slope alpha
+ * (sg_bias_act's codes). clamp < 0: none. One rounding, at the store. noise = bias = NULL, act = 1, gain = 1, clamp < 0 is a plain NHWC FIR with
+ * sg_upfirdn2d's summation order (bit-identical in fp32). 16-byte vectors along C when C % (16 / element size) == 0 and x, y are 16-byte aligned, a scalar
+ * path otherwise. Anything else (more taps, another activation, another dtype) is refused with an error. */
+int sg_fir_bias_act_nhwc(int dtype, const void* x, const float* f, void* y, const float* noise, long long noise_stride, const float* bias,
+                         int N, int Hi, int Wi, int C, int fh, int fw, int padx0, int padx1, int pady0, int pady1, int flip_filter,
+                         float filter_gain, int act, float alpha, float gain, float clamp, sg_stream_t s);
+long long sg_fir_bias_act_launches(void);                  /* launches so far (tests: which kernel ran) */
 
 /* ---- differentiable augmentations in front of the discriminator and the consistency regularisers' loss -----------------------
  * sg_augment_fwd: y = cutout(translate(flip(contrast(saturation(brightness(x)))))) on fp32 NCHW image batches in ONE gather pass (one more partial-sum

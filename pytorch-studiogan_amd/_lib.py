@@ -67,6 +67,11 @@ class LinearItem(C.Structure):
     _fields_ = [("w", _vp), ("y", _vp), ("bias", _vp), ("out", _vp), ("rows", _i), ("K", _i), ("ldy", _i), ("ldo", _i)]
 
 
+class LinearItemScaled(C.Structure):
+    _fields_ = [("w", _vp), ("y", _vp), ("bias", _vp), ("out", _vp), ("rows", _i), ("K", _i), ("ldy", _i), ("ldo", _i),
+                ("wscale", _f), ("bscale", _f), ("oscale", _f), ("pad_", _i)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [("dtype", _i), ("p_form", _i), ("q_form", _i), ("I", _i), ("J", _i), ("K", _i), ("batch", _i),
                 ("p", _vp), ("p_bstride", _ll), ("ldp", _i), ("q", _vp), ("q_bstride", _ll), ("ldq", _i),
@@ -128,6 +133,8 @@ _PROTOS = {
     "sg_quad_pack": [_i, _i, _vp, _vp, _i, _i, _vp],
     "sg_quad_pack_batch": [_i, _vp, C.POINTER(QuadItem), _i, _vp],
     "sg_linear_group": [_vp, C.POINTER(LinearItem), _i, _i, _vp],
+    "sg_linear_group_scaled": [_vp, C.POINTER(LinearItemScaled), _i, _i, _vp],
+    "sg_linear_group_scaled_launches": [],                 # returns a count
     "sg_conv2d_q_wgrad_plan": [C.POINTER(ConvQWgradDesc), C.POINTER(_i), C.POINTER(_ll)],
     "sg_conv2d_q_wgrad": [C.POINTER(ConvQWgradDesc), _vp],
     "sg_prof_collect_ex": [C.POINTER(C.c_double), _i],
@@ -256,7 +263,9 @@ _PROTOS = {
     "sg_bias_act": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _i, _i, _i, _f, _f, _f, _vp],
     "sg_upfirdn2d": [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp],
     "sg_filtered_lrelu": [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _vp],
-    "sg_augment_work_floats": [C.POINTER(AugDesc)],       # returns a count (call through lib(), not call())
+    "sg_fir_bias_act_nhwc": [_i, _vp, _vp, _vp, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp],
+    "sg_fir_bias_act_launches": [],                        # returns a count
+    "sg_augment_work_floats": [C.POINTER(AugDesc)],      # returns a count (call through lib(), not call())
     "sg_augment_fwd": [C.POINTER(AugDesc), _vp, _vp, _vp, _vp],
     "sg_augment_bwd": [C.POINTER(AugDesc), _vp, _vp, _vp, _vp],
     "sg_mse_work_floats": [],                              # returns a count
@@ -312,6 +321,8 @@ def lib():
         l.sg_mha_launches.restype = _ll
         l.sg_f32_split_launches.restype = _ll
         l.sg_ew_vec_launches.restype = _ll
+        l.sg_linear_group_scaled_launches.restype = _ll
+        l.sg_fir_bias_act_launches.restype = _ll
         # SG_F32_MODE=bf16x3 | bf16x6: the generic engine's fp32 contractions process-wide on a split-precision path (functional.f32_mode is the scoped
         # form and says what each mode covers); default = exact fp32 MFMA
         f32_mode = {"bf16x3": 3, "bf16x6": 6}.get(os.environ.get("SG_F32_MODE", "exact"), 0)

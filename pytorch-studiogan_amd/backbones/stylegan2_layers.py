@@ -8,8 +8,9 @@ constructor and forward argument lists, and the attribute names behind the state
     SynthesisLayer        styles = affine(w);  y = clamp( gain * sqrt(2) * lrelu_0.2( modconv(x, W, styles) + strength * noise + b ) )
     ToRGBLayer            styles = affine(w) / sqrt(fan_in);  y = clamp( modconv(x, W, styles, no demodulation) + b )
 
-The convolution is style_ops.modulated_conv2d (csrc/modconv.hip), the activation style_ops.bias_act; the [N, w_dim] x [w_dim, C] affine is torch.
-The mapping / synthesis NETWORKS are not here yet, and nothing of this file is registered in config_map.py."""
+The convolution is style_ops.modulated_conv2d (csrc/modconv.hip), the activation style_ops.bias_act; the [N, w_dim] x [w_dim, C] affine is torch unless the
+caller hands the styles in (backbones/stylegan2.py computes all of a forward's in one launch). The mapping / synthesis networks are backbones/stylegan2.py;
+the discriminator and the StyleGAN2 training loop are still to come, and nothing of this file is registered in config_map.BACKBONES."""
 import math
 
 import torch
@@ -17,7 +18,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..style_ops.bias_act import activation_funcs, bias_act
-from ..style_ops.modulated_conv2d import modulated_conv2d
+from ..style_ops.modulated_conv2d import modulated_conv2d, modulated_conv2d_act
 from ..style_ops.upfirdn2d import setup_filter
 
 
@@ -69,15 +70,23 @@ class SynthesisLayer(nn.Module):
         plane = self.noise_const if mode == "const" else torch.randn(batch, 1, self.resolution, self.resolution, device=device)
         return plane * self.noise_strength
 
-    def forward(self, x, w, noise_mode="random", fused_modconv=True, gain=1):
+    def forward(self, x, w, noise_mode="random", fused_modconv=True, gain=1, styles=None, fused_resample=False):
+        """styles: this layer's affine(w) when the caller already has it (the synthesis network computes every layer's in one launch); w is then unused.
+        fused_resample: run through modulated_conv2d_act, whose up = 2 tail (FIR, noise, bias, activation) is one launch."""
         if noise_mode not in ("random", "const", "none"):
             raise AssertionError(f"SynthesisLayer: noise_mode {noise_mode!r} (random / const / none)")
         side = self.resolution // self.up
         if tuple(x.shape[1:]) != (self.weight.shape[1], side, side):
             raise AssertionError(f"SynthesisLayer: x must be [N, {self.weight.shape[1]}, {side}, {side}], got {tuple(x.shape)}")
+        if styles is None:
+            styles = self.affine(w)
         # the transposed convolution of up = 2 scatters the taps as stored (a convolution), up = 1 correlates like torch's conv2d
-        y = modulated_conv2d(x, self.weight, self.affine(w), noise=self._noise(x.shape[0], noise_mode, x.device), up=self.up, padding=self.padding,
-                             resample_filter=self.resample_filter, flip_weight=self.up == 1, fused_modconv=fused_modconv)
+        kw = dict(noise=self._noise(x.shape[0], noise_mode, x.device), up=self.up, padding=self.padding, resample_filter=self.resample_filter,
+                  flip_weight=self.up == 1, fused_modconv=fused_modconv)
+        if fused_resample:
+            return modulated_conv2d_act(x, self.weight, styles, bias=self.bias, act=self.activation, gain=self.act_gain * gain,
+                                        clamp=_scaled(self.conv_clamp, gain), **kw)
+        y = modulated_conv2d(x, self.weight, styles, **kw)
         return bias_act(y, self.bias.to(y.dtype), act=self.activation, gain=self.act_gain * gain, clamp=_scaled(self.conv_clamp, gain))
 
 
@@ -90,6 +99,9 @@ class ToRGBLayer(nn.Module):
         self.weight = _conv_weight(out_channels, in_channels, kernel_size, channels_last)
         self.bias = nn.Parameter(torch.zeros(out_channels))
 
-    def forward(self, x, w, fused_modconv=True):
-        y = modulated_conv2d(x, self.weight, self.affine(w) * self.weight_gain, demodulate=False, fused_modconv=fused_modconv)
+    def forward(self, x, w, fused_modconv=True, styles=None):
+        """styles: affine(w) * weight_gain when the caller already has it (see SynthesisLayer.forward)"""
+        if styles is None:
+            styles = self.affine(w) * self.weight_gain
+        y = modulated_conv2d(x, self.weight, styles, demodulate=False, fused_modconv=fused_modconv)
         return bias_act(y, self.bias.to(y.dtype), clamp=self.conv_clamp)

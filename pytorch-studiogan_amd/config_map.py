@@ -55,6 +55,28 @@ def model_args(y):
     return M["backbone"], modules, gen, dis
 
 
+def stylegan2_generator_args(y, mixed_precision=False):
+    """Keyword arguments of `backbones.stylegan2.Generator` for a `MODEL.backbone: stylegan2` configuration, as the reference builds it (src/models/model.py:26-46):
+    channel_base 32768 for CIFAR10 / CIFAR100 and for images of 512 and above, else 16384, channel_max 512; the generator is label-conditioned only under
+    g_cond_mtd = cAdaIN; mixed precision = the 4 highest resolutions in low precision with the convolution outputs clamped to +-256. (`model_args` keeps refusing
+    the StyleGAN backbones: there is no discriminator or training loop for them yet.)"""
+    import types
+    M, D, S = dict(y.get("MODEL") or {}), dict(y.get("DATA") or {}), dict(y.get("STYLEGAN") or {})
+    if M.get("backbone") != "stylegan2":
+        raise NotImplementedError(f"MODEL.backbone = {M.get('backbone')}: stylegan2_generator_args maps the stylegan2 generator only")
+    for sec, key in ((M, "w_dim"), (S, "mapping_network")):
+        if sec.get(key, _N) == _N:
+            raise NotImplementedError(f"{'MODEL' if sec is M else 'STYLEGAN'}.{key} must be set for a stylegan2 generator")
+    img, name = D.get("img_size", 32), D.get("name", "CIFAR10")
+    channel_base = 32768 if (img >= 512 or name in ("CIFAR10", "CIFAR100")) else 16384
+    M = {**_MODEL, **M}
+    namespace = {k: M[k] for k in ("info_type", "g_info_injection", "info_num_discrete_c", "info_num_conti_c", "info_dim_discrete_c", "backbone")}
+    return dict(z_dim=M["z_dim"], c_dim=D.get("num_classes", 10) if M["g_cond_mtd"] == "cAdaIN" else 0, w_dim=M["w_dim"], img_resolution=img,
+                img_channels=D.get("img_channels", 3), MODEL=types.SimpleNamespace(**namespace), mapping_kwargs={"num_layers": S["mapping_network"]},
+                synthesis_kwargs={"channel_base": channel_base, "channel_max": 512, "num_fp16_res": 4 if mixed_precision else 0,
+                                  "conv_clamp": 256 if mixed_precision else None})
+
+
 def model_namespace(y):
     import types
     M = sections(y)[0]

@@ -12,7 +12,9 @@
 
 #define LG_T 64
 #define LG_KC 32
-__global__ __launch_bounds__(256) void k_linear_group(const sg_linear_item* items, int n, int B) {
+// Item: sg_linear_item, or sg_linear_item_scaled whose three scales enter in the store only (SCALED): the tiling and the FMA chain are one body.
+template <typename Item, bool SCALED>
+__global__ __launch_bounds__(256) void k_linear_group(const Item* items, int n, int B) {
   __shared__ float Ws[LG_T][LG_KC + 1];
   __shared__ float Ys[LG_T][LG_KC + 1];
   int it = 0;
@@ -23,7 +25,7 @@ __global__ __launch_bounds__(256) void k_linear_group(const sg_linear_item* item
     t0 += nt;
   }
   if (it >= n) return;
-  const sg_linear_item q = items[it];
+  const Item q = items[it];
   const int o0 = ((int)blockIdx.x - t0) * LG_T, b0 = blockIdx.y * LG_T;
   const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
   float acc[4][4];
@@ -60,17 +62,23 @@ __global__ __launch_bounds__(256) void k_linear_group(const sg_linear_item* item
 #pragma unroll
     for (int i = 0; i < 4; i++) {
       const int o = o0 + tx + 16 * i;
-      if (o < q.rows) q.out[(long long)b * q.ldo + o] = acc[i][j] + (q.bias ? q.bias[o] : 0.f);
+      if (o >= q.rows) continue;
+      if constexpr (SCALED) q.out[(long long)b * q.ldo + o] = q.oscale * (q.wscale * acc[i][j] + (q.bias ? q.bscale * q.bias[o] : 0.f));
+      else q.out[(long long)b * q.ldo + o] = acc[i][j] + (q.bias ? q.bias[o] : 0.f);
     }
   }
 }
 
-extern "C" int sg_linear_group(const sg_linear_item* items_dev, const sg_linear_item* items_host, int n, int B, sg_stream_t stream) {
+static long long g_linear_group_scaled_launches = 0;
+extern "C" long long sg_linear_group_scaled_launches() { return __atomic_load_n(&g_linear_group_scaled_launches, __ATOMIC_RELAXED); }
+
+template <typename Item, bool SCALED>
+static int linear_group_launch(const Item* items_dev, const Item* items_host, int n, int B, sg_stream_t stream) {
   SG_CHECK(items_dev && items_host && n > 0 && B > 0, "sg_linear_group: bad arguments");
   long long tiles = 0;
   double flop = 0.0;
   for (int i = 0; i < n; i++) {
-    const sg_linear_item& q = items_host[i];
+    const Item& q = items_host[i];
     SG_CHECK(q.w && q.y && q.out && q.rows > 0 && q.K > 0 && q.ldy >= q.K && q.ldo >= q.rows, "sg_linear_group: bad item");
     tiles += (q.rows + LG_T - 1) / LG_T;
     flop += 2.0 * (double)q.rows * q.K * B;
@@ -78,8 +86,20 @@ extern "C" int sg_linear_group(const sg_linear_item* items_dev, const sg_linear_
   SG_CHECK(tiles < (1ll << 30), "sg_linear_group: too many tiles");
   hipStream_t st = (hipStream_t)stream;
   const int prof = sg_prof_begin(st, flop, 2);
-  hipLaunchKernelGGL(k_linear_group, dim3((unsigned)tiles, (unsigned)((B + LG_T - 1) / LG_T)), dim3(256), 0, st, items_dev, n, B);
+  hipLaunchKernelGGL((k_linear_group<Item, SCALED>), dim3((unsigned)tiles, (unsigned)((B + LG_T - 1) / LG_T)), dim3(256), 0, st, items_dev, n, B);
   sg_prof_end(st, prof);
   SG_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int sg_linear_group(const sg_linear_item* items_dev, const sg_linear_item* items_host, int n, int B, sg_stream_t stream) {
+  return linear_group_launch<sg_linear_item, false>(items_dev, items_host, n, B, stream);
+}
+
+// out = oscale * (wscale * sum_k w y + bscale * bias): the style affines of a StyleGAN2 synthesis network (FullyConnectedLayer's equalised-learning-rate
+// gains on the stored weight and bias, ToRGBLayer's fan-in gain on the result), every layer of a forward in one launch, each reading its slice of ws in place.
+extern "C" int sg_linear_group_scaled(const sg_linear_item_scaled* items_dev, const sg_linear_item_scaled* items_host, int n, int B, sg_stream_t stream) {
+  const int rc = linear_group_launch<sg_linear_item_scaled, true>(items_dev, items_host, n, B, stream);
+  if (rc == 0) __atomic_fetch_add(&g_linear_group_scaled_launches, 1, __ATOMIC_RELAXED);
+  return rc;
 }

@@ -2,5 +2,6 @@
 SURVEY.md 8(f4)): same function names, argument meaning and error behaviour, every launch a kernel of libsgamd.so (csrc/style.hip).
 `impl='cuda'` (the default, kept for call-site compatibility -- on PyTorch-ROCm the device type is still 'cuda') runs the HIP kernels;
 there is no `impl='ref'` here: the reference path lives in the reference and, restated for the tests, in oracle/style_ref.py.
-modulated_conv2d (reference src/models/stylegan2.py:28-98, the operator StyleGAN2's synthesis layers are made of) runs on csrc/modconv.hip."""
-from . import bias_act, upfirdn2d, filtered_lrelu, modulated_conv2d  # noqa: F401
+modulated_conv2d (reference src/models/stylegan2.py:28-98, the operator StyleGAN2's synthesis layers are made of) runs on csrc/modconv.hip;
+fir_bias_act (no counterpart in the reference: the FIR + noise + bias + activation tail of an up = 2 synthesis layer in one launch) on csrc/style_fir.hip."""
+from . import bias_act, upfirdn2d, filtered_lrelu, modulated_conv2d, fir_bias_act  # noqa: F401

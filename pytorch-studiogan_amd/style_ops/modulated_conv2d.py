@@ -197,3 +197,26 @@ def modulated_conv2d(x, weight, styles, noise=None, up=1, down=1, padding=0, res
     if noise is not None:
         y = y + noise.to(y.dtype)
     return y.contiguous(memory_format=torch.channels_last)
+
+
+def modulated_conv2d_act(x, weight, styles, noise=None, up=1, down=1, padding=0, resample_filter=None, demodulate=True, flip_weight=True, fused_modconv=True,
+                         bias=None, act="linear", gain=None, clamp=None):
+    """bias_act(modulated_conv2d(...), bias, act=act, gain=gain, clamp=clamp) -- a synthesis layer's whole arithmetic -- with the up = 2 tail in one launch.
+    up = 1: the convolution kernel (noise in its epilogue) and sg_bias_act, the two launches of the separate operators. up = 2: the transposed convolution to
+    the [2H+1, 2W+1] core, then ONE sg_fir_bias_act_nhwc (style_ops/fir_bias_act.py): low-pass, noise, bias, activation, gain and clamp on the fp32
+    accumulator, channels-last in and out. noise and bias enter in fp32 there, where the separate operators round both to x's dtype and round the activation
+    after the FIR and after the noise. act: 'linear' or 'lrelu' at up = 2. First-order gradients only."""
+    from .bias_act import bias_act
+    from .fir_bias_act import ACTS, MAX_TAPS, fir_bias_act
+    N, C, H, W, Cout, k = _validate(x, weight, styles, noise, up, down, padding, resample_filter)
+    fw, fh = _upfirdn2d._get_filter_size(resample_filter)
+    if up == 2 and (act not in ACTS or max(fw, fh) > MAX_TAPS):
+        raise NotImplementedError(f"modulated_conv2d_act: act={act!r} with a {fh} x {fw} filter has no fused tail at up=2 "
+                                  f"({' / '.join(ACTS)}, at most {MAX_TAPS} x {MAX_TAPS} taps): use modulated_conv2d and bias_act")
+    L.require_gpu(x.device)
+    if up == 1:
+        y = _ModConvFn.apply(x, weight, styles, noise, 1, bool(demodulate), bool(flip_weight))
+        return bias_act(y, None if bias is None else bias.to(y.dtype), act=act, gain=gain, clamp=clamp)
+    core = _ModConvFn.apply(x, weight, styles, None, 2, bool(demodulate), bool(flip_weight))
+    pad = [padding + (fw + up - 1) // 2 - (k - 1), padding + (fw - up) // 2 - (k - up), padding + (fh + up - 1) // 2 - (k - 1), padding + (fh - up) // 2 - (k - up)]
+    return fir_bias_act(core, resample_filter, pad, noise=noise, bias=bias, act=act, gain=gain, clamp=clamp, filter_gain=up ** 2)
