@@ -628,6 +628,32 @@ int sg_fir_bias_act_nhwc(int dtype, const void* x, const float* f, void* y, cons
                          int N, int Hi, int Wi, int C, int fh, int fw, int padx0, int padx1, int pady0, int pady1, int flip_filter,
                          float filter_gain, int act, float alpha, float gain, float clamp, sg_stream_t s);
 long long sg_fir_bias_act_launches(void);                  /* launches so far (tests: which kernel ran) */
+/* sg_act_fir_nhwc (csrc/style_fir.hip): the head of a StyleGAN2 discriminator down layer, activation on the LOAD side of a decimating FIR. x [N][Hi][Wi][C]
+ * dense channels-last -> y [N][Ho][Wo][C] of the same dtype (fp32 / bf16), Ho = (Hi + pady0 + pady1 - fh) / down + 1 (floor), Wo likewise:
+ *   a = clamp( gain * act( x + bias[c] ) ) inside the image, 0 outside (never act(bias));   y = filter_gain * sum F a[oy * down - pady0 + fy][ox * down - padx0 + fx]
+ * down: 1 or 2. f: fp32 [fh][fw] on the device, at most 4 x 4 taps, sg_upfirdn2d's flip_filter convention; negative padding crops. act: 1 linear or 3 lrelu
+ * (sg_bias_act's codes and tie convention). bias: fp32 [C] or NULL. clamp < 0: none. a is evaluated in fp32 and never stored; one rounding, at the store.
+ * With act = 1, bias = NULL, gain = 1, clamp < 0 the kernel is a plain decimating NHWC FIR, bit-identical to sg_upfirdn2d on the NCHW copy.
+ * sg_act_fir_nhwc_bwd takes the FORWARD's arguments plus dy [N][Ho][Wo][C] and writes dx [N][Hi][Wi][C] = (adjoint FIR of dy) * da/dx in one launch, da/dx
+ * re-evaluated from x and bias (x may be NULL when there is no gate; the launch then equals sg_upfirdn2d's adjoint bit for bit). Anything else is refused. */
+int sg_act_fir_nhwc(int dtype, const void* x, const float* f, void* y, const float* bias, int N, int Hi, int Wi, int C, int fh, int fw, int down,
+                    int padx0, int padx1, int pady0, int pady1, int flip_filter, float filter_gain, int act, float alpha, float gain, float clamp,
+                    sg_stream_t s);
+int sg_act_fir_nhwc_bwd(int dtype, const void* x, const void* dy, const float* f, void* dx, const float* bias, int N, int Hi, int Wi, int C, int fh,
+                        int fw, int down, int padx0, int padx1, int pady0, int pady1, int flip_filter, float filter_gain, int act, float alpha,
+                        float gain, float clamp, sg_stream_t s);
+long long sg_act_fir_launches(void);                       /* forward + backward launches so far */
+/* sg_mbstd_fwd / sg_mbstd_bwd (csrc/mbstd.hip): the minibatch standard deviation layer, one launch each. x: fp32 [N][H][W] pixels of pitch ldx >= C;
+ * G samples per group (sample g * (N / G) + m is in group m), F statistics channels over slices of C / F channels:
+ *   out [N][H][W][C + F] dense: out[..., :C] = x, out[n][h][w][C + f] = mean_{j,h,w} sqrt(var_g(x) + 1e-8)   (biased variance, two-pass)
+ *   dx  [N][H][W][C] dense   = dout[..., :C] + dS (x - mean_g) / (G (C / F) H W sqrt(var + 1e-8)),  dS[m][f] = sum_{g,h,w} dout[..., C + f]
+ * Deterministic (fixed-order sums, no float atomics). N % G != 0 or C % F != 0 is refused. A (group, slice) pair is cut into sg_mbstd_splits() chunks so
+ * that few pairs still fill the chip; when that is > 1 the forward needs part (fp32 [(N / G) F splits], any contents) and tickets ([(N / G) F] ZEROED
+ * counters, left nonzero): the last chunk of a pair to finish adds the partial sums in chunk order. NULL, NULL otherwise. */
+int sg_mbstd_splits(int N, int H, int W, int C, int G, int F);
+int sg_mbstd_fwd(const float* x, int ldx, float* out, float* part, unsigned* tickets, int N, int H, int W, int C, int G, int F, sg_stream_t s);
+int sg_mbstd_bwd(const float* x, int ldx, const float* dout, float* dx, int N, int H, int W, int C, int G, int F, sg_stream_t s);
+long long sg_mbstd_launches(void);
 
 /* ---- differentiable augmentations in front of the discriminator and the consistency regularisers' loss -----------------------
  * sg_augment_fwd: y = cutout(translate(flip(contrast(saturation(brightness(x)))))) on fp32 NCHW image batches in ONE gather pass (one more partial-sum

@@ -265,6 +265,13 @@ _PROTOS = {
     "sg_filtered_lrelu": [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _vp],
     "sg_fir_bias_act_nhwc": [_i, _vp, _vp, _vp, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp],
     "sg_fir_bias_act_launches": [],                        # returns a count
+    "sg_act_fir_nhwc": [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp],
+    "sg_act_fir_nhwc_bwd": [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp],
+    "sg_act_fir_launches": [],                             # returns a count
+    "sg_mbstd_splits": [_i, _i, _i, _i, _i, _i],           # returns a count (call through lib(), not call())
+    "sg_mbstd_fwd": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "sg_mbstd_bwd": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "sg_mbstd_launches": [],                               # returns a count
     "sg_augment_work_floats": [C.POINTER(AugDesc)],      # returns a count (call through lib(), not call())
     "sg_augment_fwd": [C.POINTER(AugDesc), _vp, _vp, _vp, _vp],
     "sg_augment_bwd": [C.POINTER(AugDesc), _vp, _vp, _vp, _vp],
@@ -323,6 +330,8 @@ def lib():
         l.sg_ew_vec_launches.restype = _ll
         l.sg_linear_group_scaled_launches.restype = _ll
         l.sg_fir_bias_act_launches.restype = _ll
+        l.sg_act_fir_launches.restype = _ll
+        l.sg_mbstd_launches.restype = _ll
         # SG_F32_MODE=bf16x3 | bf16x6: the generic engine's fp32 contractions process-wide on a split-precision path (functional.f32_mode is the scoped
         # form and says what each mode covers); default = exact fp32 MFMA
         f32_mode = {"bf16x3": 3, "bf16x6": 6}.get(os.environ.get("SG_F32_MODE", "exact"), 0)

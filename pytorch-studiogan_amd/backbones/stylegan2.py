@@ -18,7 +18,7 @@ Two things are computed differently from a layer-by-layer evaluation, both switc
   * every layer's style affine of a synthesis forward is ONE sg_linear_group_scaled launch (StyleAffineGroupFn) reading its row of ws in place
     (`grouped_styles`; per layer it is a gain multiply, a cast, a bias multiply and an addmm on a [N, w_dim] x [w_dim, C] problem);
   * the up = 2 layers run modulated_conv2d_act, whose FIR + noise + bias + activation tail is one launch (`fused_resample`).
-The discriminator (down = 2 convolutions, minibatch standard deviation) and the StyleGAN2 training loop are still to come."""
+The discriminator (down = 2 convolutions, minibatch standard deviation) is backbones/stylegan2_dis.py; the StyleGAN2 training loop is still to come."""
 import ctypes
 import math
 

@@ -10,7 +10,7 @@ constructor and forward argument lists, and the attribute names behind the state
 
 The convolution is style_ops.modulated_conv2d (csrc/modconv.hip), the activation style_ops.bias_act; the [N, w_dim] x [w_dim, C] affine is torch unless the
 caller hands the styles in (backbones/stylegan2.py computes all of a forward's in one launch). The mapping / synthesis networks are backbones/stylegan2.py;
-the discriminator and the StyleGAN2 training loop are still to come, and nothing of this file is registered in config_map.BACKBONES."""
+the discriminator is backbones/stylegan2_dis.py; the StyleGAN2 training loop is still to come, and nothing of this file is registered in config_map.BACKBONES."""
 import math
 
 import torch

@@ -59,7 +59,7 @@ def stylegan2_generator_args(y, mixed_precision=False):
     """Keyword arguments of `backbones.stylegan2.Generator` for a `MODEL.backbone: stylegan2` configuration, as the reference builds it (src/models/model.py:26-46):
     channel_base 32768 for CIFAR10 / CIFAR100 and for images of 512 and above, else 16384, channel_max 512; the generator is label-conditioned only under
     g_cond_mtd = cAdaIN; mixed precision = the 4 highest resolutions in low precision with the convolution outputs clamped to +-256. (`model_args` keeps refusing
-    the StyleGAN backbones: there is no discriminator or training loop for them yet.)"""
+    the StyleGAN backbones: there is no training loop for them yet.)"""
     import types
     M, D, S = dict(y.get("MODEL") or {}), dict(y.get("DATA") or {}), dict(y.get("STYLEGAN") or {})
     if M.get("backbone") != "stylegan2":
@@ -75,6 +75,28 @@ def stylegan2_generator_args(y, mixed_precision=False):
                 img_channels=D.get("img_channels", 3), MODEL=types.SimpleNamespace(**namespace), mapping_kwargs={"num_layers": S["mapping_network"]},
                 synthesis_kwargs={"channel_base": channel_base, "channel_max": 512, "num_fp16_res": 4 if mixed_precision else 0,
                                   "conv_clamp": 256 if mixed_precision else None})
+
+
+def stylegan2_discriminator_args(y, mixed_precision=False):
+    """Keyword arguments of `backbones.stylegan2_dis.Discriminator` for a `MODEL.backbone: stylegan2` configuration, as the reference builds it
+    (src/models/model.py:26-36, 65-85): the generator's channel_base rule; label-conditioned (c_dim = num_classes) under d_cond_mtd PD / SPD / 2C / D2DCE;
+    architecture and the minibatch-std group size from the STYLEGAN section; mixed precision as for the generator."""
+    import types
+    M, D, S = dict(y.get("MODEL") or {}), dict(y.get("DATA") or {}), dict(y.get("STYLEGAN") or {})
+    if M.get("backbone") != "stylegan2":
+        raise NotImplementedError(f"MODEL.backbone = {M.get('backbone')}: stylegan2_discriminator_args maps the stylegan2 discriminator only")
+    for key in ("d_architecture", "d_epilogue_mbstd_group_size"):
+        if S.get(key, _N) == _N:
+            raise NotImplementedError(f"STYLEGAN.{key} must be set for a stylegan2 discriminator")
+    img, name, ncls = D.get("img_size", 32), D.get("name", "CIFAR10"), D.get("num_classes", 10)
+    channel_base = 32768 if (img >= 512 or name in ("CIFAR10", "CIFAR100")) else 16384
+    M = {**_MODEL, **M}
+    namespace = {k: M[k] for k in ("info_type", "g_info_injection", "info_num_discrete_c", "info_num_conti_c", "info_dim_discrete_c", "backbone")}
+    return dict(c_dim=ncls if M["d_cond_mtd"] in ("PD", "SPD", "2C", "D2DCE") else 0, img_resolution=img, img_channels=D.get("img_channels", 3),
+                architecture=S["d_architecture"], channel_base=channel_base, channel_max=512, num_fp16_res=4 if mixed_precision else 0,
+                conv_clamp=256 if mixed_precision else None, cmap_dim=None, d_cond_mtd=M["d_cond_mtd"], aux_cls_type=M["aux_cls_type"],
+                d_embed_dim=M["d_embed_dim"], num_classes=ncls, normalize_d_embed=M["normalize_d_embed"], block_kwargs={}, mapping_kwargs={},
+                epilogue_kwargs={"mbstd_group_size": S["d_epilogue_mbstd_group_size"]}, MODEL=types.SimpleNamespace(**namespace))
 
 
 def model_namespace(y):
