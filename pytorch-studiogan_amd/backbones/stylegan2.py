@@ -26,10 +26,10 @@ import torch
 from torch import nn
 
 from .. import _lib as L
-from ..style_ops.bias_act import activation_funcs, bias_act
+from ..style_ops.bias_act import bias_act
 from ..style_ops.modulated_conv2d import modulated_conv2d
 from ..style_ops.upfirdn2d import setup_filter, upsample2d
-from .stylegan2_layers import FullyConnectedLayer, SynthesisLayer, ToRGBLayer, _conv_weight, _scaled
+from .stylegan2_layers import EqualizedConv2dBase, FullyConnectedLayer, SynthesisLayer, ToRGBLayer, _scaled
 
 ACT_DTYPE = torch.bfloat16      # what use_fp16 selects
 
@@ -38,34 +38,18 @@ def normalize_2nd_moment(x, dim=1, eps=1e-8):
     return x * (x.square().mean(dim=dim, keepdim=True) + eps).rsqrt()
 
 
-class Conv2dLayer(nn.Module):
+class Conv2dLayer(EqualizedConv2dBase):
     """Plain (unmodulated) equalised-lr convolution with optional 2x upsampling: the resnet architecture's skip path. The convolution is the modulated
     kernel with unit styles and no demodulation. Resampling order: a 1x1 kernel convolves first and upsamples the result through the low-pass
     (fewer pixels to convolve), a 3x3 kernel is the transposed stride-2 convolution followed by the low-pass, as in modulated_conv2d."""
 
     def __init__(self, in_channels, out_channels, kernel_size, bias=True, activation="linear", up=1, down=1, resample_filter=[1, 3, 3, 1], conv_clamp=None,
                  channels_last=False, trainable=True):
-        super().__init__()
         if down != 1:
             raise NotImplementedError(f"Conv2dLayer: down={down} is the discriminator's path, which is not implemented (down=1 only)")
         if kernel_size not in (1, 3) or up not in (1, 2):
             raise NotImplementedError(f"Conv2dLayer: kernel_size={kernel_size}, up={up} is not supported (1 or 3; 1 or 2)")
-        self.activation, self.up, self.down, self.conv_clamp = activation, up, down, conv_clamp
-        self.register_buffer("resample_filter", setup_filter(resample_filter))
-        self.padding = kernel_size // 2
-        self.weight_gain = 1.0 / math.sqrt(in_channels * kernel_size ** 2)
-        self.act_gain = activation_funcs[activation].def_gain
-        weight = _conv_weight(out_channels, in_channels, kernel_size, channels_last)
-        b = torch.zeros(out_channels) if bias else None
-        if trainable:
-            self.weight = weight
-            self.register_parameter("bias", None if b is None else nn.Parameter(b))
-        else:
-            self.register_buffer("weight", weight.detach())
-            if b is not None:
-                self.register_buffer("bias", b)
-            else:
-                self.bias = None
+        super().__init__(in_channels, out_channels, kernel_size, bias, activation, up, down, resample_filter, conv_clamp, channels_last, trainable)
 
     def forward(self, x, gain=1):
         ones = torch.ones((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)

@@ -26,43 +26,27 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
+from ..style_ops._fir_common import ACTS, MAX_TAPS, down2_padding
 from ..style_ops.act_fir import act_fir
-from ..style_ops.bias_act import activation_funcs, bias_act
+from ..style_ops.bias_act import bias_act
 from ..style_ops.conv2d_resample import conv2d_plain, conv2d_resample
-from ..style_ops.fir_bias_act import ACTS, MAX_TAPS
 from ..style_ops.minibatch_std import minibatch_std
 from ..style_ops.upfirdn2d import _get_filter_size, downsample2d, setup_filter
 from .stylegan2 import ACT_DTYPE, MappingNetwork
-from .stylegan2_layers import FullyConnectedLayer, _conv_weight, _scaled
+from .stylegan2_layers import EqualizedConv2dBase, FullyConnectedLayer, _scaled
 
 
-class DConv2dLayer(nn.Module):
+class DConv2dLayer(EqualizedConv2dBase):
     """The reference's Conv2dLayer for up = 1 (the generator's Conv2dLayer keeps refusing down = 2). forward(x, gain) is the whole layer; `raw` and `epilogue`
     are its two halves, which DiscriminatorBlock uses to move this layer's epilogue into the head of the next one."""
 
     def __init__(self, in_channels, out_channels, kernel_size, bias=True, activation="linear", up=1, down=1, resample_filter=[1, 3, 3, 1], conv_clamp=None,
                  channels_last=False, trainable=True):
-        super().__init__()
         if up != 1:
             raise NotImplementedError(f"DConv2dLayer: up={up} is the generator's path (backbones.stylegan2.Conv2dLayer)")
         if kernel_size not in (1, 3) or down not in (1, 2):
             raise NotImplementedError(f"DConv2dLayer: kernel_size={kernel_size}, down={down} is not supported (1 or 3; 1 or 2)")
-        self.activation, self.up, self.down, self.conv_clamp = activation, up, down, conv_clamp
-        self.register_buffer("resample_filter", setup_filter(resample_filter))
-        self.padding = kernel_size // 2
-        self.weight_gain = 1.0 / math.sqrt(in_channels * kernel_size ** 2)
-        self.act_gain = activation_funcs[activation].def_gain
-        weight = _conv_weight(out_channels, in_channels, kernel_size, channels_last)
-        b = torch.zeros(out_channels) if bias else None
-        if trainable:
-            self.weight = weight
-            self.register_parameter("bias", None if b is None else nn.Parameter(b))
-        else:
-            self.register_buffer("weight", weight.detach())
-            if b is not None:
-                self.register_buffer("bias", b)
-            else:
-                self.bias = None
+        super().__init__(in_channels, out_channels, kernel_size, bias, activation, up, down, resample_filter, conv_clamp, channels_last, trainable)
 
     def epilogue(self, gain=1):
         """what follows the convolution, as keyword arguments of bias_act / act_fir"""
@@ -86,13 +70,10 @@ class DConv2dLayer(nn.Module):
                 raise AssertionError("DConv2dLayer: this layer's resampling is not fused")
             return conv2d_resample(x, w, f=self.resample_filter, down=2, padding=self.padding, fused=False)
         k = self.weight.shape[2]
-        fw, fh = _get_filter_size(self.resample_filter)
-        p = self.padding
-        pad = [p + (fw - 1) // 2, p + (fw - 2) // 2, p + (fh - 1) // 2, p + (fh - 2) // 2]
         head = dict(head or {})
         if head.get("bias") is not None:
             head["bias"] = head["bias"].to(torch.float32)
-        x = act_fir(x, self.resample_filter, pad, down=2 if k == 1 else 1, filter_gain=filter_gain, **head)
+        x = act_fir(x, self.resample_filter, down2_padding(self.resample_filter, self.padding), down=2 if k == 1 else 1, filter_gain=filter_gain, **head)
         return conv2d_plain(x, w, 1 if k == 1 else 2)
 
     def finish(self, y, gain=1):
@@ -125,15 +106,13 @@ class DiscriminatorBlock(nn.Module):
             self.num_layers += 1
             return first_layer_idx + self.num_layers - 1 >= freeze_layers
 
-        common = {}
         if in_channels == 0 or architecture == "skip":
-            self.fromrgb = DConv2dLayer(img_channels, tmp_channels, kernel_size=1, activation=activation, trainable=trainable(), conv_clamp=conv_clamp, **common)
-        self.conv0 = DConv2dLayer(tmp_channels, tmp_channels, kernel_size=3, activation=activation, trainable=trainable(), conv_clamp=conv_clamp, **common)
+            self.fromrgb = DConv2dLayer(img_channels, tmp_channels, kernel_size=1, activation=activation, trainable=trainable(), conv_clamp=conv_clamp)
+        self.conv0 = DConv2dLayer(tmp_channels, tmp_channels, kernel_size=3, activation=activation, trainable=trainable(), conv_clamp=conv_clamp)
         self.conv1 = DConv2dLayer(tmp_channels, out_channels, kernel_size=3, activation=activation, down=2, trainable=trainable(),
-                                  resample_filter=resample_filter, conv_clamp=conv_clamp, **common)
+                                  resample_filter=resample_filter, conv_clamp=conv_clamp)
         if architecture == "resnet":
-            self.skip = DConv2dLayer(tmp_channels, out_channels, kernel_size=1, bias=False, down=2, trainable=trainable(), resample_filter=resample_filter,
-                                     **common)
+            self.skip = DConv2dLayer(tmp_channels, out_channels, kernel_size=1, bias=False, down=2, trainable=trainable(), resample_filter=resample_filter)
 
     def _head_fusable(self):
         return self.fused_down and self.conv1.fusable_head() and self.conv0.activation in ACTS

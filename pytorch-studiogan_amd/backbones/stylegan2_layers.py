@@ -33,6 +33,31 @@ def _scaled(value, gain):
     return None if value is None else value * gain
 
 
+class EqualizedConv2dBase(nn.Module):
+    """What the generator's Conv2dLayer and the discriminator's DConv2dLayer share: the equalised-lr weight and the bias, parameters or (Freeze-D, trainable=False)
+    buffers, the resample filter, and the gains, registered in the order the reference's state_dict lists them. Each subclass refuses what it does not serve
+    before it calls this constructor, and has its own forward."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, bias, activation, up, down, resample_filter, conv_clamp, channels_last, trainable):
+        super().__init__()
+        self.activation, self.up, self.down, self.conv_clamp = activation, up, down, conv_clamp
+        self.register_buffer("resample_filter", setup_filter(resample_filter))
+        self.padding = kernel_size // 2
+        self.weight_gain = 1.0 / math.sqrt(in_channels * kernel_size ** 2)
+        self.act_gain = activation_funcs[activation].def_gain
+        weight = _conv_weight(out_channels, in_channels, kernel_size, channels_last)
+        b = torch.zeros(out_channels) if bias else None
+        if trainable:
+            self.weight = weight
+            self.register_parameter("bias", None if b is None else nn.Parameter(b))
+        else:
+            self.register_buffer("weight", weight.detach())
+            if b is not None:
+                self.register_buffer("bias", b)
+            else:
+                self.bias = None
+
+
 class FullyConnectedLayer(nn.Module):
     def __init__(self, in_features, out_features, bias=True, activation="linear", lr_multiplier=1, bias_init=0):
         super().__init__()

@@ -13,31 +13,15 @@ import torch
 
 from .. import _lib as L
 from ..functional._base import _first_order_only
-from .bias_act import activation_funcs
-from .fir_bias_act import ACTS, filter_2d
-
-
-def _out_size(Hi, Wi, fh, fw, pad, down):
-    px0, px1, py0, py1 = pad
-    return (Hi + py0 + py1 - fh) // down + 1, (Wi + px0 + px1 - fw) // down + 1
+from ._fir_common import check_args, epilogue_args, epilogue_defaults, filter_2d, nhwc_out, out_size
 
 
 def act_fir_nhwc_raw(xh, f2d, pad, down=1, flip_filter=False, filter_gain=1.0, bias=None, act="linear", alpha=0.0, gain=1.0, clamp=-1.0):
     """one sg_act_fir_nhwc launch. xh: dense [N, Hi, Wi, C] fp32 / bf16 on the GPU; pad = (padx0, padx1, pady0, pady1); -> [N, Ho, Wo, C] of xh's dtype"""
-    L.require_gpu(xh.device)
-    if xh.dtype not in (torch.float32, torch.bfloat16):
-        raise NotImplementedError(f"act_fir: x of dtype {xh.dtype} is not supported (float32 / bfloat16)")
-    if not xh.is_contiguous():
-        raise AssertionError("act_fir: the kernel takes a dense NHWC tensor")
-    N, Hi, Wi, C = xh.shape
-    fh, fw = int(f2d.shape[0]), int(f2d.shape[1])
-    if Hi + pad[2] + pad[3] < fh or Wi + pad[0] + pad[1] < fw:
-        raise RuntimeError("act_fir: the padded image is smaller than the filter")
-    Ho, Wo = _out_size(Hi, Wi, fh, fw, pad, down)
-    y = torch.empty((N, Ho, Wo, C), dtype=xh.dtype, device=xh.device)
+    y, (N, Hi, Wi, C, fh, fw) = nhwc_out("act_fir", xh, f2d, pad, down)
     if y.numel():
-        L.call("sg_act_fir_nhwc", L.dt(xh), L.ptr(xh), L.ptr(f2d), L.ptr(y), L.ptr(bias), N, Hi, Wi, C, fh, fw, int(down), *pad, 1 if flip_filter else 0,
-               float(filter_gain), activation_funcs[act].cuda_idx, float(alpha), float(gain), float(clamp), L.stream())
+        L.call("sg_act_fir_nhwc", L.dt(xh), L.ptr(xh), L.ptr(f2d), L.ptr(y), L.ptr(bias), N, Hi, Wi, C, fh, fw, int(down),
+               *epilogue_args(pad, flip_filter, filter_gain, act, alpha, gain, clamp))
     return y
 
 
@@ -56,11 +40,11 @@ def act_fir_nhwc_bwd_raw(x_shape, xh, dyh, f2d, pad, down=1, flip_filter=False, 
     N, Hi, Wi, C = x_shape
     dx = torch.empty((N, Hi, Wi, C), dtype=dyh.dtype, device=dyh.device)
     fh, fw = int(f2d.shape[0]), int(f2d.shape[1])
-    if tuple(dyh.shape) != (N,) + _out_size(Hi, Wi, fh, fw, pad, down) + (C,):
+    if tuple(dyh.shape) != (N,) + out_size(Hi, Wi, fh, fw, pad, down) + (C,):
         raise AssertionError("act_fir: dy does not match the forward's output")
     if dx.numel():
-        L.call("sg_act_fir_nhwc_bwd", L.dt(dyh), L.ptr(xh), L.ptr(dyh), L.ptr(f2d), L.ptr(dx), L.ptr(bias), N, Hi, Wi, C, fh, fw, int(down), *pad,
-               1 if flip_filter else 0, float(filter_gain), activation_funcs[act].cuda_idx, float(alpha), float(gain), float(clamp), L.stream())
+        L.call("sg_act_fir_nhwc_bwd", L.dt(dyh), L.ptr(xh), L.ptr(dyh), L.ptr(f2d), L.ptr(dx), L.ptr(bias), N, Hi, Wi, C, fh, fw, int(down),
+               *epilogue_args(pad, flip_filter, filter_gain, act, alpha, gain, clamp))
     return dx
 
 
@@ -95,22 +79,8 @@ class ActFirFn(torch.autograd.Function):
 def act_fir(x, f, padding, down=1, bias=None, act="linear", alpha=None, gain=None, clamp=None, flip_filter=False, filter_gain=1.0):
     """x: [N, C, Hi, Wi], channels_last (a contiguous x is copied once), float32 / bfloat16 on the GPU. f: None, or a float32 filter of at most 4 x 4 taps.
     padding = [padx0, padx1, pady0, pady1]; down: 1 or 2. Returns the channels_last [N, C, Ho, Wo] result; alpha / gain default to the activation's."""
-    if not (isinstance(x, torch.Tensor) and x.dim() == 4):
-        raise AssertionError("act_fir: x must be a 4-D NCHW tensor")
-    if x.dtype not in (torch.float32, torch.bfloat16):
-        raise NotImplementedError(f"act_fir: x of dtype {x.dtype} is not supported (float32 / bfloat16)")
-    if act not in ACTS:
-        raise NotImplementedError(f"act_fir: act={act!r} is not supported ({' / '.join(ACTS)}; bias_act takes the others)")
+    check_args("act_fir", x, act, clamp, padding, bias)
     if down not in (1, 2):
         raise NotImplementedError(f"act_fir: down={down!r} is not supported (1 or 2; upfirdn2d takes the others)")
-    if clamp is not None and clamp < 0:
-        raise AssertionError("act_fir: clamp must be >= 0")
-    if len(padding) != 4:
-        raise AssertionError("act_fir: padding = [padx0, padx1, pady0, pady1]")
-    if bias is not None and not (isinstance(bias, torch.Tensor) and tuple(bias.shape) == (x.shape[1],)):
-        raise AssertionError(f"act_fir: bias must be a vector of {x.shape[1]} channels")
-    f2d = filter_2d(f, x.device)
-    spec = activation_funcs[act]
-    return ActFirFn.apply(x, f2d, bias, tuple(int(p) for p in padding), int(down), bool(flip_filter), float(filter_gain), act,
-                          float(spec.def_alpha if alpha is None else alpha), float(spec.def_gain if gain is None else gain),
-                          float(-1 if clamp is None else clamp))
+    return ActFirFn.apply(x, filter_2d(f, x.device), bias, tuple(int(p) for p in padding), int(down), bool(flip_filter), float(filter_gain), act,
+                          *epilogue_defaults(act, alpha, gain, clamp))

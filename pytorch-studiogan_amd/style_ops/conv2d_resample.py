@@ -19,8 +19,8 @@ import torch
 from .. import _lib as L
 from ..functional._base import _first_order_only, conv2d_raw, conv2d_wgrad_raw
 from . import upfirdn2d as _upfirdn2d
+from ._fir_common import MAX_TAPS, down2_padding
 from .act_fir import act_fir
-from .fir_bias_act import MAX_TAPS
 from .modulated_conv2d import _modconv_raw
 
 ENTRIES = ("sg_conv2d_fwd", "sg_modconv2d_fwd")
@@ -135,18 +135,11 @@ def conv2d_resample(x, w, f=None, up=1, down=1, padding=0, groups=1, flip_weight
         raise NotImplementedError(f"conv2d_resample: padding={padding} is not supported (padding = kernel_size // 2 = {k // 2})")
     if down == 1:
         return conv2d_plain(x, w, 1)
-    fw, fh = _upfirdn2d._get_filter_size(f)
-    px0, px1 = padding + (fw - down + 1) // 2, padding + (fw - down) // 2           # conv2d_resample.py:76-83
-    py0, py1 = padding + (fh - down + 1) // 2, padding + (fh - down) // 2
-    use_fused = fused and max(fw, fh) <= MAX_TAPS
-    if k == 1:
-        if use_fused:
-            x = act_fir(x, f, [px0, px1, py0, py1], down=2, flip_filter=flip_filter)
-        else:
-            x = _upfirdn2d.upfirdn2d(x, f, down=down, padding=[px0, px1, py0, py1], flip_filter=flip_filter)
-        return conv2d_plain(x, w, 1)
+    pad = down2_padding(f, padding)
+    use_fused = fused and max(_upfirdn2d._get_filter_size(f)) <= MAX_TAPS
+    fir_down = 2 if k == 1 else 1       # a 1x1 kernel decimates in the low-pass, a 3x3 kernel in the convolution
     if use_fused:
-        x = act_fir(x, f, [px0, px1, py0, py1], flip_filter=flip_filter)
+        x = act_fir(x, f, pad, down=fir_down, flip_filter=flip_filter)
     else:
-        x = _upfirdn2d.upfirdn2d(x, f, padding=[px0, px1, py0, py1], flip_filter=flip_filter)
-    return conv2d_plain(x, w, 2)
+        x = _upfirdn2d.upfirdn2d(x, f, down=fir_down, padding=pad, flip_filter=flip_filter)
+    return conv2d_plain(x, w, 1 if k == 1 else 2)

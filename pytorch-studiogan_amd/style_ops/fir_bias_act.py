@@ -14,41 +14,16 @@ import torch
 
 from .. import _lib as L
 from ..functional._base import _first_order_only
+from ._fir_common import ACTS, MAX_TAPS, check_args, epilogue_args, epilogue_defaults, filter_2d, nhwc_out, out_size  # noqa: F401  (ACTS, MAX_TAPS, filter_2d: this module's public names)
 from .bias_act import activation_funcs
-
-MAX_TAPS = 4
-ACTS = ("linear", "lrelu")
-
-
-def filter_2d(f, device):
-    """the filter constant of upfirdn2d.setup_filter (None, 1-D separable or 2-D) as the dense fp32 [fh][fw] table the kernel takes"""
-    if f is None:
-        return torch.ones((1, 1), dtype=torch.float32, device=device)
-    if not (isinstance(f, torch.Tensor) and f.dim() in (1, 2) and f.dtype == torch.float32):
-        raise AssertionError("fir_bias_act: the filter must be None or a float32 vector / matrix from upfirdn2d.setup_filter")
-    f2 = torch.outer(f, f) if f.dim() == 1 else f
-    if f2.shape[0] > MAX_TAPS or f2.shape[1] > MAX_TAPS:
-        raise NotImplementedError(f"fir_bias_act: a filter of {tuple(f2.shape)} taps is not supported (at most {MAX_TAPS} x {MAX_TAPS}; upfirdn2d takes the others)")
-    return f2.to(device).contiguous()
 
 
 def fir_nhwc_raw(xh, f2d, pad, flip_filter=False, filter_gain=1.0, noise=None, noise_stride=0, bias=None, act="linear", alpha=0.0, gain=1.0, clamp=-1.0):
     """one sg_fir_bias_act_nhwc launch. xh: dense [N, Hi, Wi, C] fp32 / bf16 on the GPU; pad = (padx0, padx1, pady0, pady1); -> [N, Ho, Wo, C] of xh's dtype"""
-    L.require_gpu(xh.device)
-    if xh.dtype not in (torch.float32, torch.bfloat16):
-        raise NotImplementedError(f"fir_bias_act: x of dtype {xh.dtype} is not supported (float32 / bfloat16)")
-    if not xh.is_contiguous():
-        raise AssertionError("fir_bias_act: the kernel takes a dense NHWC tensor")
-    N, Hi, Wi, C = xh.shape
-    fh, fw = int(f2d.shape[0]), int(f2d.shape[1])
-    px0, px1, py0, py1 = pad
-    Ho, Wo = Hi + py0 + py1 - fh + 1, Wi + px0 + px1 - fw + 1
-    if Ho < 1 or Wo < 1:
-        raise RuntimeError("fir_bias_act: the padded image is smaller than the filter")
-    y = torch.empty((N, Ho, Wo, C), dtype=xh.dtype, device=xh.device)
+    y, (N, Hi, Wi, C, fh, fw) = nhwc_out("fir_bias_act", xh, f2d, pad)
     if y.numel():
-        L.call("sg_fir_bias_act_nhwc", L.dt(xh), L.ptr(xh), L.ptr(f2d), L.ptr(y), L.ptr(noise), noise_stride, L.ptr(bias), N, Hi, Wi, C, fh, fw, px0, px1, py0, py1,
-               1 if flip_filter else 0, float(filter_gain), activation_funcs[act].cuda_idx, float(alpha), float(gain), float(clamp), L.stream())
+        L.call("sg_fir_bias_act_nhwc", L.dt(xh), L.ptr(xh), L.ptr(f2d), L.ptr(y), L.ptr(noise), noise_stride, L.ptr(bias), N, Hi, Wi, C, fh, fw,
+               *epilogue_args(pad, flip_filter, filter_gain, act, alpha, gain, clamp))
     return y
 
 
@@ -100,24 +75,11 @@ class FirBiasActFn(torch.autograd.Function):
 def fir_bias_act(x, f, padding, noise=None, bias=None, act="linear", alpha=None, gain=None, clamp=None, flip_filter=False, filter_gain=1.0):
     """x: [N, C, Hi, Wi], channels_last (a contiguous x is copied once), float32 / bfloat16 on the GPU. f: None, or a float32 filter of at most 4 x 4 taps.
     padding = [padx0, padx1, pady0, pady1]. Returns the channels_last [N, C, Ho, Wo] result; alpha / gain default to the activation's (bias_act's table)."""
-    if not (isinstance(x, torch.Tensor) and x.dim() == 4):
-        raise AssertionError("fir_bias_act: x must be a 4-D NCHW tensor")
-    if x.dtype not in (torch.float32, torch.bfloat16):
-        raise NotImplementedError(f"fir_bias_act: x of dtype {x.dtype} is not supported (float32 / bfloat16)")
-    if act not in ACTS:
-        raise NotImplementedError(f"fir_bias_act: act={act!r} is not supported ({' / '.join(ACTS)}; bias_act takes the others)")
-    if clamp is not None and clamp < 0:
-        raise AssertionError("fir_bias_act: clamp must be >= 0")
-    if len(padding) != 4:
-        raise AssertionError("fir_bias_act: padding = [padx0, padx1, pady0, pady1]")
-    N, C = x.shape[0], x.shape[1]
+    check_args("fir_bias_act", x, act, clamp, padding, bias)
+    N = x.shape[0]
     f2d = filter_2d(f, x.device)
-    Ho, Wo = x.shape[2] + padding[2] + padding[3] - f2d.shape[0] + 1, x.shape[3] + padding[0] + padding[1] - f2d.shape[1] + 1
+    Ho, Wo = out_size(x.shape[2], x.shape[3], f2d.shape[0], f2d.shape[1], padding)
     if noise is not None and not (isinstance(noise, torch.Tensor) and tuple(noise.shape) in ((N, 1, Ho, Wo), (Ho, Wo))):
         raise NotImplementedError(f"fir_bias_act: noise must be [N, 1, {Ho}, {Wo}] per sample or one shared [{Ho}, {Wo}] plane")
-    if bias is not None and not (isinstance(bias, torch.Tensor) and tuple(bias.shape) == (C,)):
-        raise AssertionError(f"fir_bias_act: bias must be a vector of {C} channels")
-    spec = activation_funcs[act]
     return FirBiasActFn.apply(x, f2d, noise, bias, tuple(int(p) for p in padding), bool(flip_filter), float(filter_gain), act,
-                              float(spec.def_alpha if alpha is None else alpha), float(spec.def_gain if gain is None else gain),
-                              float(-1 if clamp is None else clamp))
+                              *epilogue_defaults(act, alpha, gain, clamp))

@@ -207,7 +207,8 @@ def modulated_conv2d_act(x, weight, styles, noise=None, up=1, down=1, padding=0,
     accumulator, channels-last in and out. noise and bias enter in fp32 there, where the separate operators round both to x's dtype and round the activation
     after the FIR and after the noise. act: 'linear' or 'lrelu' at up = 2. First-order gradients only."""
     from .bias_act import bias_act
-    from .fir_bias_act import ACTS, MAX_TAPS, fir_bias_act
+    from ._fir_common import ACTS, MAX_TAPS
+    from .fir_bias_act import fir_bias_act
     N, C, H, W, Cout, k = _validate(x, weight, styles, noise, up, down, padding, resample_filter)
     fw, fh = _upfirdn2d._get_filter_size(resample_filter)
     if up == 2 and (act not in ACTS or max(fw, fh) > MAX_TAPS):

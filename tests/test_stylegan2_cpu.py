@@ -1,16 +1,21 @@
 """Host-side checks of the StyleGAN2 generator networks (backbones/stylegan2.py): the fixture tests/golden/stylegan2_gen.npz against the restatement that
 wrote its expectation, the state_dict contract with the reference, the ws bookkeeping, truncation and the w_avg update on the mapping network's torch path,
-the refusals, the table of the grouped style affines, and config_map.stylegan2_generator_args over the reference's configuration files. No GPU."""
+the refusals, the table of the grouped style affines, config_map.stylegan2_generator_args over the reference's configuration files, and the fused layer tail
+(sg_fir_bias_act_nhwc with its autograd function) through the kernel-source interpreter. No GPU."""
 import ctypes
 import glob
 import inspect
 import os
+import sys
 
 import pytest
 import torch
 
-import modconv_ref as R
-import stylegan2_ref as S
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hipemu"))
+import emu  # noqa: E402
+import modconv_ref as R  # noqa: E402
+import stylegan2_dis_ref as D  # noqa: E402
+import stylegan2_ref as S  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -198,3 +203,87 @@ def test_generator_args_of_every_stylegan2_config():
     assert base[("ImageNet", 128)] == 16384 and base[("CIFAR100", 32)] == 32768
     with pytest.raises(NotImplementedError):
         config_map.stylegan2_generator_args({"MODEL": {"backbone": "big_resnet"}})
+
+
+# ---- the layer tail through the interpreter (tests/hipemu): the store-side epilogue of the kernel whose load side test_stylegan2_dis_cpu.py runs ---------------
+emulated = pytest.mark.skipif(not emu.available(), reason="host clang++ of the ROCm toolchain not found")
+FIR_SHAPES = {"vec": (3, 12, 9, 9), "scalar": (2, 13, 10, 6)}       # (N, C, H, W): whole fp32 vectors (the scalar path in bf16) / the scalar path; odd extents
+FIR_CASES = {"sample-clamp": ("sample", "clamp"), "plane-noclamp": ("plane", "noclamp"), "plain": (None, "plain")}     # (noise, epilogue of D.HEAD_EPI)
+FIR_PAD, FIR_GAIN, FIR_MARGIN = (1, 1, 1, 1), 4.0, 1e-2
+
+
+def _fir_misses(pre, e):
+    """where the fp64 pre-activation sits on the leaky ReLU's kink, or its unclamped output within FIR_MARGIN (relative) of the clamp"""
+    miss = pre == 0
+    if e["clamp_"] is not None:
+        miss = miss | (((D.bias_act(pre, None, e["act"], e["gain"]).abs() - e["clamp_"]).abs()) <= FIR_MARGIN * e["clamp_"])
+    return miss
+
+
+def _fir_inputs(shape, noise, epi):
+    """x, noise and gy on the 2^-6 grid, bias on the grid + 2^-7, drawn as stylegan2_dis_ref.head_inputs draws them from one fixed seed. A draw alone does not
+    clear the margins the test asserts: of the 2304 outputs of the `vec` shape about nine land within 1e-2 of the clamp, and none of 6000 seeds had none. So
+    where the fp64 reference misses a margin, that noise value moves by the next multiple of 1/16 (still on the grid) under which every output it feeds holds."""
+    N, C, H, W = FIR_SHAPES[shape]
+    g = torch.Generator().manual_seed(5200)
+    q = lambda *s, scale=1.0: (torch.randn(*s, generator=g, dtype=torch.float64) * scale * 64).round().clamp(-192, 192) / 64      # noqa: E731
+    x = q(N, C, H, W)
+    bias = q(C, scale=0.5).clamp(-126 / 64, 126 / 64) + 2.0 ** -7
+    Ho, Wo = D.out_hw(H, W, FIR_PAD, 1)
+    gy = q(N, C, Ho, Wo)
+    if noise is None:
+        return x, bias, None, gy
+    nz0 = q(N, 1, Ho, Wo) if noise == "sample" else q(Ho, Wo)
+    core = D.fir(x, R.low_pass().double(), FIR_PAD, gain=FIR_GAIN) + bias.reshape(1, -1, 1, 1)
+    over = (1,) if noise == "sample" else (0, 1)        # the outputs one noise value feeds
+    nz = nz0
+    for k in (1, -1, 2, -2, 3, -3):
+        miss = _fir_misses(core + nz, D.HEAD_EPI[epi]).any(dim=over, keepdim=noise == "sample")
+        nz = torch.where(miss, nz0 + k / 16, nz)
+    return x, bias, nz, gy
+
+
+@emulated
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("case", list(FIR_CASES))
+@pytest.mark.parametrize("shape", list(FIR_SHAPES))
+def test_fir_bias_act_through_the_interpreter(shape, case, dtype):
+    """fir_bias_act (forward, dx, dnoise through sg_modconv_reduce, dbias) on the kernel sources against fp64 clamp(gain * lrelu(fir(x) + noise + bias)), at the
+    tolerances of the head's interpreter test; the plain mode IS upfirdn2d on the NCHW copy, forward and adjoint, bit for bit"""
+    import fullemu
+    from studiogan_amd.style_ops.fir_bias_act import fir_bias_act
+    from studiogan_amd.style_ops.upfirdn2d import upfirdn2d
+    noise, epi = FIR_CASES[case]
+    e = D.HEAD_EPI[epi]
+    f = R.low_pass()
+    tol = 2e-5 if dtype == torch.float32 else 1e-2
+    x, bias, nz, gy = _fir_inputs(shape, noise, epi)
+    leaves = {k: v.clone().requires_grad_(True) for k, v in (("x", x), ("noise", nz), ("bias", bias if e["bias"] else None)) if v is not None}
+    pre = D.fir(leaves["x"], f.double(), FIR_PAD, gain=FIR_GAIN)
+    if "noise" in leaves:
+        pre = pre + leaves["noise"]
+    if "bias" in leaves:
+        pre = pre + leaves["bias"].reshape(1, -1, 1, 1)
+    if e["act"] == "lrelu":     # the two margins, on every element of the reference
+        assert float(pre.detach().abs().min()) > 0
+    if e["clamp_"] is not None:
+        a = D.bias_act(pre.detach(), None, e["act"], e["gain"]).abs()
+        assert float(((a - e["clamp_"]).abs() / e["clamp_"]).min()) > FIR_MARGIN and bool((a > e["clamp_"]).any()), "too near the clamp, or it does not bite"
+    y64 = D.bias_act(pre, None, e["act"], e["gain"], e["clamp_"])
+    g64 = dict(zip(leaves, torch.autograd.grad(y64, list(leaves.values()), gy)))
+    with fullemu.Installed() as E:
+        dev = {k: (v.to(dtype).contiguous(memory_format=torch.channels_last) if k == "x" else v.float()).detach().requires_grad_(True) for k, v in leaves.items()}
+        xd = dev["x"]
+        n0, h0 = E.lib.sg_fir_bias_act_launches(), E.lib.sg_act_fir_launches()
+        y = fir_bias_act(xd, f, list(FIR_PAD), noise=dev.get("noise"), bias=dev.get("bias"), act=e["act"], gain=e["gain"], clamp=e["clamp_"], filter_gain=FIR_GAIN)
+        y.backward(gy.to(dtype))
+        assert E.lib.sg_fir_bias_act_launches() - n0 == 2 and E.lib.sg_act_fir_launches() == h0       # forward + data gradient, the tail's entry
+        assert y.dtype == dtype and y.is_contiguous(memory_format=torch.channels_last) and tuple(y.shape) == tuple(y64.shape)
+        assert _err(y.detach(), y64.detach()) <= tol, (shape, case)
+        for k, v in dev.items():
+            assert tuple(v.grad.shape) == tuple(g64[k].shape) and _err(v.grad, g64[k]) <= tol, (shape, case, k)
+        if epi == "plain":
+            xn = x.to(dtype).requires_grad_(True)
+            yu = upfirdn2d(xn, f, padding=list(FIR_PAD), gain=FIR_GAIN)
+            yu.backward(gy.to(dtype))
+            assert torch.equal(yu, y.detach().contiguous()) and torch.equal(xn.grad, xd.grad.contiguous())
