@@ -642,7 +642,14 @@ int sg_act_fir_nhwc(int dtype, const void* x, const float* f, void* y, const flo
 int sg_act_fir_nhwc_bwd(int dtype, const void* x, const void* dy, const float* f, void* dx, const float* bias, int N, int Hi, int Wi, int C, int fh,
                         int fw, int down, int padx0, int padx1, int pady0, int pady1, int flip_filter, float filter_gain, int act, float alpha,
                         float gain, float clamp, sg_stream_t s);
-long long sg_act_fir_launches(void);                       /* forward + backward launches so far */
+/* sg_act_fir_nhwc_gate: the backward of sg_act_fir_nhwc_bwd with respect to dy (second order). The FORWARD's arguments, v [N][Hi][Wi][C] (the cotangent on
+ * dx) in place of x, and the forward's raw x for the gate:   y [N][Ho][Wo][C] = FIR( v * da/dx(x + bias) ), decimated; da/dx = gain (gain * alpha on the
+ * negative side of lrelu), 0 where the forward clamped, evaluated as the _bwd launch evaluates it and only inside the image. x may be NULL when there is no
+ * gate; the launch is then the plain FIR of v, bit for bit. The gradients with respect to x and bias are zero (a is piecewise linear). */
+int sg_act_fir_nhwc_gate(int dtype, const void* v, const void* x, const float* f, void* y, const float* bias, int N, int Hi, int Wi, int C, int fh,
+                         int fw, int down, int padx0, int padx1, int pady0, int pady1, int flip_filter, float filter_gain, int act, float alpha,
+                         float gain, float clamp, sg_stream_t s);
+long long sg_act_fir_launches(void);                       /* forward + backward + gate launches so far */
 /* sg_mbstd_fwd / sg_mbstd_bwd (csrc/mbstd.hip): the minibatch standard deviation layer, one launch each. x: fp32 [N][H][W] pixels of pitch ldx >= C;
  * G samples per group (sample g * (N / G) + m is in group m), F statistics channels over slices of C / F channels:
  *   out [N][H][W][C + F] dense: out[..., :C] = x, out[n][h][w][C + f] = mean_{j,h,w} sqrt(var_g(x) + 1e-8)   (biased variance, two-pass)
@@ -653,6 +660,13 @@ long long sg_act_fir_launches(void);                       /* forward + backward
 int sg_mbstd_splits(int N, int H, int W, int C, int G, int F);
 int sg_mbstd_fwd(const float* x, int ldx, float* out, float* part, unsigned* tickets, int N, int H, int W, int C, int G, int F, sg_stream_t s);
 int sg_mbstd_bwd(const float* x, int ldx, const float* dout, float* dx, int N, int H, int W, int C, int G, int F, sg_stream_t s);
+/* sg_mbstd_bwd2: the backward of sg_mbstd_bwd (second order), one launch. v [N][H][W][C] dense: the cotangent on dx; x and dout: the arguments of the
+ * backward. With c_g = x_g - mean_g x, sigma = sqrt(var + 1e-8), P = (C / F) H W and dot = sum_g v_g c_g per element:
+ *   d_dout [N][H][W][C + F]: [..., :C] = v,  [n][h][w][C + f] = sum_{j,h,w} dot / (G sigma P)        (one scalar per pair, broadcast)
+ *   d_x    [N][H][W][C]    = dS / (G P) * ( (v - mean_g v) / sigma - c dot / (G sigma^3) )
+ * part / tickets as for sg_mbstd_fwd (the pair's scalar is handed over the same way). */
+int sg_mbstd_bwd2(const float* x, int ldx, const float* dout, const float* v, float* d_dout, float* d_x, float* part, unsigned* tickets, int N, int H, int W,
+                  int C, int G, int F, sg_stream_t s);
 long long sg_mbstd_launches(void);
 
 /* ---- differentiable augmentations in front of the discriminator and the consistency regularisers' loss -----------------------

@@ -267,10 +267,12 @@ _PROTOS = {
     "sg_fir_bias_act_launches": [],                        # returns a count
     "sg_act_fir_nhwc": [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp],
     "sg_act_fir_nhwc_bwd": [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp],
+    "sg_act_fir_nhwc_gate": [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp],
     "sg_act_fir_launches": [],                             # returns a count
     "sg_mbstd_splits": [_i, _i, _i, _i, _i, _i],           # returns a count (call through lib(), not call())
     "sg_mbstd_fwd": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "sg_mbstd_bwd": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "sg_mbstd_bwd2": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "sg_mbstd_launches": [],                               # returns a count
     "sg_augment_work_floats": [C.POINTER(AugDesc)],      # returns a count (call through lib(), not call())
     "sg_augment_fwd": [C.POINTER(AugDesc), _vp, _vp, _vp, _vp],

@@ -19,7 +19,8 @@ What is computed differently from a layer-by-layer evaluation (`fused_down`, swi
 ONE sg_act_fir_nhwc launch (style_ops/act_fir.py) that applies conv0's bias, lrelu, gain and clamp to each value as it loads it into the low-pass: the activated
 full-resolution map, the largest tensor of the block, is never stored, and nothing changes layout between the two convolutions. The resnet skip's decimating
 low-pass is a plain launch of the same kernel with the sqrt 1/2 of that half folded into the filter gain. With fused_down=False every layer is
-conv2d_resample -> bias_act, the FIR through upfirdn2d on NCHW copies. First-order gradients only (no R1 through this network yet)."""
+conv2d_resample -> bias_act, the FIR through upfirdn2d on NCHW copies. Second-order gradients (R1: losses.stylegan_cal_r1_reg)
+exist inside style_ops.second_order() and are refused outside it."""
 import math
 
 import torch

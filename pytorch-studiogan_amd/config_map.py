@@ -99,6 +99,25 @@ def stylegan2_discriminator_args(y, mixed_precision=False):
                 epilogue_kwargs={"mbstd_group_size": S["d_epilogue_mbstd_group_size"]}, MODEL=types.SimpleNamespace(**namespace))
 
 
+def stylegan2_r1_args(y):
+    """The lazy R1 regulariser of a `MODEL.backbone: stylegan2` configuration and what it does to the discriminator's Adam (reference src/config.py:540-550):
+    dict(r1_lambda, d_reg_interval, r1_place, lr, betas), lr and betas rescaled by d_ratio = d_reg_interval / (d_reg_interval + 1) (1 at an interval of 1)."""
+    M, Ls, O, S = dict(y.get("MODEL") or {}), {**_LOSS, **dict(y.get("LOSS") or {})}, {**_OPT, **dict(y.get("OPTIMIZATION") or {})}, dict(y.get("STYLEGAN") or {})
+    if M.get("backbone") != "stylegan2":
+        raise NotImplementedError(f"MODEL.backbone = {M.get('backbone')}: stylegan2_r1_args maps the stylegan2 discriminator only")
+    if not Ls["apply_r1_reg"]:
+        raise NotImplementedError("LOSS.apply_r1_reg must be set: stylegan2_r1_args maps the R1 regulariser")
+    if Ls["r1_lambda"] == _N or Ls["r1_place"] not in ("inside_loop", "outside_loop"):
+        raise NotImplementedError("LOSS.r1_lambda must be set and LOSS.r1_place one of inside_loop / outside_loop")
+    interval = S.get("d_reg_interval", _N)
+    if interval == _N:
+        raise NotImplementedError("STYLEGAN.d_reg_interval must be set for the lazy R1 regulariser")
+    if O["type_"] != "Adam":
+        raise NotImplementedError(f"OPTIMIZATION.type_ = {O['type_']}: the reference rescales Adam only")
+    ratio = interval / (interval + 1) if interval != 1 else 1
+    return dict(r1_lambda=Ls["r1_lambda"], d_reg_interval=interval, r1_place=Ls["r1_place"], lr=O["d_lr"] * ratio, betas=[O["beta1"] ** ratio, O["beta2"] ** ratio])
+
+
 def model_namespace(y):
     import types
     M = sections(y)[0]

@@ -31,6 +31,12 @@
 // caller derives (upfirdn2d.py); da/dx is re-evaluated from the kept x and bias (gain or gain * alpha, 0 where the forward clamped). One thread per dx vector,
 // the polyphase tap loops written as k_upfirdn2d writes them (bit-identical with no gate); dy is a quarter of dx at down = 2 and its 2 x 2 reads per output
 // are shared between neighbouring threads through the cache.
+//
+// sg_act_fir_nhwc_gate: the backward of THAT launch with respect to dy (second order, R1 through the discriminator). dx = FIR^T(dy) * m(x) is linear in dy, so
+// a cotangent v on dx gives d_dy = FIR(v * m(x + bias)), decimated: the forward's strip walk with the epilogue on the load side replaced by a gate, m = da/dx
+// evaluated from the kept raw x exactly as k_act_fir_nhwc_bwd evaluates it (the same expressions in the same order, so the two passes agree on every
+// element). v takes the place of x; x travels through the dy slot of FirArgs and costs one more vector of loads per tap column, issued with v's before the
+// first gate is evaluated. a is piecewise linear: d_x and d_bias are zero. With no gate x is never read and the launch is the plain FIR bit for bit.
 #include "common.h"
 #include "../../include/sgamd.h"
 
@@ -38,8 +44,8 @@ static long long g_fir_launches = 0, g_act_fir_launches = 0;
 extern "C" long long sg_fir_bias_act_launches() { return __atomic_load_n(&g_fir_launches, __ATOMIC_RELAXED); }
 extern "C" long long sg_act_fir_launches() { return __atomic_load_n(&g_act_fir_launches, __ATOMIC_RELAXED); }
 
-enum FirMode { FIR_TAIL, FIR_HEAD, FIR_HEAD_BWD };      // the three entry points
-enum { EPI_STORE, EPI_LOAD };                           // the side of the forward kernel's epilogue
+enum FirMode { FIR_TAIL, FIR_HEAD, FIR_HEAD_BWD, FIR_HEAD_GATE };      // the four entry points
+enum { EPI_STORE, EPI_LOAD, EPI_LOAD_GATE };            // the side of the forward kernel's epilogue; LOAD_GATE: the second-order pass of the head (below)
 
 struct FirArgs {
   const void* x; const float* f; void* y; const float* noise; const float* bias; const void* dy;
@@ -92,6 +98,17 @@ __device__ __forceinline__ float fir_act(float v, A a) {
   return v;
 }
 
+// g * da/dx at pre-activation v (bias included): the side of the leaky ReLU, the gain, and zero where the forward clamped. One statement for the first-order
+// backward (g = the adjoint FIR of dy) and the second-order gate (g = the cotangent on dx), so that both passes take the same decision on every element.
+__device__ __forceinline__ float fir_gate(float g, float v, const FirArgs& a) {
+  const bool pos = a.act != 3 || v > 0.f;
+  const float yv = (pos ? v : v * a.alpha) * a.gain;
+  g = pos ? g : g * a.alpha;
+  g *= a.gain;
+  if (a.clamp >= 0.f && !(yv > -a.clamp && yv < a.clamp)) g = 0.f;
+  return g;
+}
+
 // strip height of the row-walking kernel: as tall as leaves the chip ~half a million threads (the rows a strip re-reads from its neighbour are (fh - 1) / TY
 // of the input); -> workgroups of 256 threads for per_row threads per strip
 static unsigned fir_strip_grid(long long per_row, int Ho, int& TY, int& strips) {
@@ -104,7 +121,8 @@ static unsigned fir_strip_grid(long long per_row, int Ho, int& TY, int& strips) 
 }
 
 // SIDE = EPI_STORE: noise, bias, act, gain, clamp on the accumulator as it is stored (a.gate unused: every piece has its own test). SIDE = EPI_LOAD: bias, act,
-// gain, clamp on each loaded value when a.gate (a.noise unused).
+// gain, clamp on each loaded value when a.gate (a.noise unused). SIDE = EPI_LOAD_GATE: each loaded value of a.x times da/dx at the same element of a.dy (the
+// forward's raw input) when a.gate.
 template <typename T, int V, int DOWN, int SIDE>
 __global__ __launch_bounds__(256) void k_fir_nhwc(FirArgs a) {
   constexpr int NACC = 4 / DOWN;      // output rows one input row reaches
@@ -148,6 +166,29 @@ __global__ __launch_bounds__(256) void k_fir_nhwc(FirArgs a) {
           else {
 #pragma unroll
             for (int e = 0; e < V; e++) xv[fx][e] = 0.f;
+          }
+        }
+        if constexpr (SIDE == EPI_LOAD_GATE) {
+          if (a.gate && rowin) {
+            const T* rn = (const T*)a.dy + (long long)n * a.Hi * a.Wi * a.C + c0;
+            float rv[4][V];
+#pragma unroll
+            for (int fx = 0; fx < 4; fx++) {      // (the raw row's loads join the cotangent's in flight; a tap outside the image keeps its zero)
+              const int ix = ix0 + fx;
+              if (fx >= dx && ix >= 0 && ix < a.Wi) load_f<T, V>(rn + ((long long)iy * a.Wi + ix) * a.C, rv[fx]);
+              else {
+#pragma unroll
+                for (int e = 0; e < V; e++) rv[fx][e] = 1.f;
+              }
+            }
+#pragma unroll
+            for (int fx = 0; fx < 4; fx++) {
+              const int ix = ix0 + fx;
+              if (fx >= dx && ix >= 0 && ix < a.Wi) {
+#pragma unroll
+                for (int e = 0; e < V; e++) xv[fx][e] = fir_gate(xv[fx][e], rv[fx][e] + bv[e], a);
+              }
+            }
           }
         }
         if constexpr (SIDE == EPI_LOAD) {
@@ -251,15 +292,7 @@ __global__ __launch_bounds__(256) void k_act_fir_nhwc_bwd(FirArgs a) {
       float xv[V];
       load_f<T, V>((const T*)a.x + off, xv);
 #pragma unroll
-      for (int e = 0; e < V; e++) {
-        const float v = xv[e] + (a.bias ? a.bias[c0 + e] : 0.f);
-        const bool pos = a.act != 3 || v > 0.f;
-        const float yv = (pos ? v : v * a.alpha) * a.gain;
-        float g = pos ? acc[e] : acc[e] * a.alpha;
-        g *= a.gain;
-        if (a.clamp >= 0.f && !(yv > -a.clamp && yv < a.clamp)) g = 0.f;
-        acc[e] = g;
-      }
+      for (int e = 0; e < V; e++) acc[e] = fir_gate(acc[e], xv[e] + (a.bias ? a.bias[c0 + e] : 0.f), a);
     }
     *(vec_t<T, V>*)((T*)a.y + off) = pack_f<T, V>(acc);
   }
@@ -267,6 +300,7 @@ __global__ __launch_bounds__(256) void k_act_fir_nhwc_bwd(FirArgs a) {
 
 template <typename T, int V, int DOWN> static void fir_launch_v(const FirArgs& a, FirMode mode, unsigned blocks, hipStream_t st) {
   if (mode == FIR_HEAD_BWD) hipLaunchKernelGGL((k_act_fir_nhwc_bwd<T, V, DOWN>), dim3(blocks), dim3(256), 0, st, a);
+  else if (mode == FIR_HEAD_GATE) hipLaunchKernelGGL((k_fir_nhwc<T, V, DOWN, EPI_LOAD_GATE>), dim3(blocks), dim3(256), 0, st, a);
   else if (mode == FIR_HEAD) hipLaunchKernelGGL((k_fir_nhwc<T, V, DOWN, EPI_LOAD>), dim3(blocks), dim3(256), 0, st, a);
   else if constexpr (DOWN == 1) hipLaunchKernelGGL((k_fir_nhwc<T, V, 1, EPI_STORE>), dim3(blocks), dim3(256), 0, st, a);      // (the tail has no down = 2)
 }
@@ -287,7 +321,8 @@ template <typename T, int DOWN> static void fir_launch(FirArgs& a, FirMode mode,
   else fir_launch_v<T, 1, DOWN>(a, mode, blocks, st);
 }
 
-// validation, argument set-up and launch of all three entry points (the tail: down = 1, dy = NULL; the head: noise = NULL; out = y, or dx of the backward)
+// validation, argument set-up and launch of all four entry points (the tail: down = 1, dy = NULL; the head: noise = NULL; out = y, or dx of the backward; the
+// gate: x = the cotangent, dy = the forward's raw input)
 static int fir_run(const char* who, FirMode mode, int dtype, const void* x, const void* dy, const float* f, void* out, const float* noise, long long noise_stride,
                    const float* bias, int N, int Hi, int Wi, int C, int fh, int fw, int down, int padx0, int padx1, int pady0, int pady1, int flip_filter,
                    float filter_gain, int act, float alpha, float gain, float clamp, hipStream_t st) {
@@ -306,7 +341,7 @@ static int fir_run(const char* who, FirMode mode, int dtype, const void* x, cons
   FIR_CHECK(Ho < (1 << 24) && Wo < (1 << 24), "image extent or padding too large");
   FIR_CHECK(!noise || noise_stride == 0 || noise_stride >= Ho * Wo, "noise_stride must be 0 (one shared plane) or >= Ho * Wo");
   const bool gate = bias || act != 1 || gain != 1.f || clamp >= 0.f;
-  FIR_CHECK(mode == FIR_HEAD_BWD ? (dy && (x || !gate)) : x != nullptr, "bad tensor arguments");
+  FIR_CHECK(mode == FIR_HEAD_BWD ? (dy && (x || !gate)) : mode == FIR_HEAD_GATE ? (x && (dy || !gate)) : x != nullptr, "bad tensor arguments");
 #undef FIR_CHECK
   FirArgs a;
   a.x = x; a.f = f; a.y = out; a.noise = noise; a.bias = bias; a.dy = dy; a.noise_stride = noise ? noise_stride : 0;
@@ -342,5 +377,12 @@ extern "C" int sg_act_fir_nhwc_bwd(int dtype, const void* x, const void* dy, con
                                    int fw, int down, int padx0, int padx1, int pady0, int pady1, int flip_filter, float filter_gain, int act, float alpha,
                                    float gain, float clamp, sg_stream_t s) {
   return fir_run("sg_act_fir_nhwc_bwd", FIR_HEAD_BWD, dtype, x, dy, f, dx, nullptr, 0, bias, N, Hi, Wi, C, fh, fw, down, padx0, padx1, pady0, pady1, flip_filter,
+                 filter_gain, act, alpha, gain, clamp, (hipStream_t)s);
+}
+
+extern "C" int sg_act_fir_nhwc_gate(int dtype, const void* v, const void* x, const float* f, void* y, const float* bias, int N, int Hi, int Wi, int C, int fh,
+                                    int fw, int down, int padx0, int padx1, int pady0, int pady1, int flip_filter, float filter_gain, int act, float alpha,
+                                    float gain, float clamp, sg_stream_t s) {
+  return fir_run("sg_act_fir_nhwc_gate", FIR_HEAD_GATE, dtype, v, x, f, y, nullptr, 0, bias, N, Hi, Wi, C, fh, fw, down, padx0, padx1, pady0, pady1, flip_filter,
                  filter_gain, act, alpha, gain, clamp, (hipStream_t)s);
 }

@@ -9,12 +9,37 @@ from .. import comm as _comm
 from ..bank import ensure_grad
 
 
+# The StyleGAN2 discriminator's operators have a differentiable backward (R1), but only inside style_ops.second_order(): a bare create_graph=True through them
+# keeps raising, so that a caller who did not ask for the heavier graph (kept cotangents, grad-functions instead of in-place launches) never gets it silently.
+_SECOND_ORDER = [0]                 # nesting depth of second_order(); process-wide
+_SECOND_ORDER_LIFTS = ("act_fir", "conv2d_resample", "minibatch_std")
+
+
+class second_order:
+    """with style_ops.second_order(): torch.autograd.grad(..., create_graph=True) through act_fir, conv2d_plain / conv2d_resample and minibatch_std records a
+    differentiable backward (the reference wraps the same call of its R1 regulariser in conv2d_gradfix.no_weight_gradients()). The graph recorded inside stays
+    valid outside: penalty.backward() needs no context. Process-wide, re-entrant, restored on exit; every other first-order operator keeps refusing."""
+
+    def __enter__(self):
+        _SECOND_ORDER[0] += 1
+        return self
+
+    def __exit__(self, *exc):
+        _SECOND_ORDER[0] -= 1
+        return False
+
+
 def _first_order_only(name):
-    """Functions without a differentiable backward refuse create_graph=True instead of silently cutting the graph."""
+    """Functions without a differentiable backward refuse create_graph=True instead of silently cutting the graph. Returns True where the caller has a
+    differentiable route and is to take it (one of _SECOND_ORDER_LIFTS inside second_order()), False when no graph is being recorded."""
     if torch.is_grad_enabled():
+        if _SECOND_ORDER[0] > 0 and name in _SECOND_ORDER_LIFTS:
+            return True
         raise NotImplementedError(name + ": no differentiable backward (create_graph=True). Second-order passes exist for the discriminator's conv / BN / pooling / "
                                          "self-attention / head path (gradient penalties, R1) and for the ResNet / BigGAN / BigGAN-Deep generators incl. conditional "
-                                         "batch norm (latent optimisation); not for third order, nor for the DCGAN generator's transposed convolutions")
+                                         "batch norm (latent optimisation); not for third order, nor for the DCGAN generator's transposed convolutions. The "
+                                         "StyleGAN2 discriminator's operators (" + ", ".join(_SECOND_ORDER_LIFTS) + ") record theirs inside style_ops.second_order()")
+    return False
 
 
 def _param_grad_wanted(*params):
@@ -326,4 +351,4 @@ def gemm_dgrad_rows(w_ptr, dy, dx, B, K, O):
     return dx
 
 
-__all__ = ['L', 'zeros_small', 'zeros_like_small', '_BN_FUSED_STATS', '_CBN_MERGED', '_DGRAD_SPLITK', '_SEQ', '_STATS_OFFER', '_c', '_comm', '_first_order_only', '_offer_stats', '_param_grad_wanted', '_take_stats', '_tick', 'conv2d_q_raw', 'conv2d_q_wgrad_raw', 'conv2d_raw', 'conv2d_skip_raw', 'conv2d_wgrad_raw', 'dist', 'ensure_grad', 'f32_mode', 'gemm_dgrad_rows', 'gemm_raw', 'os', 'quad_pack_raw', 'torch']
+__all__ = ['L', 'zeros_small', 'zeros_like_small', '_BN_FUSED_STATS', '_CBN_MERGED', '_DGRAD_SPLITK', '_SEQ', '_STATS_OFFER', '_c', '_comm', '_first_order_only', '_offer_stats', '_param_grad_wanted', '_take_stats', '_tick', 'conv2d_q_raw', 'conv2d_q_wgrad_raw', 'conv2d_raw', 'conv2d_skip_raw', 'conv2d_wgrad_raw', 'dist', 'ensure_grad', 'f32_mode', 'gemm_dgrad_rows', 'gemm_raw', 'os', 'quad_pack_raw', 'second_order', 'torch']

@@ -206,6 +206,34 @@ def cal_r1_reg(adv_output, images, device):
     return F.GradPenaltyFn.apply(grad_dout, 1)
 
 
+def stylegan_cal_r1_reg(adv_output, images):
+    """R1 through the StyleGAN2 discriminator, reference src/utils/losses.py:378-382: mean_b 0.5 ||d sum(D(x)) / d x_b||^2. `images` must have
+    requires_grad=True before the forward that produced `adv_output`. The first pass runs inside style_ops.second_order() (where the reference has
+    conv2d_gradfix.no_weight_gradients(): the discriminator's operators record a differentiable backward and launch no weight gradient for it); the
+    penalty's own backward() needs no context."""
+    from .style_ops import second_order
+    with second_order():
+        r1_grads = autograd.grad(outputs=[adv_output.sum()], inputs=[images], create_graph=True, only_inputs=True)[0]
+    r1_penalty = r1_grads.square().sum([1, 2, 3]) / 2
+    return r1_penalty.mean()
+
+
+def stylegan_d_reg_step(discriminator, real_images, real_labels, r1_lambda, d_reg_interval, acml_steps=1):
+    """One accumulation step of the lazy R1 regulariser outside the training loop (reference src/worker.py:445-465, without its augmentations): forward on the
+    real batch with a gradient on the images, penalty * d_reg_interval * r1_lambda / acml_steps, backward into the parameters' .grad (the caller zeroes them
+    before and steps the optimiser after). Every returned tensor of the network enters with weight 0, as the reference's enable_allreduce does, so that a head
+    the penalty does not reach gets a zero gradient, not none. Returns the detached scaled penalty."""
+    real_images = real_images.detach().requires_grad_(True)
+    real_dict = discriminator(real_images, real_labels)
+    penalty = stylegan_cal_r1_reg(adv_output=real_dict["adv_output"], images=real_images)
+    for key, value in real_dict.items():
+        if value is not None and key != "label":
+            penalty = penalty + value.mean() * 0
+    penalty = penalty * (d_reg_interval * r1_lambda / acml_steps)
+    penalty.backward()
+    return penalty.detach()
+
+
 def l2_loss(a, b):
     """torch.nn.MSELoss() as the reference's worker builds it (src/worker.py:116): the consistency terms of CR / bCR / zCR
     (src/worker.py:326-361) and the generator's latent-consistency repulsion (:601-603)."""

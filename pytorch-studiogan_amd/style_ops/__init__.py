@@ -5,3 +5,4 @@ there is no `impl='ref'` here: the reference path lives in the reference and, re
 modulated_conv2d (reference src/models/stylegan2.py:28-98, the operator StyleGAN2's synthesis layers are made of) runs on csrc/modconv.hip;
 fir_bias_act (no counterpart in the reference: the FIR + noise + bias + activation tail of an up = 2 synthesis layer in one launch) on csrc/style_fir.hip."""
 from . import bias_act, upfirdn2d, filtered_lrelu, modulated_conv2d, fir_bias_act  # noqa: F401
+from ..functional._base import second_order  # noqa: F401      (the opt-in of the discriminator operators' differentiable backward: R1)

@@ -8,7 +8,9 @@ convolution) reads. a is never stored. act: 'linear' or 'lrelu'; with neither bi
 
 Gradients (first order; x is kept, not a):
     dx    = sg_act_fir_nhwc_bwd: (adjoint FIR of dy) * da/dx in one launch, da/dx re-evaluated from x and bias
-    dbias = sum_{n,p} dx"""
+    dbias = sum_{n,p} dx
+Second order, inside style_ops.second_order() only: the backward runs as ActFirGradFn, whose own backward is one sg_act_fir_nhwc_gate launch,
+    d_dy  = FIR( v * da/dx ), decimated                 v: the cotangent on dx; d_x = d_bias = 0 (a is piecewise linear)"""
 import torch
 
 from .. import _lib as L
@@ -48,6 +50,41 @@ def act_fir_nhwc_bwd_raw(x_shape, xh, dyh, f2d, pad, down=1, flip_filter=False, 
     return dx
 
 
+def act_fir_nhwc_gate_raw(vh, xh, f2d, pad, down=1, flip_filter=False, filter_gain=1.0, bias=None, act="linear", alpha=0.0, gain=1.0, clamp=-1.0):
+    """one sg_act_fir_nhwc_gate launch with the forward's arguments. vh: dense [N, Hi, Wi, C], the cotangent on dx; xh: the forward's input (None for the
+    plain FIR); -> d_dy [N, Ho, Wo, C]"""
+    y, (N, Hi, Wi, C, fh, fw) = nhwc_out("act_fir", vh, f2d, pad, down)
+    if xh is None and _gated(bias, act, gain, clamp):
+        raise AssertionError("act_fir: the gated second-order pass needs the forward's input")
+    if xh is not None and (not xh.is_contiguous() or xh.dtype != vh.dtype or tuple(xh.shape) != tuple(vh.shape)):
+        raise AssertionError("act_fir: the kernel takes dense NHWC tensors of one dtype")
+    if y.numel():
+        L.call("sg_act_fir_nhwc_gate", L.dt(vh), L.ptr(vh), L.ptr(xh), L.ptr(f2d), L.ptr(y), L.ptr(bias), N, Hi, Wi, C, fh, fw, int(down),
+               *epilogue_args(pad, flip_filter, filter_gain, act, alpha, gain, clamp))
+    return y
+
+
+class ActFirGradFn(torch.autograd.Function):
+    """apply(dyh, xh, b32, f2d, x_shape, pad, down, flip_filter, filter_gain, act, alpha, gain, clamp) -> dxh: ActFirFn's data gradient as a differentiable
+    function of dy (all tensors dense NHWC). Its backward is the gate launch; x and bias get no gradient (zero: the activation is piecewise linear)."""
+
+    @staticmethod
+    def forward(ctx, dyh, xh, b32, f2d, x_shape, pad, down, flip_filter, filter_gain, act, alpha, gain, clamp):
+        ctx.save_for_backward(xh, b32, f2d)
+        ctx.cfg = (pad, down, flip_filter, filter_gain, act, alpha, gain, clamp)
+        return act_fir_nhwc_bwd_raw(x_shape, xh, dyh, f2d, pad, down, flip_filter, filter_gain, b32, act, alpha, gain, clamp)
+
+    @staticmethod
+    def backward(ctx, v):
+        _first_order_only("act_fir (third order)")
+        xh, b32, f2d = ctx.saved_tensors
+        pad, down, flip_filter, filter_gain, act, alpha, gain, clamp = ctx.cfg
+        d_dy = None
+        if ctx.needs_input_grad[0]:
+            d_dy = act_fir_nhwc_gate_raw(v.contiguous(), xh, f2d, pad, down, flip_filter, filter_gain, b32, act, alpha, gain, clamp)
+        return (d_dy,) + (None,) * 12
+
+
 class ActFirFn(torch.autograd.Function):
     """apply(x, f2d, bias, pad, down, flip_filter, filter_gain, act, alpha, gain, clamp): x an NCHW view of NHWC memory, the result likewise"""
 
@@ -62,13 +99,16 @@ class ActFirFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        _first_order_only("act_fir")
+        differentiable = _first_order_only("act_fir")
         f2d, xh, b32 = ctx.saved_tensors
         x_shape, x_dtype, pad, down, flip_filter, filter_gain, act, alpha, gain, clamp, bias_dtype = ctx.cfg
         dx = db = None
         if ctx.needs_input_grad[0] or (bias_dtype is not None and ctx.needs_input_grad[2]):
             dyh = dy.to(x_dtype).permute(0, 2, 3, 1).contiguous()
-            dxh = act_fir_nhwc_bwd_raw(x_shape, xh, dyh, f2d, pad, down, flip_filter, filter_gain, b32, act, alpha, gain, clamp)
+            if differentiable:
+                dxh = ActFirGradFn.apply(dyh, xh, b32, f2d, x_shape, pad, down, flip_filter, filter_gain, act, alpha, gain, clamp)
+            else:
+                dxh = act_fir_nhwc_bwd_raw(x_shape, xh, dyh, f2d, pad, down, flip_filter, filter_gain, b32, act, alpha, gain, clamp)
             if ctx.needs_input_grad[0]:
                 dx = dxh.permute(0, 3, 1, 2)
             if bias_dtype is not None and ctx.needs_input_grad[2]:

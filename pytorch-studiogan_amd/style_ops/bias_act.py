@@ -80,6 +80,10 @@ def _make(dim, act, alpha, gain, clamp):
             if ctx.needs_input_grad[0] or (ctx.has_b and ctx.needs_input_grad[1]):
                 dx = dy
                 if act != "linear" or gain != 1 or clamp >= 0:
+                    if not spec.has_2nd_grad and y is not None:
+                        # (a piecewise-linear activation: BiasActGrad has no gradient for y, and an edge to the forward graph that carries none would still
+                        # make a second-order backward walk that graph's whole backward with zeros: R1 through the discriminator's epilogue)
+                        y = y.detach()
                     dx = BiasActGrad.apply(dy, x, b, y)
             if ctx.has_b and ctx.needs_input_grad[1]:
                 db = dx.sum([i for i in range(dx.dim()) if i != dim])

@@ -1,4 +1,5 @@
-"""conv2d_resample: the plain (unmodulated) convolutions of the StyleGAN2 discriminator, channels-last, float32 or bfloat16, with first-order gradients.
+"""conv2d_resample: the plain (unmodulated) convolutions of the StyleGAN2 discriminator, channels-last, float32 or bfloat16, with first-order gradients
+(second-order ones inside style_ops.second_order()).
 
     conv2d_plain(x, w, stride)     1x1 or 3x3 at stride 1 / pad k // 2, or 3x3 at stride 2 / pad 0; correlation, like torch's conv2d
     conv2d_resample(x, w, f, down, padding, ...)   the reference's operator for up = 1 (conv2d_resample.py:86-108): a 1x1 kernel decimates through the low-pass
@@ -12,12 +13,14 @@ of plain convolutions must not, so this is an autograd.Function of its own. Each
     sg_modconv2d_fwd   with NULL scale tables otherwise (C = 3 of the image, C + 1 of the epilogue, 12 bf16 channels): the same generic engine behind an
                        entry that serves these three geometries for any channel count
 Data gradient: the same dispatch on the transposed image at stride 1, the SG_PIX_TRANSPOSED gather at stride 2; weight gradient: sg_conv2d_wgrad (at stride 2
-in the geometry the up = 2 path uses with swapped roles). `record()` collects which entry every launch took (tools/stylegan2_dis_bench.py prints it per layer);
+in the geometry the up = 2 path uses with swapped roles). Second order (R1), inside style_ops.second_order() only: the backward runs as _PlainConvDgradFn /
+_PlainConvWgradFn. A convolution is bilinear, so their backwards are the same three launches with the roles permuted (roles `dgrad2` / `wgrad2` in the log);
+a weight gradient nobody asked for (autograd.grad(inputs=[images]), the reference's no_weight_gradients) is not launched. `record()` collects which entry every launch took (tools/stylegan2_dis_bench.py prints it per layer);
 FORCE pins one entry for an A/B."""
 import torch
 
 from .. import _lib as L
-from ..functional._base import _first_order_only, conv2d_raw, conv2d_wgrad_raw
+from ..functional._base import _first_order_only, _param_grad_wanted, conv2d_raw, conv2d_wgrad_raw
 from . import upfirdn2d as _upfirdn2d
 from ._fir_common import MAX_TAPS, down2_padding
 from .act_fir import act_fir
@@ -64,45 +67,109 @@ def _conv_raw(role, xh, wimg, Cout, k, mode):
     return conv2d_raw(xh, L.ptr(wimg), C, Cout, k, k, 2, 0, 0, L.PIX_TRANSPOSED, transposed_out_hw=(2 * Hs + 1, 2 * Ws + 1))
 
 
+def _fwd(role, xh, weight, stride):
+    """y (NHWC) of the correlation of dense NHWC xh with weight [O, I, k, k]"""
+    Cout, C, k, _ = weight.shape
+    wimg = weight.detach().permute(0, 2, 3, 1).contiguous().to(xh.dtype)         # [Cout][r][s][C]
+    return _conv_raw(role, xh, wimg, Cout, k, "same" if stride == 1 else "down2")
+
+
+def _dgrad(role, gyh, weight, stride):
+    """dx (NHWC) from dense NHWC gyh"""
+    Cout, C, k, _ = weight.shape
+    w = weight.detach()
+    if stride == 1:
+        wd = w.flip(2, 3).permute(1, 2, 3, 0).contiguous().to(gyh.dtype)        # [C][2-r][2-s][Cout]
+        return _conv_raw(role, gyh, wd, C, k, "same")
+    # the adjoint of y[h, w] = sum x[2h + r, 2w + s] W[r, s] is the transposed gather with the same taps
+    wd = w.permute(1, 2, 3, 0).contiguous().to(gyh.dtype)                       # [C][r][s][Cout]
+    return _conv_raw(role, gyh, wd, C, k, "up2")
+
+
+def _wgrad(role, xh, gyh, wshape, stride, out_dtype):
+    """dw [O, I, k, k] in out_dtype from dense NHWC xh and gyh (fp32 accumulation)"""
+    Cout, C, k, _ = wshape
+    N, H, W, _ = xh.shape
+    if _log is not None and role is not None:       # (role None: the first-order backward outside second_order(), whose log lists the convolution entries only)
+        _log.append((role, "sg_conv2d_wgrad", "bf16" if xh.dtype == torch.bfloat16 else "fp32", N, H, W, C, Cout, k, "same" if stride == 1 else "down2"))
+    dwi = torch.zeros((Cout, k, k, C), dtype=torch.float32, device=xh.device)
+    if stride == 1:
+        conv2d_wgrad_raw(xh, gyh, L.ptr(dwi), C, Cout, k, k, H, W, 1, k // 2, k // 2)
+    else:
+        conv2d_wgrad_raw(xh, gyh, L.ptr(dwi), C, Cout, k, k, gyh.shape[1], gyh.shape[2], 2, 0, 0)
+    return dwi.permute(0, 3, 1, 2).to(out_dtype)
+
+
+class _PlainConvDgradFn(torch.autograd.Function):
+    """apply(gyh, weight, stride) -> dxh: the data gradient as a differentiable function of gy and the weight (dense NHWC tensors of one dtype)"""
+
+    @staticmethod
+    def forward(ctx, gyh, weight, stride):
+        ctx.save_for_backward(gyh, weight)
+        ctx.stride = stride
+        return _dgrad("dgrad", gyh, weight, stride)
+
+    @staticmethod
+    def backward(ctx, v):
+        _first_order_only("conv2d_resample (third order)")
+        gyh, weight = ctx.saved_tensors
+        vh = v.to(gyh.dtype).contiguous()
+        d_gy = d_w = None
+        if ctx.needs_input_grad[0]:         # dx is linear in gy: the forward convolution of the cotangent
+            d_gy = _fwd("dgrad2", vh, weight, ctx.stride)
+        if ctx.needs_input_grad[1] and _param_grad_wanted(weight):      # <v, dgrad(gy, W)> = <conv(v, W), gy>: the weight gradient with v in x's place
+            d_w = _wgrad("wgrad2", vh, gyh, weight.shape, ctx.stride, weight.dtype)
+        return d_gy, d_w, None
+
+
+class _PlainConvWgradFn(torch.autograd.Function):
+    """apply(xh, gyh, weight, stride) -> dw: the weight gradient as a differentiable function of x and gy (weight: shape and dtype only)"""
+
+    @staticmethod
+    def forward(ctx, xh, gyh, weight, stride):
+        ctx.save_for_backward(xh, gyh)
+        ctx.stride = stride
+        return _wgrad("wgrad", xh, gyh, weight.shape, stride, weight.dtype)
+
+    @staticmethod
+    def backward(ctx, v):
+        _first_order_only("conv2d_resample (third order)")
+        xh, gyh = ctx.saved_tensors
+        d_x = d_gy = None
+        if ctx.needs_input_grad[0]:         # <v, wgrad(x, gy)> = <conv(x, v), gy>
+            d_x = _dgrad("dgrad2", gyh, v, ctx.stride)
+        if ctx.needs_input_grad[1]:
+            d_gy = _fwd("dgrad2", xh, v, ctx.stride)
+        return d_x, d_gy, None, None
+
+
 class _PlainConvFn(torch.autograd.Function):
     """apply(x, weight, stride): x an NCHW view of NHWC memory, weight [O, I, k, k]; the result likewise channels-last"""
 
     @staticmethod
     def forward(ctx, x, weight, stride):
         xh = x.detach().permute(0, 2, 3, 1).contiguous()                 # free for a channels_last x
-        Cout, C, k, _ = weight.shape
-        wimg = weight.detach().permute(0, 2, 3, 1).contiguous().to(x.dtype)         # [Cout][r][s][C]
-        y = _conv_raw("fwd", xh, wimg, Cout, k, "same" if stride == 1 else "down2")
-        ctx.save_for_backward(xh, weight)
+        y = _fwd("fwd", xh, weight, stride)
+        ctx.save_for_backward(xh, weight, x)        # (x: for the second-order pass, whose gradient has to reach the graph behind it; xh's storage)
         ctx.stride = stride
         return y.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, gy):
-        _first_order_only("conv2d_resample")
-        xh, weight = ctx.saved_tensors
+        xh, weight, x = ctx.saved_tensors
         stride = ctx.stride
-        N, H, W, C = xh.shape
-        Cout, _, k, _ = weight.shape
-        T = xh.dtype
-        gyh = gy.to(T).permute(0, 2, 3, 1).contiguous()
+        gyh = gy.to(xh.dtype).permute(0, 2, 3, 1).contiguous()
         dx = dw = None
+        if _first_order_only("conv2d_resample"):
+            if ctx.needs_input_grad[0]:
+                dx = _PlainConvDgradFn.apply(gyh, weight, stride).permute(0, 3, 1, 2)
+            if ctx.needs_input_grad[1] and _param_grad_wanted(weight):
+                dw = _PlainConvWgradFn.apply(x.permute(0, 2, 3, 1).contiguous(), gyh, weight, stride)
+            return dx, dw, None
         if ctx.needs_input_grad[0]:
-            w = weight.detach()
-            if stride == 1:
-                wd = w.flip(2, 3).permute(1, 2, 3, 0).contiguous().to(T)            # [C][2-r][2-s][Cout]
-                dx = _conv_raw("dgrad", gyh, wd, C, k, "same")
-            else:       # the adjoint of y[h, w] = sum x[2h + r, 2w + s] W[r, s] is the transposed gather with the same taps
-                wd = w.permute(1, 2, 3, 0).contiguous().to(T)                       # [C][r][s][Cout]
-                dx = _conv_raw("dgrad", gyh, wd, C, k, "up2")
-            dx = dx.permute(0, 3, 1, 2)
+            dx = _dgrad("dgrad", gyh, weight, stride).permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1]:
-            dwi = torch.zeros((Cout, k, k, C), dtype=torch.float32, device=xh.device)
-            if stride == 1:
-                conv2d_wgrad_raw(xh, gyh, L.ptr(dwi), C, Cout, k, k, H, W, 1, k // 2, k // 2)
-            else:
-                conv2d_wgrad_raw(xh, gyh, L.ptr(dwi), C, Cout, k, k, gyh.shape[1], gyh.shape[2], 2, 0, 0)
-            dw = dwi.permute(0, 3, 1, 2).to(weight.dtype)
+            dw = _wgrad(None, xh, gyh, weight.shape, stride, weight.dtype)
         return dx, dw, None
 
 

@@ -5,7 +5,8 @@
     out      = cat([x, s broadcast to [N, num_channels, H, W]], dim=1)
 
 One launch forward, writing the concatenated channels-last tensor itself, and one launch backward (mean and variance recomputed from the kept x). fp32,
-deterministic, first order."""
+deterministic. Second order inside style_ops.second_order() only: the backward runs as MinibatchStdGradFn, whose own backward is one sg_mbstd_bwd2 launch
+(gradients for both dout and x: the statistic is the one operator on the discriminator's path with a second derivative)."""
 import torch
 
 from .. import _lib as L
@@ -22,6 +23,40 @@ def _groups(N, C, group_size, num_channels):
     return G, F
 
 
+def _scratch(N, H, W, C, G, F, device):
+    """(part, tickets) of a launch whose (group, slice) pairs are cut into chunks: their partial sums, and the zeroed counter the last chunk is found with"""
+    S = L.lib().sg_mbstd_splits(N, H, W, C, G, F)
+    if S <= 1:
+        return None, None
+    return torch.empty((N // G) * F * S, dtype=torch.float32, device=device), zeros_small((N // G) * F, torch.int32, device)
+
+
+class MinibatchStdGradFn(torch.autograd.Function):
+    """apply(dh, xh, G, F) -> dxh: MinibatchStdFn's backward as a differentiable function of dout AND x (dense fp32 NHWC tensors)"""
+
+    @staticmethod
+    def forward(ctx, dh, xh, G, F):
+        N, H, W, C = xh.shape
+        dx = torch.empty_like(xh)
+        L.call("sg_mbstd_bwd", L.ptr(xh), C, L.ptr(dh), L.ptr(dx), N, H, W, C, G, F, L.stream())
+        ctx.save_for_backward(dh, xh)
+        ctx.cfg = (G, F)
+        return dx
+
+    @staticmethod
+    def backward(ctx, v):
+        _first_order_only("minibatch_std (third order)")
+        dh, xh = ctx.saved_tensors
+        G, F = ctx.cfg
+        N, H, W, C = xh.shape
+        vh = v.to(torch.float32).contiguous()
+        d_dout = torch.empty_like(dh)
+        d_x = torch.empty_like(xh)
+        part, tickets = _scratch(N, H, W, C, G, F, xh.device)
+        L.call("sg_mbstd_bwd2", L.ptr(xh), C, L.ptr(dh), L.ptr(vh), L.ptr(d_dout), L.ptr(d_x), L.ptr(part), L.ptr(tickets), N, H, W, C, G, F, L.stream())
+        return d_dout, d_x, None, None
+
+
 class MinibatchStdFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, G, F):
@@ -29,23 +64,23 @@ class MinibatchStdFn(torch.autograd.Function):
         N, C, H, W = x.shape
         xh = x.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()       # free for an fp32 channels_last x
         out = torch.empty((N, H, W, C + F), dtype=torch.float32, device=x.device)
-        part = tickets = None
-        S = L.lib().sg_mbstd_splits(N, H, W, C, G, F)
-        if S > 1:       # a pair cut into chunks: their partial sums, and the zeroed ticket counter the last chunk to finish is found with
-            part = torch.empty((N // G) * F * S, dtype=torch.float32, device=x.device)
-            tickets = zeros_small((N // G) * F, torch.int32, x.device)
+        part, tickets = _scratch(N, H, W, C, G, F, x.device)
         L.call("sg_mbstd_fwd", L.ptr(xh), C, L.ptr(out), L.ptr(part), L.ptr(tickets), N, H, W, C, G, F, L.stream())
-        ctx.save_for_backward(xh)
+        # (x itself rides along for the second-order pass, whose gradient has to reach the graph behind it; for an fp32 channels_last x it is xh's storage)
+        ctx.save_for_backward(xh, x)
         ctx.cfg = (G, F, x.dtype)
         return out.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, dout):
-        _first_order_only("minibatch_std")
-        (xh,) = ctx.saved_tensors
+        differentiable = _first_order_only("minibatch_std")
+        xh, x = ctx.saved_tensors
         G, F, x_dtype = ctx.cfg
         N, H, W, C = xh.shape
         dh = dout.to(torch.float32).permute(0, 2, 3, 1).contiguous()
+        if differentiable:
+            dx = MinibatchStdGradFn.apply(dh, x.to(torch.float32).permute(0, 2, 3, 1).contiguous(), G, F)
+            return dx.permute(0, 3, 1, 2).to(x_dtype), None, None
         dx = torch.empty_like(xh)
         L.call("sg_mbstd_bwd", L.ptr(xh), C, L.ptr(dh), L.ptr(dx), N, H, W, C, G, F, L.stream())
         return dx.permute(0, 3, 1, 2).to(x_dtype), None, None
