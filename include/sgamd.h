@@ -379,6 +379,34 @@ int sg_cbn_bwd2_dgain(const float* sums, const double* chan, double count, const
 int sg_cbn_bwd2_apply(int dtype, const void* x, const void* dy, const void* u, void* g_dy, void* g_x, int N, long long HW, int C,
                       const float* mean, const float* invstd, const float* gain, const float* bias, const float* A, const float* B,
                       int gb_stride_n, int relu, const double* chan, double count, int use_batch_stats, sg_stream_t s);
+/* Which kernel a batch-norm entry point launched: one relaxed atomic counter per (entry point, kernel) pair, moved on the host next to the launch.
+ * Every kernel of an entry point gives the same values; the counters are for tests that have to prove which one ran. */
+enum {
+  SG_BN_PATH_PARTIAL_GENERIC = 0,        /* sg_bn_partial_stats: scalar loads, fp64 throughout */
+  SG_BN_PATH_PARTIAL_STREAM = 1,         /*   16-byte loads, rows >= 4096 */
+  SG_BN_PATH_APPLY_SCALAR = 2,           /* sg_bn_apply: one element per thread */
+  SG_BN_PATH_APPLY_VEC = 3,              /*   16-byte vectors, generic indexing */
+  SG_BN_PATH_APPLY_STREAM = 4,           /*   16-byte vectors, several loads in flight (variants: sg_bn_apply_variant) */
+  SG_BN_PATH_BWD_REDUCE_GENERIC = 5,     /* sg_bn_bwd_reduce */
+  SG_BN_PATH_BWD_REDUCE_STREAM = 6,
+  SG_BN_PATH_BWD_APPLY_SCALAR = 7,       /* sg_bn_bwd_apply_res (and sg_bn_bwd_apply, which forwards to it) */
+  SG_BN_PATH_BWD_APPLY_VEC = 8,
+  SG_BN_PATH_BWD_APPLY_STREAM = 9,
+  SG_BN_PATH_CBN_BWD2_APPLY_SCALAR = 10, /* sg_cbn_bwd2_apply */
+  SG_BN_PATH_CBN_BWD2_APPLY_VEC = 11,
+  SG_BN_PATH_APPLY_STREAM_V0 = 12,       /* which instantiation a streaming launch of sg_bn_apply was (counted besides SG_BN_PATH_APPLY_STREAM): */
+  SG_BN_PATH_APPLY_STREAM_V1 = 13,       /*   V0 four loads in flight, V1 eight, V2 four + non-temporal accesses, V3 eight + non-temporal */
+  SG_BN_PATH_APPLY_STREAM_V2 = 14,
+  SG_BN_PATH_APPLY_STREAM_V3 = 15,
+  SG_BN_PATH_COUNT = 16
+};
+/* launches so far that took `path` (-1 for a value outside the enum) */
+long long sg_bn_path_launches(int path);
+/* The streaming kernel of sg_bn_apply for this process: variant 0 = four loads in flight, 1 = eight, 2 = four + non-temporal accesses, 3 = eight +
+ * non-temporal, spread over about `workgroups` workgroups (<= 0: the target that SG_BN_APPLY or the default gives). variant < 0 returns to what the
+ * environment variable SG_BN_APPLY ("<variant><workgroups / 1024>") or the default (variant 0, 2048 workgroups) says; a variant above 3 is refused.
+ * Every variant does the same arithmetic per element and writes the same bytes. */
+int sg_bn_apply_variant(int variant, int workgroups);
 
 /* ---- spectral norm (torch.nn.utils.spectral_norm, eps 1e-6, one power iteration per forward) -------------- */
 typedef struct {

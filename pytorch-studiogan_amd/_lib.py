@@ -170,6 +170,8 @@ _PROTOS = {
     "sg_get_f32_mode": [],
     "sg_f32_split_launches": [_i],                         # returns a count
     "sg_ew_vec_launches": [],                              # returns a count
+    "sg_bn_path_launches": [_i],                           # returns a count
+    "sg_bn_apply_variant": [_i, _i],
     "sg_reduce_scatter_flat": [_vp, _vp, _ll, _vp],
     "sg_allgather_flat": [_vp, _vp, _ll, _vp],
     "sg_p2p_create": [_i, _i, _ll, C.POINTER(_vp), _vp],
@@ -330,6 +332,7 @@ def lib():
         l.sg_mha_launches.restype = _ll
         l.sg_f32_split_launches.restype = _ll
         l.sg_ew_vec_launches.restype = _ll
+        l.sg_bn_path_launches.restype = _ll
         l.sg_linear_group_scaled_launches.restype = _ll
         l.sg_fir_bias_act_launches.restype = _ll
         l.sg_act_fir_launches.restype = _ll

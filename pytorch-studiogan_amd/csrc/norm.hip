@@ -6,6 +6,36 @@
 #include "common.h"
 #include "../../include/sgamd.h"
 
+// which kernel an entry point launched (sgamd.h SG_BN_PATH_*): counted on the host next to the launch, read by tests that have to prove which one ran
+static long long g_bn_path_launches[SG_BN_PATH_COUNT] = {};
+static inline void bn_path_count(int path) { __atomic_fetch_add(&g_bn_path_launches[path], 1, __ATOMIC_RELAXED); }
+extern "C" long long sg_bn_path_launches(int path) {
+  if (path < 0 || path >= SG_BN_PATH_COUNT) return -1;
+  return __atomic_load_n(&g_bn_path_launches[path], __ATOMIC_RELAXED);
+}
+
+// The arithmetic that the kernels of one entry point, and the forward and the backward of one layer, have to share BIT FOR BIT, written once with the fused
+// multiply-adds spelled out and no contraction beyond them. Left to the compiler, a * b + c was fused in one instantiation and not in another (in the bf16
+// k_bn_bwd_apply_stream even for six of a thread's eight channels and not for the other two), so that the streaming and the scalar kernel wrote different bytes and a
+// ReLU input within an ulp of zero could pass the forward and be masked in the backward.
+__device__ __forceinline__ float bn_xhat(float x, float mu, float is) {
+#pragma clang fp contract(off)
+  return (x - mu) * is;
+}
+// the ReLU's input, gain * xhat + bias, one rounding
+__device__ __forceinline__ float bn_pre(float xh, float ga, float bi) { return __builtin_fmaf(xh, ga, bi); }
+// dx = invstd (gain dy' - (k0 + xhat k1) / count) [+ res]
+__device__ __forceinline__ float bn_dx(float g, float xh, float ga, float is, float k0, float k1, float invc, int use_batch) {
+#pragma clang fp contract(off)
+  float d = ga * g;
+  if (use_batch) d = __builtin_fmaf(-__builtin_fmaf(xh, k1, k0), invc, d);
+  return d * is;
+}
+__device__ __forceinline__ float bn_add(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
 // ---- statistics ------------------------------------------------------------------------------------------
 template <typename T> __global__ __launch_bounds__(256) void k_bn_partial(const T* x, int ldx, long long rows, int C, double* partial, long long rpb) {
   __shared__ double sm[2][4][64];
@@ -83,6 +113,7 @@ extern "C" int sg_bn_partial_stats(int dtype, const void* x, int ldx, long long 
       long long rpb = (rows + 1023) / 1024; if (rpb < 32ll * lanes_p) rpb = 32ll * lanes_p;
       const int gx = (int)((rows + rpb - 1) / rpb);
       hipLaunchKernelGGL(k_bn_partial_stream<T>, dim3(gx), dim3(CV * lanes_p), (size_t)lanes_p * C * 2 * sizeof(double), (hipStream_t)s, (const T*)x, ldx, rows, C, partial, rpb);
+      bn_path_count(SG_BN_PATH_PARTIAL_STREAM);
       done = true;
     }
   });
@@ -92,6 +123,7 @@ extern "C" int sg_bn_partial_stats(int dtype, const void* x, int ldx, long long 
   long long rpb = (rows + want - 1) / want; if (rpb < 64) rpb = 64;
   int gy = (int)((rows + rpb - 1) / rpb);
   DISPATCH_T(dtype, hipLaunchKernelGGL(k_bn_partial<T>, dim3(ct, gy), dim3(256), 0, (hipStream_t)s, (const T*)x, ldx, rows, C, partial, rpb));
+  bn_path_count(SG_BN_PATH_PARTIAL_GENERIC);
   SG_LAUNCH_CHECK();
   return 0;
 }
@@ -176,11 +208,11 @@ template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_bn_app
 #pragma unroll
     for (int e = 0; e < V; e++) {
       const int c = c0 + e;
-      // same evaluation order as the backward's recomputation (xhat * gain + bias)
-      const float xh = (xv[e] - mean[c]) * invstd[c];
+      // the same evaluation as the backward's recomputation (bn_xhat, bn_pre)
+      const float xh = bn_xhat(xv[e], mean[c], invstd[c]);
       const float ga = gain ? gain[(long long)n * gsn + c] : 1.f;
       const float bi = bias ? bias[(long long)n * gsn + c] : 0.f;
-      float v = xh * ga + bi;
+      float v = bn_pre(xh, ga, bi);
       if (relu) v = fmaxf(v, 0.f);
       xv[e] = v;
     }
@@ -220,7 +252,7 @@ template <typename T, int UN, bool NT> __global__ __launch_bounds__(256) void k_
     unpack16<T>(raw, xv);
 #pragma unroll
     for (int e = 0; e < V; e++) {
-      float v = ((xv[e] - mu[e]) * is[e]) * ga[e] + bi[e];   // same evaluation order as the backward's recomputation
+      float v = bn_pre(bn_xhat(xv[e], mu[e], is[e]), ga[e], bi[e]);   // the same evaluation as the backward's recomputation
       if (relu) v = fmaxf(v, 0.f);
       xv[e] = v;
     }
@@ -237,12 +269,33 @@ template <typename T, int UN, bool NT> __global__ __launch_bounds__(256) void k_
   }
   for (; pix < p1; pix += lanes_p) one(*(const u32x4*)(xs + pix * C), pix);
 }
+// one instantiation launched and counted under the variant number its template arguments stand for (not the one that was asked for)
+template <typename T, int UN, bool NT> static void bn_apply_stream_go(dim3 grid, dim3 blk, hipStream_t st, const T* x, T* y, long long HW, int C, const float* mean, const float* invstd, const float* gain,
+                                                                     const float* bias, int gsn, int relu, int ppb) {
+  hipLaunchKernelGGL((k_bn_apply_stream<T, UN, NT>), grid, blk, 0, st, x, y, HW, C, mean, invstd, gain, bias, gsn, relu, ppb);
+  bn_path_count(SG_BN_PATH_APPLY_STREAM_V0 + (UN == 8 ? 1 : 0) + (NT ? 2 : 0));
+}
 template <typename T> static void bn_apply_stream_launch(int variant, dim3 grid, dim3 blk, hipStream_t st, const T* x, T* y, long long HW, int C, const float* mean, const float* invstd, const float* gain,
                                                          const float* bias, int gsn, int relu, int ppb) {
-  if (variant == 0) hipLaunchKernelGGL((k_bn_apply_stream<T, 4, false>), grid, blk, 0, st, x, y, HW, C, mean, invstd, gain, bias, gsn, relu, ppb);
-  else if (variant == 1) hipLaunchKernelGGL((k_bn_apply_stream<T, 8, false>), grid, blk, 0, st, x, y, HW, C, mean, invstd, gain, bias, gsn, relu, ppb);
-  else if (variant == 2) hipLaunchKernelGGL((k_bn_apply_stream<T, 4, true>), grid, blk, 0, st, x, y, HW, C, mean, invstd, gain, bias, gsn, relu, ppb);
-  else hipLaunchKernelGGL((k_bn_apply_stream<T, 8, true>), grid, blk, 0, st, x, y, HW, C, mean, invstd, gain, bias, gsn, relu, ppb);
+  if (variant == 0) bn_apply_stream_go<T, 4, false>(grid, blk, st, x, y, HW, C, mean, invstd, gain, bias, gsn, relu, ppb);
+  else if (variant == 1) bn_apply_stream_go<T, 8, false>(grid, blk, st, x, y, HW, C, mean, invstd, gain, bias, gsn, relu, ppb);
+  else if (variant == 2) bn_apply_stream_go<T, 4, true>(grid, blk, st, x, y, HW, C, mean, invstd, gain, bias, gsn, relu, ppb);
+  else bn_apply_stream_go<T, 8, true>(grid, blk, st, x, y, HW, C, mean, invstd, gain, bias, gsn, relu, ppb);
+}
+// The streaming variant and workgroup target of sg_bn_apply: SG_BN_APPLY (read once) or the default, unless sg_bn_apply_variant has set them for this process
+static int g_bn_apply_set_variant = -1, g_bn_apply_set_want = 0;
+extern "C" int sg_bn_apply_variant(int variant, int workgroups) {
+  SG_CHECK(variant <= 3, "sg_bn_apply_variant: variant 0-3, or < 0 for what SG_BN_APPLY or the default says");
+  __atomic_store_n(&g_bn_apply_set_want, variant >= 0 && workgroups > 0 ? workgroups : 0, __ATOMIC_RELAXED);
+  __atomic_store_n(&g_bn_apply_set_variant, variant < 0 ? -1 : variant, __ATOMIC_RELAXED);
+  return 0;
+}
+static void bn_apply_config(int* variant, long long* want) {
+  static const char* ev = getenv("SG_BN_APPLY");
+  *variant = ev && ev[0] >= '0' && ev[0] <= '3' ? ev[0] - '0' : 0;
+  *want = ev && ev[0] && ev[1] >= '1' && ev[1] <= '9' ? 1024ll * (ev[1] - '0') : 2048;
+  const int sv = __atomic_load_n(&g_bn_apply_set_variant, __ATOMIC_RELAXED), sw = __atomic_load_n(&g_bn_apply_set_want, __ATOMIC_RELAXED);
+  if (sv >= 0) { *variant = sv; if (sw > 0) *want = sw; }
 }
 extern "C" int sg_bn_apply(int dtype, const void* x, void* y, int N, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, int gb_stride_n, int relu, sg_stream_t s) {
   SgProfScope prof((hipStream_t)s, 2.0 * N * (double)HW * C * (dtype == SG_DTYPE_BF16 ? 2.0 : 4.0), 4);
@@ -257,15 +310,20 @@ extern "C" int sg_bn_apply(int dtype, const void* x, void* y, int N, long long H
       // alternations read +1.0 ms for the non-temporal arm (profiles/r06_bn_apply_step_ab_r7l.txt), but an ABBA series showed every second PROCESS on such a box running 1.5 ms
       // faster whatever the variant (profiles/r06_bn_apply_reverse_walk_r7r.txt): corrected, the effect lies between -0.9 and +0.2 ms. Unresolved, so the default stays variant 0
       // (the pass's output is the next convolution's input; what it leaves in the Infinity Cache may matter as much as its own 0.1 ms).
-      static const char* ev = getenv("SG_BN_APPLY");
-      const int variant = ev && ev[0] >= '0' && ev[0] <= '3' ? ev[0] - '0' : 0;
-      const long long want = ev && ev[0] && ev[1] >= '1' && ev[1] <= '9' ? 1024ll * (ev[1] - '0') : 2048;
+      int variant; long long want;
+      bn_apply_config(&variant, &want);
       long long chunks = want / N; if (chunks < 1) chunks = 1;
       long long ppb = (HW + chunks - 1) / chunks; if (ppb < 4 * lanes_p) ppb = 4 * lanes_p;
       const int gx = (int)((HW + ppb - 1) / ppb);
       bn_apply_stream_launch<T>(variant, dim3(gx, N), dim3(CV * lanes_p), (hipStream_t)s, (const T*)x, (T*)y, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, (int)ppb);
-    } else if (vec_ok<T>(x, y, C)) hipLaunchKernelGGL((k_bn_apply<T, true>), dim3(grid_for((long long)N * HW * C / ET<T>::VEC)), dim3(256), 0, (hipStream_t)s, (const T*)x, (T*)y, N, HW, C, mean, invstd, gain, bias, gb_stride_n, relu);
-    else hipLaunchKernelGGL((k_bn_apply<T, false>), dim3(grid_for((long long)N * HW * C)), dim3(256), 0, (hipStream_t)s, (const T*)x, (T*)y, N, HW, C, mean, invstd, gain, bias, gb_stride_n, relu);
+      bn_path_count(SG_BN_PATH_APPLY_STREAM);
+    } else if (vec_ok<T>(x, y, C)) {
+      hipLaunchKernelGGL((k_bn_apply<T, true>), dim3(grid_for((long long)N * HW * C / ET<T>::VEC)), dim3(256), 0, (hipStream_t)s, (const T*)x, (T*)y, N, HW, C, mean, invstd, gain, bias, gb_stride_n, relu);
+      bn_path_count(SG_BN_PATH_APPLY_VEC);
+    } else {
+      hipLaunchKernelGGL((k_bn_apply<T, false>), dim3(grid_for((long long)N * HW * C)), dim3(256), 0, (hipStream_t)s, (const T*)x, (T*)y, N, HW, C, mean, invstd, gain, bias, gb_stride_n, relu);
+      bn_path_count(SG_BN_PATH_APPLY_SCALAR);
+    }
   });
   SG_LAUNCH_CHECK();
   return 0;
@@ -287,9 +345,9 @@ template <typename T> __global__ __launch_bounds__(256) void k_bn_bwd_reduce(con
     const T* xp = x + (long long)n * HW * C + c;
     const T* gp = dy + (long long)n * HW * C + c;
     for (long long r = r0 + ry; r < r1; r += 4) {
-      const float xh = (to_f<T>(xp[r * C]) - mu) * is;
+      const float xh = bn_xhat(to_f<T>(xp[r * C]), mu, is);
       float g = to_f<T>(gp[r * C]);
-      if (relu && !(xh * ga + bi > 0.f)) g = 0.f;
+      if (relu && !(bn_pre(xh, ga, bi) > 0.f)) g = 0.f;
       s1 += g; s2 += g * xh;
     }
   }
@@ -327,9 +385,9 @@ template <typename T> __global__ __launch_bounds__(256) void k_bn_bwd_reduce_str
     unpack16<T>(rg, gv);
 #pragma unroll
     for (int e = 0; e < V; e++) {
-      const float xh = (xv[e] - mu[e]) * is[e];
+      const float xh = bn_xhat(xv[e], mu[e], is[e]);
       float g = gv[e];
-      if (relu && !(xh * ga[e] + bi[e] > 0.f)) g = 0.f;
+      if (relu && !(bn_pre(xh, ga[e], bi[e]) > 0.f)) g = 0.f;
       s1[e] += g; s2[e] += g * xh;
     }
   };
@@ -365,6 +423,7 @@ extern "C" int sg_bn_bwd_reduce(int dtype, const void* x, const void* dy, int N,
       long long ppb = (HW + chunks - 1) / chunks; if (ppb < 8 * lanes_p) ppb = 8 * lanes_p;
       const int gx = (int)((HW + ppb - 1) / ppb);
       hipLaunchKernelGGL(k_bn_bwd_reduce_stream<T>, dim3(gx, N), dim3(CV * lanes_p), (size_t)lanes_p * C * 2 * sizeof(float), (hipStream_t)s, (const T*)x, (const T*)dy, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, sums, (int)ppb);
+      bn_path_count(SG_BN_PATH_BWD_REDUCE_STREAM);
       done = true;
     }
   });
@@ -374,6 +433,7 @@ extern "C" int sg_bn_bwd_reduce(int dtype, const void* x, const void* dy, int N,
   long long rpb = (HW + want - 1) / want; if (rpb < 16) rpb = 16;
   int gy = (int)((HW + rpb - 1) / rpb);
   DISPATCH_T(dtype, hipLaunchKernelGGL(k_bn_bwd_reduce<T>, dim3(ct, gy, N), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, sums, rpb));
+  bn_path_count(SG_BN_PATH_BWD_REDUCE_GENERIC);
   SG_LAUNCH_CHECK();
   return 0;
 }
@@ -429,20 +489,18 @@ template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_bn_bwd
     for (int e = 0; e < V; e++) {
       const int c = c0 + e;
       const float is = invstd[c];
-      const float xh = (xv[e] - mean[c]) * is;
+      const float xh = bn_xhat(xv[e], mean[c], is);
       const float ga = gain ? gain[(long long)n * gsn + c] : 1.f;
       const float bi = bias ? bias[(long long)n * gsn + c] : 0.f;
       float g = gv[e];
-      if (relu && !(xh * ga + bi > 0.f)) g = 0.f;
-      float d = ga * g;
-      if (use_batch) d -= ((float)chan[2 * c] + xh * (float)chan[2 * c + 1]) * invc;
-      xv[e] = d * is;
+      if (relu && !(bn_pre(xh, ga, bi) > 0.f)) g = 0.f;
+      xv[e] = bn_dx(g, xh, ga, is, use_batch ? (float)chan[2 * c] : 0.f, use_batch ? (float)chan[2 * c + 1] : 0.f, invc, use_batch);
     }
     if (res) {
       float rv[V];
       if (VECP) unpack16<T>(*(const u32x4*)(res + pix * C + c0), rv); else rv[0] = to_f<T>(res[pix * C + c0]);
 #pragma unroll
-      for (int e = 0; e < V; e++) xv[e] += rv[e];
+      for (int e = 0; e < V; e++) xv[e] = bn_add(xv[e], rv[e]);
     }
     if (VECP) *(u32x4*)(dx + pix * C + c0) = pack16<T>(xv); else dx[pix * C + c0] = from_f<T>(xv[0]);
   }
@@ -475,18 +533,16 @@ template <typename T> __global__ __launch_bounds__(256) void k_bn_bwd_apply_stre
     unpack16<T>(rg, gv);
 #pragma unroll
     for (int e = 0; e < V; e++) {
-      const float xh = (xv[e] - mu[e]) * is[e];
+      const float xh = bn_xhat(xv[e], mu[e], is[e]);
       float g = gv[e];
-      if (relu && !(xh * ga[e] + bi[e] > 0.f)) g = 0.f;
-      float d = ga[e] * g;
-      if (use_batch) d -= (k0[e] + xh * k1[e]) * invc;     // same evaluation order as k_bn_bwd_apply
-      xv[e] = d * is[e];
+      if (relu && !(bn_pre(xh, ga[e], bi[e]) > 0.f)) g = 0.f;
+      xv[e] = bn_dx(g, xh, ga[e], is[e], k0[e], k1[e], invc, use_batch);     // the same evaluation as k_bn_bwd_apply
     }
     if (res) {                                                // the skip path's gradient w.r.t. the same input (see k_bn_bwd_apply)
       float rv[V];
       unpack16<T>(*(const u32x4*)(res + base + pix * C), rv);
 #pragma unroll
-      for (int e = 0; e < V; e++) xv[e] += rv[e];
+      for (int e = 0; e < V; e++) xv[e] = bn_add(xv[e], rv[e]);
     }
     *(u32x4*)(dx + base + pix * C) = pack16<T>(xv);
   };
@@ -515,8 +571,14 @@ extern "C" int sg_bn_bwd_apply_res(int dtype, const void* x, const void* dy, voi
       long long ppb = (HW + chunks - 1) / chunks; if (ppb < 4 * lanes_p) ppb = 4 * lanes_p;
       const int gx = (int)((HW + ppb - 1) / ppb);
       hipLaunchKernelGGL(k_bn_bwd_apply_stream<T>, dim3(gx, N), dim3(CV * lanes_p), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (T*)dx, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, chan, count, use_batch_stats, (int)ppb, (const T*)res);
-    } else if (vec_ok<T>(x, dy, C) && ((((uintptr_t)dx) & 15) == 0)) hipLaunchKernelGGL((k_bn_bwd_apply<T, true>), dim3(grid_for((long long)N * HW * C / ET<T>::VEC)), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (T*)dx, N, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, chan, count, use_batch_stats, (const T*)res);
-    else hipLaunchKernelGGL((k_bn_bwd_apply<T, false>), dim3(grid_for((long long)N * HW * C)), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (T*)dx, N, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, chan, count, use_batch_stats, (const T*)res);
+      bn_path_count(SG_BN_PATH_BWD_APPLY_STREAM);
+    } else if (vec_ok<T>(x, dy, C) && ((((uintptr_t)dx) & 15) == 0)) {
+      hipLaunchKernelGGL((k_bn_bwd_apply<T, true>), dim3(grid_for((long long)N * HW * C / ET<T>::VEC)), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (T*)dx, N, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, chan, count, use_batch_stats, (const T*)res);
+      bn_path_count(SG_BN_PATH_BWD_APPLY_VEC);
+    } else {
+      hipLaunchKernelGGL((k_bn_bwd_apply<T, false>), dim3(grid_for((long long)N * HW * C)), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (T*)dx, N, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, chan, count, use_batch_stats, (const T*)res);
+      bn_path_count(SG_BN_PATH_BWD_APPLY_SCALAR);
+    }
   });
   SG_LAUNCH_CHECK();
   return 0;
@@ -544,9 +606,9 @@ template <typename T> __global__ __launch_bounds__(256) void k_bn_bwd2_reduce(co
     const float bi = bias ? bias[c] : 0.f;
     const long long base = (long long)n * HW * C + c;
     for (long long r = r0 + ry; r < r1; r += 4) {
-      const float xh = (to_f<T>(x[base + r * C]) - mu) * is;
+      const float xh = bn_xhat(to_f<T>(x[base + r * C]), mu, is);
       float g = to_f<T>(dy[base + r * C]);
-      if (relu && !(xh * ga + bi > 0.f)) g = 0.f;
+      if (relu && !(bn_pre(xh, ga, bi) > 0.f)) g = 0.f;
       const float uu = to_f<T>(u[base + r * C]);
       s[0] += uu; s[1] += uu * xh; s[2] += g; s[3] += g * xh; s[4] += uu * g;
     }
@@ -610,10 +672,10 @@ template <typename T> __global__ __launch_bounds__(256) void k_bn_bwd2_apply(con
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int c = (int)(i % C);
     const float is = invstd[c];
-    const float xh = (to_f<T>(x[i]) - mean[c]) * is;
+    const float xh = bn_xhat(to_f<T>(x[i]), mean[c], is);
     const float ga = gain ? gain[c] : 1.f;
     const float bi = bias ? bias[c] : 0.f;
-    const bool on = !(relu && !(xh * ga + bi > 0.f));
+    const bool on = !(relu && !(bn_pre(xh, ga, bi) > 0.f));
     const float g = on ? to_f<T>(dy[i]) : 0.f;
     const float uu = to_f<T>(u[i]);
     float ub = 0.f, a = 0.f, gb = 0.f, cc = 0.f, m = 0.f;
@@ -658,9 +720,9 @@ template <typename T> __global__ __launch_bounds__(256) void k_cbn_bwd2_reduce(c
     const float bi = bias ? bias[(long long)n * gsn + c] : 0.f;
     const long long base = (long long)n * HW * C + c;
     for (long long r = r0 + ry; r < r1; r += 4) {
-      const float xh = (to_f<T>(x[base + r * C]) - mu) * is;
+      const float xh = bn_xhat(to_f<T>(x[base + r * C]), mu, is);
       float g = to_f<T>(dy[base + r * C]);
-      if (relu && !(xh * ga + bi > 0.f)) g = 0.f;
+      if (relu && !(bn_pre(xh, ga, bi) > 0.f)) g = 0.f;
       const float uu = to_f<T>(u[base + r * C]);
       s[0] += uu; s[1] += uu * xh; s[2] += g; s[3] += g * xh; s[4] += uu * g;
     }
@@ -778,8 +840,8 @@ template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_cbn_bw
     else { xv[0] = to_f<T>(x[o]); gv[0] = to_f<T>(dy[o]); uv[0] = to_f<T>(u[o]); }
 #pragma unroll
     for (int e = 0; e < V; e++) {
-      const float xh = (xv[e] - mu[e]) * is[e];
-      const bool on = !(relu && !(xh * ga[e] + bi[e] > 0.f));
+      const float xh = bn_xhat(xv[e], mu[e], is[e]);
+      const bool on = !(relu && !(bn_pre(xh, ga[e], bi[e]) > 0.f));
       const float g = on ? gv[e] : 0.f;
       o1[e] = on ? (P[e] * uv[e] + Q[e] * xh + R[e]) : 0.f;
       o2[e] = E1[e] * uv[e] + E2[e] * g + E3[e] * xh + E4[e];
@@ -803,6 +865,7 @@ extern "C" int sg_cbn_bwd2_apply(int dtype, const void* x, const void* dy, const
     const int gx = (int)((HW + ppb - 1) / ppb);
     if (vec) hipLaunchKernelGGL((k_cbn_bwd2_apply<T, true>), dim3(gx, N, gz), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (const T*)u, (T*)g_dy, (T*)g_x, HW, C, mean, invstd, gain, bias, A, B, gb_stride_n, relu, chan, count, use_batch_stats, (int)ppb, cvt);
     else hipLaunchKernelGGL((k_cbn_bwd2_apply<T, false>), dim3(gx, N, gz), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (const T*)u, (T*)g_dy, (T*)g_x, HW, C, mean, invstd, gain, bias, A, B, gb_stride_n, relu, chan, count, use_batch_stats, (int)ppb, cvt);
+    bn_path_count(vec ? SG_BN_PATH_CBN_BWD2_APPLY_VEC : SG_BN_PATH_CBN_BWD2_APPLY_SCALAR);
   });
   SG_LAUNCH_CHECK();
   return 0;

@@ -83,6 +83,7 @@ class Installed:
             fn.restype = C.c_int
         lib.sg_conv_rs_launches.restype = C.c_longlong
         lib.sg_ew_vec_launches.restype = C.c_longlong
+        lib.sg_bn_path_launches.restype = C.c_longlong
         lib.hipemu_config(*[int(v) for v in self.cfg[:2]], C.c_uint(self.cfg[2]))
         self.saved = (L._lib, L.ptr, L.stream, L.require_gpu)
         L._lib = lib
