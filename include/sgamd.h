@@ -51,6 +51,7 @@ typedef void* sg_stream_t; /* hipStream_t */
 #define SG_EPI_POOL 4
 #define SG_EPI_RELU 8
 #define SG_EPI_RES_F32 16
+#define SG_EPI_PLANES 32     /* the descriptor carries the sign-plane fields at its end (mask_bits, sign_out, ldmb, lds); without it they are not read */
 
 const char* sg_last_error(void);
 int sg_version(void);
@@ -74,8 +75,20 @@ typedef struct {
   const void* x; const void* w;   /* w: [Cout][R*S*C], same dtype as x */
   const float* bias; const void* res; const void* mask; void* out; const float* alpha_ptr;
   int ldo, ldr, ldm;
+  /* ---- sign planes (bf16; read only with SG_EPI_PLANES in epi_flags) ----
+   * The plane of a bf16 NHWC tensor t[P pixels][C] is uint32 plane[P][ld], ld >= ceil(C / 32): bit c & 31 of word c >> 5 = (t[p][c] > 0), the ReLU mask
+   * exactly as the masked epilogues take it (false for +-0, negatives and NaN); bits of channels >= C are zero. 1/16 of the tensor's bytes.
+   * mask_bits / ldmb: the plane of `mask`. A kernel whose epilogue is the tile epilogue (conv_v2 / v3 / v4 / quad) reads it INSTEAD of `mask`; every other
+   *   engine ignores it and reads `mask`: pass both.
+   * sign_out / lds: where the same kernels write the plane of the result next to `out` (rows of pixels the launch does not write stay untouched). The
+   *   other engines write nothing: sg_sign_plane_launches(0) tells whether a launch did. */
+  const void* mask_bits; void* sign_out;
+  int ldmb, lds;
 } sg_conv_fwd_desc;
 int sg_conv2d_fwd(const sg_conv_fwd_desc* d, sg_stream_t stream);
+/* sign-plane launch counts so far (relaxed atomic counters, for tests and benchmarks): what = 0: forward launches that wrote sign_out; 1: masked launches
+ * that read mask_bits; 2: masked launches that read the activation `mask`; anything else: -1 */
+long long sg_sign_plane_launches(int what);
 /* fp32 arithmetic of the generic engine (process-wide; default 0): 0 = v_mfma_f32_32x32x2_f32, the exact fp32 FMA chain; 3 = "bf16x3": each fp32
  * operand element is split into two bf16 terms in registers and a 16-wide k-tile runs as three bf16 MFMAs with fp32 accumulation (~2^-16 relative per
  * product, 5.3x the matrix-pipe rate); convolutions only (forward, data gradient, weight gradient). 6 = "bf16x6": three bf16 terms per element
@@ -104,6 +117,7 @@ typedef struct {
   sg_conv_fwd_desc main;
   const void* x2; const void* w2; const float* bias2;
   int C2, ldx2, x2_up;
+  /* (main.sign_out / main.lds: the plane of the fused result -- the nested descriptor's own fields, there is no second pair here) */
   float* stats;   /* optional: [sg_conv2d_fwd_skip_stat_rows()][Cout][2] floats, per 256-pixel tile the sum and the sum of squares of the (bf16) result
                      per channel -- the statistics of the batch norm behind this convolution, taken in the epilogue (no extra pass over the
                      activation); reduce with sg_bn_stats_from_tiles. Ignored with SG_EPI_POOL. */
@@ -171,6 +185,9 @@ typedef struct {
   float* stats;   /* optional: per-tile batch-norm statistics of the result, [sg_conv2d_q_stat_rows()][Cout][2] floats (see sg_conv_skip_desc) */
   int x2_norelu;  /* 1: SG_PIX_RELU applies to x only, not to the skip input (the first discriminator block: the skip reads the image). With C2 == 8
                      (the RGB image padded to 8 channels) w2q is [Cout][4][8] = sg_quad_pack_batch mode 5 */
+  /* sign planes as sg_conv_fwd_desc has them, read only with SG_EPI_PLANES. SG_Q_UP: the planes are planes of the FINE grid, like mask / res / out */
+  const void* mask_bits; void* sign_out;
+  int ldmb, lds;
 } sg_convq_desc;
 int sg_conv2d_q_stat_rows(const sg_convq_desc* d);
 int sg_conv2d_q(const sg_convq_desc* d, sg_stream_t stream);

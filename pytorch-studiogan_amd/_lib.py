@@ -19,7 +19,7 @@ CSRC = os.path.join(_HERE, "csrc")
 F32, BF16, F64 = 0, 1, 2
 PIX_RELU, PIX_UPSAMPLE, PIX_QUAD, PIX_TRANSPOSED = 1, 2, 4, 8
 Q_POOL, Q_UP = 0, 1
-EPI_OUT_F32, EPI_ATOMIC, EPI_POOL, EPI_RELU, EPI_RES_F32 = 1, 2, 4, 8, 16
+EPI_OUT_F32, EPI_ATOMIC, EPI_POOL, EPI_RELU, EPI_RES_F32, EPI_PLANES = 1, 2, 4, 8, 16, 32
 
 _vp, _i, _f, _ll = C.c_void_p, C.c_int, C.c_float, C.c_longlong
 
@@ -28,7 +28,8 @@ class ConvFwdDesc(C.Structure):
     _fields_ = [("dtype", _i), ("N", _i), ("Hs", _i), ("Ws", _i), ("C", _i), ("ldx", _i), ("Ho", _i), ("Wo", _i), ("Cout", _i),
                 ("R", _i), ("S", _i), ("stride", _i), ("pad_h", _i), ("pad_w", _i), ("pix_flags", _i), ("epi_flags", _i),
                 ("alpha", _f), ("beta", _f), ("x", _vp), ("w", _vp), ("bias", _vp), ("res", _vp), ("mask", _vp), ("out", _vp),
-                ("alpha_ptr", _vp), ("ldo", _i), ("ldr", _i), ("ldm", _i)]
+                ("alpha_ptr", _vp), ("ldo", _i), ("ldr", _i), ("ldm", _i),
+                ("mask_bits", _vp), ("sign_out", _vp), ("ldmb", _i), ("lds", _i)]      # sign planes: read only with EPI_PLANES
 
 
 class ConvSkipDesc(C.Structure):
@@ -50,7 +51,8 @@ class ConvQDesc(C.Structure):
     _fields_ = [("dtype", _i), ("form", _i), ("N", _i), ("Hl", _i), ("Wl", _i), ("C", _i), ("ldx", _i), ("Cout", _i),
                 ("pix_flags", _i), ("epi_flags", _i), ("alpha", _f), ("beta", _f), ("x", _vp), ("wq", _vp), ("bias", _vp), ("res", _vp),
                 ("mask", _vp), ("out", _vp), ("alpha_ptr", _vp), ("ldo", _i), ("ldr", _i), ("ldm", _i),
-                ("x2", _vp), ("w2q", _vp), ("bias2", _vp), ("C2", _i), ("ldx2", _i), ("stats", _vp), ("x2_norelu", _i)]
+                ("x2", _vp), ("w2q", _vp), ("bias2", _vp), ("C2", _i), ("ldx2", _i), ("stats", _vp), ("x2_norelu", _i),
+                ("mask_bits", _vp), ("sign_out", _vp), ("ldmb", _i), ("lds", _i)]
 
 
 class ConvQWgradDesc(C.Structure):
@@ -119,6 +121,7 @@ _PROTOS = {
     "sg_conv2d_fwd_skip": [C.POINTER(ConvSkipDesc), _vp],
     "sg_conv2d_fwd_skip_ok": [C.POINTER(ConvSkipDesc)],
     "sg_conv_rs_launches": [],
+    "sg_sign_plane_launches": [_i],                        # returns a count
     "sg_modconv2d_fwd": [C.POINTER(ModConvDesc), _vp],
     "sg_modconv2d_ok": [C.POINTER(ModConvDesc)],
     "sg_modconv_launches": [],                             # returns a count
@@ -327,6 +330,7 @@ def lib():
             fn.argtypes = args
             fn.restype = _i
         l.sg_conv_rs_launches.restype = _ll
+        l.sg_sign_plane_launches.restype = _ll
         l.sg_modconv_launches.restype = _ll
         l.sg_tok_gemm_launches.restype = _ll
         l.sg_mha_launches.restype = _ll

@@ -196,8 +196,12 @@ class DiscOptBlock(nn.Module):
         if self.cpad:
             self.conv2d1._sg_cin_pad = self.conv2d0._sg_cin_pad = self.cpad
 
-    def forward_nhwc(self, x, slot):
-        h = self.conv2d1.forward_nhwc(x, slot)
+    def forward_nhwc(self, x, slot, planes=False, x_plane=None, out_plane=None):
+        """planes: work with sign planes (Discriminator.forward decides). out_plane: an empty functional.SignPlane for the plane of the block's output, given
+        when the next block reads it with ReLU-on-load; x_plane is unused (the image takes no ReLU)"""
+        # h is read with ReLU-on-load by conv2d2, whose data gradient masks with it: its plane travels from conv2d1 to the block tail
+        hp = F.SignPlane() if (planes and self.apply_d_sn) else None
+        h = self.conv2d1.forward_nhwc(x, slot, out_plane=hp)
         if not self.apply_d_sn:
             h = self.bn1.forward_nhwc(h, relu=True)
             h = self.conv2d2.forward_nhwc(h, slot, out_pool=True)
@@ -205,12 +209,12 @@ class DiscOptBlock(nn.Module):
             if self.cpad == 8 and h.dtype == torch.bfloat16 and not x.requires_grad:      # (an image that wants its gradient -- gradient penalty, R1 -- keeps the chain below)
                 # pool(conv2d2(relu h)) + conv2d0(pool x) = pool(conv2d2(relu h) + conv2d0(x)): pooling is linear, so the skip on the image rides in
                 # the block tail's launch like the other blocks' (functional.ConvSkipFn; the skip input takes no ReLU here)
-                return ops.conv_skip_nhwc(self.conv2d2, self.conv2d0, h, x, slot, in_relu=True, out_pool=True, skip_relu=False)
-            h = self.conv2d2.forward_nhwc(h, slot, in_relu=True, out_pool=True)
+                return ops.conv_skip_nhwc(self.conv2d2, self.conv2d0, h, x, slot, in_relu=True, out_pool=True, skip_relu=False, h_plane=hp, out_plane=out_plane)
+            h = self.conv2d2.forward_nhwc(h, slot, in_relu=True, out_pool=True, x_plane=hp)
         x0 = F.AvgPool2Fn.apply(x)
         if not self.apply_d_sn:
             x0 = self.bn0.forward_nhwc(x0)
-        return self.conv2d0.forward_nhwc(x0, slot, res=h)
+        return self.conv2d0.forward_nhwc(x0, slot, res=h, out_plane=out_plane if self.apply_d_sn else None)
 
 
 class DiscBlock(nn.Module):
@@ -231,17 +235,22 @@ class DiscBlock(nn.Module):
             self.bn2 = MODULES.d_bn(in_features=out_channels)
         self.average_pooling = nn.AvgPool2d(2)
 
-    def forward_nhwc(self, x, slot):
+    def forward_nhwc(self, x, slot, planes=False, x_plane=None, out_plane=None):
+        """planes, out_plane: as DiscOptBlock.forward_nhwc; x_plane: the functional.SignPlane that came with x (or None)"""
         if self.apply_d_sn:
             # nn.ReLU(inplace=True) on x also rewrites the skip tensor x0 (same storage) in the reference:
             # both paths see relu(x)  (reference big_resnet.py:221-242, config.py:476)
+            # sign planes: conv2d1 and conv2d2 read x / h with ReLU-on-load and mask their data gradients with them -- x's plane comes from the block before,
+            # h's is written by conv2d1.
+            hp = F.SignPlane() if planes else None
             if self.downsample or self.ch_mismatch:
                 link = F.GradLink()      # x feeds conv2d1 and the skip: conv2d1's data gradient takes the skip's gradient as its residual
-                h = self.conv2d1.forward_nhwc(x, slot, in_relu=True, link=link)
+                h = self.conv2d1.forward_nhwc(x, slot, in_relu=True, link=link, x_plane=x_plane, out_plane=hp)
                 # pool(conv2d2(relu h)) + pool(conv2d0(relu x)) = pool(conv2d2(relu h) + conv2d0(relu x)): one launch (functional.ConvSkipFn)
-                return ops.conv_skip_nhwc(self.conv2d2, self.conv2d0, h, x, slot, in_relu=True, out_pool=self.downsample, link=link)
-            h = self.conv2d1.forward_nhwc(x, slot, in_relu=True)
-            h = self.conv2d2.forward_nhwc(h, slot, in_relu=True, out_pool=False)
+                return ops.conv_skip_nhwc(self.conv2d2, self.conv2d0, h, x, slot, in_relu=True, out_pool=self.downsample, link=link,
+                                          h_plane=hp, x_plane=x_plane, out_plane=out_plane)
+            h = self.conv2d1.forward_nhwc(x, slot, in_relu=True, x_plane=x_plane, out_plane=hp)
+            h = self.conv2d2.forward_nhwc(h, slot, in_relu=True, out_pool=False, x_plane=hp)
             return F.AddReluFn.apply(h, x)
         h = self.bn1.forward_nhwc(x, relu=True)
         h = self.conv2d1.forward_nhwc(h, slot)
@@ -307,12 +316,27 @@ class Discriminator(nn.Module):
     def forward(self, x, label, eval=False, adc_fake=False):
         dtype = self.compute_dtype
         bank = get_bank(self, dtype)
-        slot = bank.begin_forward(_need_graph(self, x))
+        need_graph = _need_graph(self, x)
+        slot = bank.begin_forward(need_graph)
         h = ops.to_nhwc(x, dtype, self.blocks[0][0].cpad)
         nxt = bank.boundaries(self.blocks) if bank.exchange is not None else None
+        # sign planes (functional.SignPlane): a block whose output the NEXT block reads with ReLU-on-load writes that output's plane, and the plane is handed
+        # to that block explicitly, next to the activation. Only where a backward will run (a graph is recorded), in bf16; a self-attention block neither
+        # takes nor gives one, so the block behind it masks with the activation. `plane` always stands for the tensor `h` of that moment -- and
+        # SignPlane.bits_for checks it again at the consumer (bank.mark / a test's teacher may hand on another tensor).
+        planes = dtype == torch.bfloat16 and need_graph and F.sign_planes_on()
+        flat = [b for bl in self.blocks for b in bl]
+        plane, k = None, 0
         for bi, blocklist in enumerate(self.blocks):
             for block in blocklist:
-                h = block.forward_nhwc(h, slot)
+                if isinstance(block, ops.SelfAttention):
+                    h, plane = block.forward_nhwc(h, slot), None
+                else:
+                    follower = flat[k + 1] if k + 1 < len(flat) else None
+                    out_plane = F.SignPlane() if (planes and isinstance(follower, DiscBlock) and follower.apply_d_sn) else None
+                    h = block.forward_nhwc(h, slot, planes=True, x_plane=plane, out_plane=out_plane) if planes else block.forward_nhwc(h, slot)
+                    plane = out_plane
+                k += 1
             if nxt is not None:
                 h = bank.mark(h, nxt[bi])          # data parallelism: the backward's return to this point releases the gradients behind it
             h = ops.block_boundary(self, bi, h)

@@ -44,6 +44,15 @@ __device__ __forceinline__ uint32_t pack2bf(float a, float b) {
 template <typename T> __device__ __forceinline__ float to_f(T v);
 template <> __device__ __forceinline__ float to_f<float>(float v) { return v; }
 template <> __device__ __forceinline__ float to_f<bf16_t>(bf16_t v) { return bf2f(v); }
+// the ReLU mask of a stored bf16 activation, as every masked epilogue and the sign-plane producers take it: false for +-0, negatives and NaN
+__device__ __forceinline__ bool sg_relu_pos(bf16_t h) { return bf2f(h) > 0.f; }
+// bits e = sg_relu_pos(element e) of the 8 bf16 values of a 16-byte chunk (element 2 d + {0, 1} = low / high half of dword d)
+__device__ __forceinline__ uint32_t sg_relu_pos8(u32x4 v) {
+  uint32_t b = 0u;
+#pragma unroll
+  for (int e = 0; e < 8; e++) b |= sg_relu_pos((bf16_t)((v[e >> 1] >> (16 * (e & 1))) & 0xffffu)) ? (1u << e) : 0u;
+  return b;
+}
 template <typename T> __device__ __forceinline__ T from_f(float v);
 template <> __device__ __forceinline__ float from_f<float>(float v) { return v; }
 template <> __device__ __forceinline__ bf16_t from_f<bf16_t>(float v) { return f2bf(v); }

@@ -15,6 +15,12 @@ extern "C" int sg_set_f32_mode(int mode) {
   return 0;
 }
 extern "C" int sg_get_f32_mode() { return g_sg_f32_mode; }
+// sign planes (conv_common.h sg_sign_plane_count): [0] launches that wrote a plane, [1] masked launches that read one, [2] masked launches that read the activation
+long long g_sg_sign_plane_launches[3] = {0, 0, 0};
+extern "C" long long sg_sign_plane_launches(int what) {
+  if (what < 0 || what > 2) return -1;
+  return __atomic_load_n(&g_sg_sign_plane_launches[what], __ATOMIC_RELAXED);
+}
 extern "C" long long sg_f32_split_launches(int mode) {
   if (mode != 3 && mode != 6) return -1;
   return __atomic_load_n(&g_sg_f32_split_launches[mode == 6], __ATOMIC_RELAXED);
@@ -136,6 +142,7 @@ template <typename T> static int conv_fwd_t(const sg_conv_fwd_desc* d, hipStream
     sg_prof_tag(prof, eng, b);
   }
   sg_prof_end(st, prof);
+  if constexpr (std::is_same_v<T, bf16_t>) sg_sign_plane_count(e, eng == SG_ENG_CONV_V4 || (eng == SG_ENG_CONV_V3 && I > 32) || eng == SG_ENG_CONV_V2, eng == SG_ENG_CONV_SK);      // (conv_v3's 32-cout tile: no plane code)
   SG_LAUNCH_CHECK();
   return 0;
 }
@@ -160,6 +167,7 @@ static int conv_fwd_skip(const sg_conv_skip_desc* sk, hipStream_t st, bool dry) 
     sg_prof_tag(prof, SG_ENG_CONV_V4_SKIP, 2.0 * ((double)d->N * d->Hs * d->Ws * d->C + x2 + (double)I * (K + sk->C2) + jout * I));
   }
   sg_prof_end(st, prof);
+  if (ok) sg_sign_plane_count(pb.e, true);
   return ok ? 1 : 0;
 }
 // rows of the per-tile statistics buffer a fused launch with d->stats writes ([rows][Cout][2] floats): 256-pixel tiles

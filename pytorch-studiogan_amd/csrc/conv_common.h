@@ -3,6 +3,7 @@
 // `make -j` at the longest single family (~1.5 min) instead of their sum.
 #pragma once
 #include <stdlib.h>
+#include <type_traits>
 #include "gemm_core.h"
 #include "../../include/sgamd.h"
 
@@ -66,8 +67,23 @@ template <typename T, typename D> static Epilogue<T> make_epilogue(const D* d, i
   e.out = d->out; e.out_bstride = 0; e.ldo = d->ldo; e.bias = d->bias;
   e.res = d->res; e.res_bstride = 0; e.ldr = d->ldr; e.beta = d->beta;
   e.mask = (const T*)d->mask; e.mask_bstride = 0; e.ldm = d->ldm; e.split_stride = 0;
-  e.alpha = d->alpha; e.alpha_ptr = d->alpha_ptr; e.flags = d->epi_flags; e.I = I; e.J = J;
+  e.alpha = d->alpha; e.alpha_ptr = d->alpha_ptr; e.flags = d->epi_flags & ~SG_EPI_PLANES; e.I = I; e.J = J;
+  // sign planes: the trailing descriptor fields are read only behind SG_EPI_PLANES (a caller built against the shorter descriptor never sets it).
+  // A plane the kernels cannot address (bf16 only; dword rows; fewer words than channels) is dropped here: the launch then runs as if it had not been given.
+  const bool planes = std::is_same_v<T, bf16_t> && (d->epi_flags & SG_EPI_PLANES);
+  const int nw = (I + 31) >> 5;
+  const bool mb = planes && d->mask && d->mask_bits && d->ldmb >= nw && !((uintptr_t)d->mask_bits & 3);
+  const bool so = planes && d->sign_out && d->lds >= nw && !((uintptr_t)d->sign_out & 3);
+  e.mask_bits = mb ? (const uint32_t*)d->mask_bits : nullptr; e.ldmb = mb ? d->ldmb : 0;
+  e.sign_out = so ? (uint32_t*)d->sign_out : nullptr; e.lds = so ? d->lds : 0;
   return e;
+}
+// sign-plane bookkeeping of a forward / data-gradient launch (sg_sign_plane_launches): epilogue_planes = the engine that took the problem ends in
+// sg_conv_epilogue (conv_v2 / v3 / v4 / v4 skip / quad), which reads and writes planes; the streaming kernel (conv_sk.h) writes them but reads the activation
+extern long long g_sg_sign_plane_launches[3];
+static inline void sg_sign_plane_count(const Epilogue<bf16_t>& e, bool epilogue_planes, bool writes_only = false) {      // writes_only: conv_sk (a producer, not a consumer)
+  if (e.sign_out && (epilogue_planes || writes_only)) __atomic_fetch_add(&g_sg_sign_plane_launches[0], 1, __ATOMIC_RELAXED);
+  if (e.mask) __atomic_fetch_add(&g_sg_sign_plane_launches[(e.mask_bits && epilogue_planes) ? 1 : 2], 1, __ATOMIC_RELAXED);
 }
 // the only epilogue of the tile / halo / streaming / quad kernels (sg_conv_epilogue): bf16 rows, 16-byte stores; the ReLU-mask and the residual tile (bf16)
 // are pre-staged with 16-byte loads (both together: the mask tile is condensed to register bits, then the residual tile is staged)

@@ -178,7 +178,7 @@ static bool convq_plan(const sg_convq_desc* d, ConvQParams& p, Epilogue<bf16_t>&
   if (4 * J >= (1ll << 29)) return false;
   const long long xbytes = bf16_extent(npix_x, d->ldx, d->C), wbytes = (long long)d->Cout * 16 * d->C * 2;
   if (xbytes >= (1ll << 31) || wbytes >= (1ll << 31)) return false;
-  if ((d->epi_flags & ~SG_EPI_RELU) || (d->pix_flags & ~SG_PIX_RELU)) return false;
+  if ((d->epi_flags & ~(SG_EPI_RELU | SG_EPI_PLANES)) || (d->pix_flags & ~SG_PIX_RELU)) return false;
   e = make_epilogue<bf16_t>(d, d->Cout, (int)J);
   if (!epi_bf16_rows_ok(e)) return false;
   NB = cout_blocks(d->Cout);
@@ -251,6 +251,7 @@ extern "C" int sg_conv2d_q(const sg_convq_desc* d, sg_stream_t stream) {
                 2.0 * (jin * d->C + (d->x2 ? 4.0 * J * d->C2 + (double)d->Cout * d->C2 : 0.0) + 16.0 * d->C * d->Cout + jout * d->Cout * (1.0 + (d->mask ? 1.0 : 0.0) + (d->res ? 1.0 : 0.0))));
   }
   sg_prof_end(st, prof);
+  if (rc == 0) sg_sign_plane_count(e, true);
   SG_CHECK(rc == 0, "sg_conv2d_q: launch failed");
   SG_LAUNCH_CHECK();
   return 0;

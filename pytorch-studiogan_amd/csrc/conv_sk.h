@@ -28,11 +28,13 @@ struct ConvSkParams {
   int I, J, K;
   unsigned xbytes;
   unsigned obytes, sbytes;     // extents of the output tensor and of the mask / residual tensor (< 2^31: bit 31 of an offset = skip)
+  unsigned pbytes;             // extent of the result's sign plane (Epilogue::sign_out), 0 = none
   int nrb;                     // row blocks of 32 * TJ pixels
 };
 
 // TI x 32 couts per accumulator pass, NP passes over the same pixel fragments (cout tile = TI * NP * 32)
-template <int TI, int NP, int TJ, int KS, int NW, bool POOL>
+// PLANE: the instantiation that also writes the result's sign plane (Epilogue::sign_out); without it the kernel is the code it was before planes existed
+template <int TI, int NP, int TJ, int KS, int NW, bool POOL, bool PLANE = false>
 __global__ __launch_bounds__(64 * NW) void sg_conv_sk_kernel(ConvSkParams p, Epilogue<bf16_t> epi) {
   constexpr int BI = TI * NP * 32;
   constexpr int NCH = 2 * KS;              // 16-byte k-chunks
@@ -62,6 +64,17 @@ __global__ __launch_bounds__(64 * NW) void sg_conv_sk_kernel(ConvSkParams p, Epi
   const auto rso = __builtin_amdgcn_make_buffer_rsrc(epi.out, 0, (int)p.obytes, 0x00020000);
   const auto rss = __builtin_amdgcn_make_buffer_rsrc((void*)(epi.mask ? (const void*)epi.mask : epi.res), 0, (int)p.sbytes, 0x00020000);
   constexpr int NIT = ((POOL ? ROWS / 4 : ROWS) * CPR + 63) / 64;      // 16-byte pieces of a staged pass tile per lane
+  // sign plane of the result (Epilogue::sign_out; the RGB stem writes the largest ReLU mask of a discriminator backward): one dword = the 32 couts of one
+  // accumulator block of one output row, TI words per row and pass. Without a plane the descriptor is empty (0 bytes) and every plane store is dropped.
+  const auto rsp = __builtin_amdgcn_make_buffer_rsrc((void*)(PLANE ? epi.sign_out : nullptr), 0, PLANE ? (int)p.pbytes : 0, 0x00020000);
+  constexpr int NITP = ((POOL ? ROWS / 4 : ROWS) * TI + 63) / 64;      // plane words of a staged pass tile per lane
+  auto plane_store = [&](uint32_t w, unsigned off) {
+#if __has_builtin(__builtin_amdgcn_raw_buffer_store_b32)
+    __builtin_amdgcn_raw_buffer_store_b32(w, rsp, (int)off, 0, 0);
+#else      // (a compiler without the builtin: the same store in plain C++, the descriptor's range check written out)
+    if (off < p.pbytes) *(uint32_t*)((char*)epi.sign_out + off) = w;
+#endif
+  };
   const int frow = lane & 31, fhi = lane >> 5;
   const unsigned ldx2 = 2u * (unsigned)p.ldx;
   const bool up = (p.flags & SG_PIX_UPSAMPLE) != 0, quad = (p.flags & SG_PIX_QUAD) != 0;
@@ -258,6 +271,28 @@ __global__ __launch_bounds__(64 * NW) void sg_conv_sk_kernel(ConvSkParams p, Epi
         const u32x4 v = *(const u32x4*)(stg + rr * CP + c * 16);
         __builtin_amdgcn_raw_buffer_store_b128(v, rso, (int)off, 0, 0);
       }
+      // The pass tile's sign plane: the same row pass over the staging tile as sg_conv_epilogue makes (conv_v2.h), issued like the tile stores above -- NITP
+      // dword stores per lane and pass, whatever the data; a lane without a word (rows past the tile or the problem, a word whose couts do not exist, no
+      // plane at all) carries an out-of-range offset and its store is dropped. The staging reads need no wait of their own: the tile is complete since the
+      // lgkmcnt(0) in front of the tile stores, and the next pass waits for these reads before it overwrites the tile.
+#pragma unroll
+      for (int it = 0; it < (PLANE ? NITP : 0); it++) {
+        const int idx = lane + 64 * it;
+        const int r = idx / TI, k = idx - r * TI;
+        const int jg = jbase + r;
+        const bool ok = idx < rows_out * TI && jg < Jout && 4 * k < ncp;
+        const int rr = idx < rows_out * TI ? r : 0;
+        uint32_t w = 0u;
+#pragma unroll 1      // (one 16-byte chunk in registers at a time: unrolled, the reads of all words are hoisted and cost the kernel a wave per SIMD)
+        for (int c = 0; c < 4; c++) {
+          const uint32_t b = sg_relu_pos8(*(const u32x4*)(stg + rr * CP + (4 * k + c) * 16));
+          w |= (4 * k + c < ncp) ? b << (8 * c) : 0u;
+        }
+        const int left = epi.I - (i0 + ic0 + 32 * k);      // couts of this word that exist (a last 16-byte chunk may be only partly inside the problem)
+        w = (left > 0 && left < 32) ? (w & ((1u << left) - 1u)) : w;
+        const unsigned off = ok ? ((unsigned)jg * (unsigned)epi.lds + (unsigned)((i0 + ic0) >> 5) + (unsigned)k) * 4u : 0x80000000u;
+        plane_store(w, off);
+      }
     }
   };
 
@@ -268,11 +303,21 @@ __global__ __launch_bounds__(64 * NW) void sg_conv_sk_kernel(ConvSkParams p, Epi
   fetch(rb, qa);
   // as many (dropped: out-of-range) stores as one row block issues, so that the loop is entered with the same vmcnt history it has
   // on its back edge -- otherwise the compiler's merged state assumes "no stores in flight" and the first wait of every other
-  // iteration drains them
+  // iteration drains them.
+  // The waits themselves are the compiler's: vmcnt retires in order, and the wait in front of a block's first MFMA has to retire that block's fragment
+  // loads, which were issued BEFORE the previous block's stores -- so it may leave exactly the stores issued since in flight. A row block issues, per
+  // pass, [NIT operand loads,] NIT tile stores and NITP plane stores, always, in that order: NP * (NIT + NITP) stores behind the youngest fragment load
+  // (plus NP * NIT operand loads with a mask / residual, which the pass itself waits for). The prologue below reproduces that history with dropped stores
+  // of both kinds, in the block's order, so entry and back edge agree and the count the compiler derives is the same constant on both.
 #pragma unroll
-  for (int it = 0; it < NP * NIT; it++) {
-    const u32x4 z = {0u, 0u, 0u, 0u};
-    __builtin_amdgcn_raw_buffer_store_b128(z, rso, (int)(0x80000000u + 16u * it), 0, 0);     // (distinct offsets: identical stores get merged)
+  for (int it = 0; it < NP; it++) {
+#pragma unroll
+    for (int k = 0; k < NIT; k++) {
+      const u32x4 z = {0u, 0u, 0u, 0u};
+      __builtin_amdgcn_raw_buffer_store_b128(z, rso, (int)(0x80000000u + 16u * (it * NIT + k)), 0, 0);     // (distinct offsets: identical stores get merged)
+    }
+#pragma unroll
+    for (int k = 0; k < (PLANE ? NITP : 0); k++) plane_store(0u, 0x80000000u + 4u * (unsigned)(it * NITP + k));
   }
   while (true) {
     fetch(rb + stride, qb);
@@ -286,7 +331,7 @@ __global__ __launch_bounds__(64 * NW) void sg_conv_sk_kernel(ConvSkParams p, Epi
   }
 }
 
-template <int TI, int NP, int TJ, int KS, bool POOL>
+template <int TI, int NP, int TJ, int KS, bool POOL, bool PLANE>
 static inline int sg_launch_conv_sk_tp(ConvSkParams p, const Epilogue<bf16_t>& e, hipStream_t st) {
   constexpr int BI = TI * NP * 32, WP = KS * 32 + 16, CP = TI * 64 + 16, ROWS = 32 * TJ;
   // 8 waves per CU (2 per SIMD: the register budget): two 4-wave workgroups when their LDS fits twice, else one 8-wave workgroup
@@ -297,7 +342,7 @@ static inline int sg_launch_conv_sk_tp(ConvSkParams p, const Epilogue<bf16_t>& e
   static_assert(lds <= 160 * 1024, "LDS");
   static bool attr_done = false;
   if (!attr_done) {
-    if (hipFuncSetAttribute((const void*)sg_conv_sk_kernel<TI, NP, TJ, KS, NW, POOL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -1;
+    if (hipFuncSetAttribute((const void*)sg_conv_sk_kernel<TI, NP, TJ, KS, NW, POOL, PLANE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -1;
     attr_done = true;
   }
   p.nrb = (p.J + ROWS - 1) / ROWS;
@@ -305,12 +350,13 @@ static inline int sg_launch_conv_sk_tp(ConvSkParams p, const Epilogue<bf16_t>& e
   int gx = (p.nrb + NW - 1) / NW;
   const int cap = (256 * (8 / NW) + tilesI - 1) / tilesI;
   if (gx > cap) gx = cap;
-  hipLaunchKernelGGL((sg_conv_sk_kernel<TI, NP, TJ, KS, NW, POOL>), dim3(gx, tilesI), dim3(64 * NW), lds, st, p, e);
+  hipLaunchKernelGGL((sg_conv_sk_kernel<TI, NP, TJ, KS, NW, POOL, PLANE>), dim3(gx, tilesI), dim3(64 * NW), lds, st, p, e);
   return 0;
 }
 template <int TI, int NP, int TJ, int KS>
 static inline int sg_launch_conv_sk_t(const ConvSkParams& p, const Epilogue<bf16_t>& e, hipStream_t st) {
-  return (e.flags & SG_EPI_POOL) ? sg_launch_conv_sk_tp<TI, NP, TJ, KS, true>(p, e, st) : sg_launch_conv_sk_tp<TI, NP, TJ, KS, false>(p, e, st);
+  if (e.sign_out) return (e.flags & SG_EPI_POOL) ? sg_launch_conv_sk_tp<TI, NP, TJ, KS, true, true>(p, e, st) : sg_launch_conv_sk_tp<TI, NP, TJ, KS, false, true>(p, e, st);
+  return (e.flags & SG_EPI_POOL) ? sg_launch_conv_sk_tp<TI, NP, TJ, KS, true, false>(p, e, st) : sg_launch_conv_sk_tp<TI, NP, TJ, KS, false, false>(p, e, st);
 }
 
 // cout tile 32 / 64 / 96 (one pass) or 128 / 192 (two passes of 64 / 96); KS in {1,3,6,12} (K <= 16/48/96/192); TJ = 2 (64-pixel

@@ -25,9 +25,10 @@ bool sg_conv_fwd_sk_try(const ConvFwdProblem& pb, hipStream_t st) {
   const long long jout = (e.flags & SG_EPI_POOL) ? (J >> 2) : J;
   const long long obytes = bf16_extent(jout, e.ldo, I);
   const long long sbytes = e.mask ? bf16_extent(jout, e.ldm, I) : (e.res ? bf16_extent(jout, e.ldr, I) : 16);
-  if (obytes >= (1ll << 31) || sbytes >= (1ll << 31)) return false;
+  const long long pbytes = e.sign_out ? ((jout - 1) * e.lds + ((I + 31) >> 5)) * 4 : 0;      // the result's sign plane: dword rows of pitch lds
+  if (obytes >= (1ll << 31) || sbytes >= (1ll << 31) || pbytes >= (1ll << 31)) return false;
   ConvSkParams p;
-  p.obytes = (unsigned)obytes; p.sbytes = (unsigned)sbytes;
+  p.obytes = (unsigned)obytes; p.sbytes = (unsigned)sbytes; p.pbytes = (unsigned)pbytes;
   p.x = (const bf16_t*)d->x; p.w = (const bf16_t*)d->w;
   p.C = d->C; p.ldx = d->ldx; p.Hs = d->Hs; p.Ws = d->Ws;
   p.Ho = d->Ho; p.Wo = d->Wo; p.wshift = pb.wshift; p.hshift = pb.hshift;

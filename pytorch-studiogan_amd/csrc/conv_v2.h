@@ -40,7 +40,8 @@ typedef __attribute__((address_space(3))) void* sg_lptr_t;
 // buffers, reused as the output staging area; sbias: BI floats in LDS (valid when epi.bias).
 // VMAP (conv_q.h, UP form): the tile's rows are positions of a LOW-resolution grid and the output / mask / residual tensors are one parity
 // view of the tensor at twice the resolution: global row of tile row jg = ((jg >> vlog) << (vlog + 2)) + ((jg & (2^vlog - 1)) << 1) + vadd.
-template <int BI, int BJ, int NW, int TI, int TJ, bool VMAP = false, bool NOSTORE = false>      // NOSTORE: ablation only (conv_v4.h ABL bit 5)
+// PLANES = false: compiled without the sign-plane code (Epilogue::mask_bits / sign_out are ignored: the mask is read from the activation, no plane is written).
+template <int BI, int BJ, int NW, int TI, int TJ, bool VMAP = false, bool NOSTORE = false, bool PLANES = true>      // NOSTORE: ablation only (conv_v4.h ABL bit 5)
 __device__ __forceinline__ void sg_conv_epilogue(f32x16 (&acc)[TI][TJ], char* smem, const float* sbias, const Epilogue<bf16_t>& epi,
                                                  int i0, int j0, int wi0, int wj0, float al, int vlog = 0, int vadd = 0,
                                                  float* stats = nullptr, int stats_C = 0, int stats_row = 0) {
@@ -56,7 +57,6 @@ __device__ __forceinline__ void sg_conv_epilogue(f32x16 (&acc)[TI][TJ], char* sm
   // (the generic one was 19 k of the kernel's 21 k instructions -- fetched by every workgroup of a short-K layer).
   const bool pool = (epi.flags & SG_EPI_POOL) != 0;
   constexpr int CP = BI * 2 + 16;              // LDS row pitch of the staged tile (bytes)
-  __syncthreads();                             // every wave is done reading the operand buffers
   // ReLU-mask / residual operand of the epilogue: its tile is fetched with the SAME coalesced 16-byte pattern as the output store,
   // into the output staging area; a lane then finds the four values it needs at the very LDS location it is going to overwrite
   // with its result (each (row, 4-channel group) location belongs to exactly one lane, so the update is in place).
@@ -82,7 +82,27 @@ __device__ __forceinline__ void sg_conv_epilogue(f32x16 (&acc)[TI][TJ], char* sm
   uint32_t mbits[TI * TJ];
 #pragma unroll
   for (int q = 0; q < TI * TJ; q++) mbits[q] = 0u;
-  if (pre_both) {
+  // The mask as a sign plane (Epilogue::mask_bits: one bit per element, 1/16 of the activation's bytes): no staging and no barrier. Every lane loads, per
+  // accumulator block, the ONE dword that holds the block's 32 channels of its pixel and keeps its own 16 bits in the layout the mask-and-residual path
+  // condenses a staged tile to (bit 4 g4 + e = channel 8 g4 + 4 (lane >> 5) + e of the block). Requested in front of the barrier that frees the operand
+  // buffers, so the round trip runs while the workgroup's other waves finish their last k-tile.
+  const bool plane = PLANES && pre_mask && epi.mask_bits != nullptr;
+  if (plane) {
+#pragma unroll
+    for (int ta = 0; ta < TI; ta++)
+#pragma unroll
+      for (int tb = 0; tb < TJ; tb++) {
+        const int jl = wj0 + tb * 32 + (lane & 31);
+        const int jg = jbase + (pool ? (jl >> 2) : jl);
+        const int ib = i0 + wi0 + ta * 32;                 // first channel of the block: a multiple of 32 (cout tiles and wave blocks are)
+        uint32_t w = 0u;
+        if (jg < Jout && ib < epi.I) w = epi.mask_bits[grow(jg) * epi.ldmb + (ib >> 5)];
+        w >>= 4 * (lane >> 5);
+        mbits[ta * TJ + tb] = (w & 0xfu) | ((w >> 4) & 0xf0u) | ((w >> 8) & 0xf00u) | ((w >> 12) & 0xf000u);
+      }
+  }
+  __syncthreads();                             // every wave is done reading the operand buffers
+  if (pre_both && !plane) {
     stage_tile(epi.mask, epi.ldm);
     __syncthreads();
 #pragma unroll
@@ -97,15 +117,16 @@ __device__ __forceinline__ void sg_conv_epilogue(f32x16 (&acc)[TI][TJ], char* sm
           const int il = wi0 + ta * 32 + 8 * g4 + 4 * (lane >> 5);
           const u32x2 m = *(const u32x2*)(smem + jo * CP + il * 2);
 #pragma unroll
-          for (int e = 0; e < 4; e++) { const bf16_t h = (bf16_t)((m[e >> 1] >> (16 * (e & 1))) & 0xffffu); if (bf2f(h) > 0.f) bits |= 1u << (4 * g4 + e); }
+          for (int e = 0; e < 4; e++) { const bf16_t h = (bf16_t)((m[e >> 1] >> (16 * (e & 1))) & 0xffffu); if (sg_relu_pos(h)) bits |= 1u << (4 * g4 + e); }
         }
         mbits[ta * TJ + tb] = bits;
       }
     __syncthreads();
     stage_tile((const bf16_t*)epi.res, epi.ldr);
     __syncthreads();
-  } else if (pre_mask || pre_res) {
-    stage_tile(pre_mask ? epi.mask : (const bf16_t*)epi.res, pre_mask ? epi.ldm : epi.ldr);
+  } else if ((pre_mask && !plane) || pre_res) {      // one operand to stage: the residual, or the mask when it came without a plane
+    const bool sm = pre_mask && !plane;
+    stage_tile(sm ? epi.mask : (const bf16_t*)epi.res, sm ? epi.ldm : epi.ldr);
     __syncthreads();
   }
   const bool relu_out = (epi.flags & SG_EPI_RELU) != 0;
@@ -134,14 +155,14 @@ __device__ __forceinline__ void sg_conv_epilogue(f32x16 (&acc)[TI][TJ], char* sm
 #pragma unroll
             for (int e = 0; e < 4; e++) v[e] += b[e];
           }
-          if (pre_both) {
+          if (pre_both || plane) {
             const uint32_t bits = mbits[ta * TJ + tb] >> (4 * g4);
 #pragma unroll
             for (int e = 0; e < 4; e++) if (!((bits >> e) & 1u)) v[e] = 0.f;
           } else if (pre_mask) {
             const u32x2 m = *(const u32x2*)loc;
 #pragma unroll
-            for (int e = 0; e < 4; e++) { const bf16_t h = (bf16_t)((m[e >> 1] >> (16 * (e & 1))) & 0xffffu); if (!(bf2f(h) > 0.f)) v[e] = 0.f; }
+            for (int e = 0; e < 4; e++) { const bf16_t h = (bf16_t)((m[e >> 1] >> (16 * (e & 1))) & 0xffffu); if (!sg_relu_pos(h)) v[e] = 0.f; }
           }
           if (pre_res) {
             const u32x2 r = *(const u32x2*)loc;
@@ -205,6 +226,25 @@ __device__ __forceinline__ void sg_conv_epilogue(f32x16 (&acc)[TI][TJ], char* sm
         const u32x4 v = *(const u32x4*)(smem + r * CP + c * 16);
         if (v[0] == 0x12345678u && v[1] == 0x9abcdef0u) *(u32x4*)(o + grow(jg) * epi.ldo + i0 + c * 8) = v;      // (never: keeps the read alive)
       } else if (jg < Jout && c < ncr) *(u32x4*)(o + grow(jg) * epi.ldo + i0 + c * 8) = *(const u32x4*)(smem + r * CP + c * 16);
+    }
+  }
+  if (PLANES && epi.sign_out) {
+    // Sign plane of the result (Epilogue::sign_out): one more pass over the finished tile in LDS, behind the tile's own stores. A thread owns one word =
+    // 32 channels of one output row (four 16-byte chunks); consecutive threads write consecutive words of a row, then the next row. Rows beyond the problem
+    // and words whose first chunk does not exist (cout tail tile) are skipped; inside a word, chunks and channels beyond the problem give zero bits.
+    constexpr int NWD = BI / 32;
+    const int nch = epi.I - i0 < BI ? epi.I - i0 : BI;      // channels of this tile that exist
+    for (int idx = tid; idx < rows_out * NWD; idx += 64 * NW) {
+      const int r = idx / NWD, k = idx - r * NWD;
+      const int jg = jbase + r;
+      if (jg >= Jout || 4 * k >= ncr) continue;
+      uint32_t w = 0u;
+#pragma unroll 1      // (one 16-byte chunk in registers at a time: the pass must not raise the kernel's register count)
+      for (int c = 0; c < 4; c++)
+        if (4 * k + c < ncr) w |= sg_relu_pos8(*(const u32x4*)(smem + r * CP + (4 * k + c) * 16)) << (8 * c);
+      const int left = nch - 32 * k;                         // (a last chunk that is only partly inside the problem)
+      if (left < 32) w &= (1u << left) - 1u;
+      epi.sign_out[grow(jg) * epi.lds + (i0 >> 5) + k] = w;
     }
   }
 }

@@ -270,7 +270,8 @@ __global__ __launch_bounds__(64 * WJ * WI) void sg_conv_v3_kernel(ConvV3Params p
 
   float al = epi.alpha;
   if (epi.alpha_ptr) al *= *epi.alpha_ptr;
-  sg_conv_epilogue<BI, BJ, NW, TI, TJ>(acc, smem, sbias, epi, i0, j0, wi0, wj0, al);
+  // (the 32-cout tile -- the generator's RGB layer -- sits at a register boundary and has no use for sign planes: compiled without them, counted so in conv.hip)
+  sg_conv_epilogue<BI, BJ, NW, TI, TJ, false, false, BI != 32>(acc, smem, sbias, epi, i0, j0, wi0, wj0, al);
 }
 
 // LDS layout and need (bytes) of a configuration, or -1 when it does not fit: [patch(es) | weight buffers], overlaid by the staged output tile; behind it

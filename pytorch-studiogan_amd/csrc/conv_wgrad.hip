@@ -333,7 +333,7 @@ template <typename T, bool TR> static int conv_wgrad_t(const sg_conv_wgrad_desc*
     two_stage = c.work_floats > 0 && d->work && d->work_floats >= c.work_floats;
     Epilogue<T> e;
     e.out = d->dw; e.out_bstride = 0; e.ldo = I; e.bias = nullptr; e.res = nullptr; e.res_bstride = 0; e.ldr = 0; e.beta = 0.f;
-    e.mask = nullptr; e.mask_bstride = 0; e.ldm = 0; e.alpha = d->alpha; e.alpha_ptr = d->alpha_ptr; e.split_stride = 0;
+    e.mask = nullptr; e.mask_bstride = 0; e.ldm = 0; e.alpha = d->alpha; e.alpha_ptr = d->alpha_ptr; e.split_stride = 0; e.mask_bits = nullptr; e.ldmb = 0; e.sign_out = nullptr; e.lds = 0;
     e.flags = SG_EPI_OUT_F32; e.I = I; e.J = J;
     if (c.splits == 1) { e.res = d->dw; e.ldr = I; e.beta = 1.f; e.flags |= SG_EPI_RES_F32; }   // single writer: dw += tile, no atomics
     else if (two_stage) { e.out = d->work; e.split_stride = c.n; }                                // partial tiles, reduced below

@@ -60,7 +60,7 @@ template <typename T, bool TR> static int gemm_t(const sg_gemm_desc* d, hipStrea
   Epilogue<T> e;
   e.out = d->out; e.out_bstride = d->out_bstride; e.ldo = d->ldo; e.bias = d->bias;
   e.res = d->res; e.res_bstride = d->res_bstride; e.ldr = d->ldr; e.beta = d->beta;
-  e.mask = nullptr; e.mask_bstride = 0; e.ldm = 0; e.split_stride = 0;
+  e.mask = nullptr; e.mask_bstride = 0; e.ldm = 0; e.split_stride = 0; e.mask_bits = nullptr; e.ldmb = 0; e.sign_out = nullptr; e.lds = 0;
   e.alpha = d->alpha; e.alpha_ptr = d->alpha_ptr; e.flags = d->epi_flags; e.I = d->I; e.J = d->J;
   if (d->splits > 1) SG_CHECK(d->epi_flags & SG_EPI_ATOMIC, "sg_gemm: split-K needs the atomic epilogue");
   const int V = ET<T>::VEC;

@@ -259,6 +259,7 @@ template <typename T, bool FAST = false> struct ConvPixMC {
 #define SG_EPI_POOL 4       // sum the 4 rows of each j-quad (rows must be quad-major), output row = j>>2
 #define SG_EPI_RELU 8       // ReLU on the result
 #define SG_EPI_RES_F32 16   // residual operand is fp32
+#define SG_EPI_PLANES 32    // (descriptors only, never in Epilogue::flags) the descriptor carries the sign-plane fields mask_bits / sign_out
 
 template <typename T> struct Epilogue {
   void* out; long long out_bstride; int ldo;
@@ -268,6 +269,10 @@ template <typename T> struct Epilogue {
   float alpha; const float* alpha_ptr;
   int flags; int I; int J;
   long long split_stride;  // != 0: k-split s writes its partial tile to out + s*split_stride (two-stage split-K)
+  // sign planes (sg_conv_epilogue only; every other epilogue ignores them): uint32 plane[pixel][ld], bit c & 31 of word c >> 5 = sg_relu_pos(x[pixel][c]).
+  // mask_bits: the plane of `mask` (read instead of it); sign_out: the plane of the result, written next to `out`. nullptr = none.
+  const uint32_t* mask_bits; int ldmb;
+  uint32_t* sign_out; int lds;
 
   __device__ __forceinline__ void set_batch(int b) {
     if (flags & (SG_EPI_OUT_F32 | SG_EPI_ATOMIC)) out = (float*)out + (long long)b * out_bstride;

@@ -118,6 +118,64 @@ def _take_stats(x):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# sign planes: the ReLU mask of a bf16 activation as one bit per element (include/sgamd.h, sg_conv_fwd_desc)
+# ---------------------------------------------------------------------------------------------------------
+def sign_planes_on():
+    """SG_SIGN_PLANE=0 (read per call: A/B runs and tests flip it inside one process) turns sign planes off everywhere: no convolution writes one,
+    every masked data gradient reads the activation."""
+    return os.environ.get("SG_SIGN_PLANE", "1") != "0"
+
+
+class SignPlane:
+    """The sign plane of ONE activation tensor, carried next to it from the convolution that wrote both to the convolution that reads the tensor with
+    ReLU-on-load and needs a backward: that one's masked data gradient then loads int32 bits[N][H][W][ceil(C / 32)] instead of the activation (1/16 of the
+    bytes). A producer is handed an empty carrier and fills it when its kernel wrote the plane (the tile-epilogue engines; the others leave it empty); a
+    consumer takes the bits only while they still describe the tensor it saves -- same storage, same version, same grid -- so a tensor that was re-wrapped,
+    replaced or written in place in between falls back to the activation instead of being masked by a stale plane."""
+    __slots__ = ("bits", "ptr", "version", "shape")
+
+    def __init__(self):
+        self.bits = None
+
+    def fill(self, bits, t):
+        self.bits, self.ptr, self.version, self.shape = bits, t.data_ptr(), t._version, tuple(t.shape)
+
+    def bits_for(self, t):
+        if self.bits is None or t.dtype != torch.bfloat16 or self.ptr != t.data_ptr() or self.version != t._version or self.shape != tuple(t.shape):
+            return None
+        return self.bits
+
+
+def plane_like(N, H, W, C, device):
+    return torch.empty((N, H, W, (C + 31) // 32), dtype=torch.int32, device=device)
+
+
+def sign_plane_counts():
+    """(forward launches that wrote a plane, masked launches that read a plane, masked launches that read the activation) so far in this process"""
+    l = L.lib()
+    return tuple(int(l.sg_sign_plane_launches(k)) for k in range(3))
+
+
+def _plane_args(d, out_plane, out, mask, mask_bits):
+    """the sign-plane fields of a ConvFwdDesc / ConvQDesc. Returns (plane tensor offered to the launch or None, the producer count before the launch)"""
+    bits = None
+    if out_plane is not None and out.dtype == torch.bfloat16 and sign_planes_on():
+        bits = plane_like(out.shape[0], out.shape[1], out.shape[2], out.shape[3], out.device)
+        d.sign_out, d.lds = bits.data_ptr(), bits.shape[3]
+        d.epi_flags |= L.EPI_PLANES
+    if mask is not None and mask_bits is not None:
+        d.mask_bits, d.ldmb = mask_bits.data_ptr(), mask_bits.shape[3]
+        d.epi_flags |= L.EPI_PLANES
+    return bits, (L.lib().sg_sign_plane_launches(0) if bits is not None else 0)
+
+
+def _plane_done(out_plane, bits, before, out):
+    """after the launch: the carrier gets the plane when the engine that took the problem wrote it (the library counts those launches)"""
+    if bits is not None and L.lib().sg_sign_plane_launches(0) > before:
+        out_plane.fill(bits, out)
+
+
+# ---------------------------------------------------------------------------------------------------------
 # raw launch helpers (also used directly by the kernel-level tests)
 # ---------------------------------------------------------------------------------------------------------
 class f32_mode:
@@ -144,8 +202,9 @@ class f32_mode:
 
 
 def conv2d_raw(x, w_ptr, Cin, Cout, R, S, stride=1, pad_h=0, pad_w=0, pix_flags=0, epi_flags=0, bias=None, res=None, mask=None,
-               alpha=1.0, beta=1.0, alpha_ptr=None, out=None, ldx=None, transposed_out_hw=None, out_coff=0, x_coff=0, desc=None):
-    """x: [N,Hs,Ws,ldx] NHWC; returns [N,Ho',Wo',Cout]. w_ptr -> [Cout][R*S*Cin] in x.dtype."""
+               alpha=1.0, beta=1.0, alpha_ptr=None, out=None, ldx=None, transposed_out_hw=None, out_coff=0, x_coff=0, desc=None, mask_bits=None, out_plane=None):
+    """x: [N,Hs,Ws,ldx] NHWC; returns [N,Ho',Wo',Cout]. w_ptr -> [Cout][R*S*Cin] in x.dtype. mask_bits: the sign plane of `mask` (int32 [N,H,W,words]), read instead
+    of it by the engines that can; out_plane: an empty SignPlane that receives the plane of the result when the engine wrote it."""
     N, Hs, Ws = x.shape[0], x.shape[1], x.shape[2]
     ldx = x.shape[3] if ldx is None else ldx
     up = 2 if (pix_flags & L.PIX_UPSAMPLE) else 1
@@ -178,11 +237,13 @@ def conv2d_raw(x, w_ptr, Cin, Cout, R, S, stride=1, pad_h=0, pad_w=0, pix_flags=
     d.ldm = mask.shape[-1] if mask is not None else 0
     if desc is not None:        # the caller launches (conv2d_skip_raw)
         return out
+    bits, before = _plane_args(d, out_plane if out_coff == 0 else None, out, mask, mask_bits)
     L.call("sg_conv2d_fwd", d, L.stream())
+    _plane_done(out_plane, bits, before, out)
     return out
 
 
-def conv2d_skip_raw(x, w_ptr, Cin, Cout, x2, w2_ptr, C2, x2_up=False, pix_flags=0, epi_flags=0, bias=None, bias2=None, alpha=1.0, dry=False, stats=False):
+def conv2d_skip_raw(x, w_ptr, Cin, Cout, x2, w2_ptr, C2, x2_up=False, pix_flags=0, epi_flags=0, bias=None, bias2=None, alpha=1.0, dry=False, stats=False, out_plane=None):
     """[pool]( conv3x3(x; w) + conv1x1(up2?(x2); w2) ) + bias + bias2 in ONE launch (include/sgamd.h sg_conv2d_fwd_skip): the residual block's
     skip convolution as extra K-slices of its last 3x3 launch. dry=True: only ask whether the fused kernel takes the problem.
     Returns the output tensor, or None when the problem is not eligible (the caller then runs the two launches)."""
@@ -195,6 +256,7 @@ def conv2d_skip_raw(x, w_ptr, Cin, Cout, x2, w2_ptr, C2, x2_up=False, pix_flags=
         return None
     if dry:
         return out
+    bits, before = _plane_args(sk.main, out_plane, out, None, None)
     if stats and not (epi_flags & L.EPI_POOL):
         # per-tile batch-norm statistics of the result from the epilogue (consumed by BNFn through _offer_stats / _take_stats)
         rows = L.lib().sg_conv2d_fwd_skip_stat_rows(L.C.byref(sk))
@@ -202,8 +264,10 @@ def conv2d_skip_raw(x, w_ptr, Cin, Cout, x2, w2_ptr, C2, x2_up=False, pix_flags=
         sk.stats = st.data_ptr()
         L.call("sg_conv2d_fwd_skip", sk, L.stream())
         _offer_stats(out, st, rows, Cout)
+        _plane_done(out_plane, bits, before, out)
         return out
     L.call("sg_conv2d_fwd_skip", sk, L.stream())
+    _plane_done(out_plane, bits, before, out)
     return out
 
 
@@ -245,7 +309,7 @@ def quad_pack_raw(src_ptr, dst, mode, M, Cs):
 
 
 def conv2d_q_raw(x, wq_ptr, form, Cin, Cout, pix_flags=0, epi_flags=0, bias=None, res=None, mask=None, alpha=1.0, beta=1.0, dry=False,
-                 x2=None, w2q_ptr=None, bias2=None, stats=False, x2_norelu=False):
+                 x2=None, w2q_ptr=None, bias2=None, stats=False, x2_norelu=False, mask_bits=None, out_plane=None):
     """The quad forms of a 3x3 / pad-1 convolution next to a 2x resampling (include/sgamd.h sg_conv2d_q). form Q_POOL: x [N,2Hl,2Wl,C] ->
     [N,Hl,Wl,Cout] = avgpool2(conv3x3(x)); form Q_UP: x [N,Hl,Wl,C] -> [N,2Hl,2Wl,Cout] = conv3x3(up2(x)). Returns None when not eligible."""
     N = x.shape[0]
@@ -279,7 +343,9 @@ def conv2d_q_raw(x, wq_ptr, form, Cin, Cout, pix_flags=0, epi_flags=0, bias=None
             rows = L.lib().sg_conv2d_q_stat_rows(L.C.byref(d))
             st = torch.empty((rows, Cout, 2), dtype=torch.float32, device=x.device)
             d.stats = st.data_ptr()
+        bits, before = _plane_args(d, out_plane, out, mask, mask_bits)
         L.call("sg_conv2d_q", d, L.stream())
+        _plane_done(out_plane, bits, before, out)
         if st is not None:
             _offer_stats(out, st, rows, Cout)
     return out
@@ -351,4 +417,4 @@ def gemm_dgrad_rows(w_ptr, dy, dx, B, K, O):
     return dx
 
 
-__all__ = ['L', 'zeros_small', 'zeros_like_small', '_BN_FUSED_STATS', '_CBN_MERGED', '_DGRAD_SPLITK', '_SEQ', '_STATS_OFFER', '_c', '_comm', '_first_order_only', '_offer_stats', '_param_grad_wanted', '_take_stats', '_tick', 'conv2d_q_raw', 'conv2d_q_wgrad_raw', 'conv2d_raw', 'conv2d_skip_raw', 'conv2d_wgrad_raw', 'dist', 'ensure_grad', 'f32_mode', 'gemm_dgrad_rows', 'gemm_raw', 'os', 'quad_pack_raw', 'second_order', 'torch']
+__all__ = ['L', 'zeros_small', 'zeros_like_small', 'SignPlane', 'sign_planes_on', 'sign_plane_counts', 'plane_like', '_BN_FUSED_STATS', '_CBN_MERGED', '_DGRAD_SPLITK', '_SEQ', '_STATS_OFFER', '_c', '_comm', '_first_order_only', '_offer_stats', '_param_grad_wanted', '_take_stats', '_tick', 'conv2d_q_raw', 'conv2d_q_wgrad_raw', 'conv2d_raw', 'conv2d_skip_raw', 'conv2d_wgrad_raw', 'dist', 'ensure_grad', 'f32_mode', 'gemm_dgrad_rows', 'gemm_raw', 'os', 'quad_pack_raw', 'second_order', 'torch']

@@ -74,18 +74,19 @@ def _quad_form(rt, cfg, x):
     return L.Q_POOL if cfg.out_pool else L.Q_UP
 
 
-def _conv_fwd(x, rt, slot, cfg, bias, res=None, stats=False):
-    """ConvFn's forward launch: [res +] avgpool2?(conv(up2?(relu?(x)))) + bias. stats: also offer the result's batch-norm statistics (quad kernel)"""
+def _conv_fwd(x, rt, slot, cfg, bias, res=None, stats=False, out_plane=None):
+    """ConvFn's forward launch: [res +] avgpool2?(conv(up2?(relu?(x)))) + bias. stats: also offer the result's batch-norm statistics (quad kernel);
+    out_plane: an empty SignPlane for the result's sign plane"""
     bank = rt.bank()
     Cin = x.shape[3]
     form = _quad_form(rt, cfg, x)
     if form is not None:
         y = conv2d_q_raw(x, bank.w_quad(slot, rt, form), form, Cin, rt.rows_pad, L.PIX_RELU if cfg.in_relu else 0, 0, bias=bias, res=res,
-                         stats=stats and _BN_FUSED_STATS[0] and rt.rows_pad == rt.rows)
+                         stats=stats and _BN_FUSED_STATS[0] and rt.rows_pad == rt.rows, out_plane=out_plane)
         if y is not None:
             return y
     return conv2d_raw(x, bank.w_fwd(slot, rt), Cin, rt.rows_pad, cfg.R, cfg.S, cfg.stride, cfg.pad_h, cfg.pad_w, cfg.pix_flags(), cfg.epi_flags(),
-                      bias=bias, res=res, alpha=cfg.scale)
+                      bias=bias, res=res, alpha=cfg.scale, out_plane=out_plane)
 
 
 def _conv_wgrad(x, dy, rt, slot, cfg, dbias=None):
@@ -102,12 +103,25 @@ def _conv_wgrad(x, dy, rt, slot, cfg, dbias=None):
 
 def _conv_dgrad(dy, x, rt, slot, cfg, res=None):
     """data gradient of ConvFn's fused launch: dx = relu-mask(x) * F^T(dy) [+ res], F = pool?(conv(up?(.))) * (0.25 if pool)."""
+    return _conv_dgrad_bits(dy, x, rt, slot, cfg, res, None)
+
+
+def _dgrad(dy, x, rt, slot, cfg, res=None, x_bits=None):
+    """the backward's call: `_conv_dgrad` as it always was (looked up per call: tests wrap it) unless a sign plane of x came along"""
+    if x_bits is None or not cfg.in_relu:
+        return _conv_dgrad(dy, x, rt, slot, cfg, res=res)
+    return _conv_dgrad_bits(dy, x, rt, slot, cfg, res, x_bits)
+
+
+def _conv_dgrad_bits(dy, x, rt, slot, cfg, res, x_bits):
+    """_conv_dgrad with the sign plane of x (SignPlane.bits, or None): the plane goes along with x as the ReLU mask, and the engine that takes the launch
+    reads the one it can."""
     bank = rt.bank()
     N, Hs, Ws, Cin = x.shape
     form = _quad_form(rt, cfg, x)
     if form is not None and dy.shape[3] == rt.rows_pad:
         # the data gradient of one quad form is the other form with the transformed flipped image (sg_quad_pack modes 2 / 3)
-        dx = conv2d_q_raw(dy, bank.w_quad(slot, rt, 2 + form), 1 - form, rt.rows_pad, Cin, 0, 0, mask=x if cfg.in_relu else None, res=res)
+        dx = conv2d_q_raw(dy, bank.w_quad(slot, rt, 2 + form), 1 - form, rt.rows_pad, Cin, 0, 0, mask=x if cfg.in_relu else None, res=res, mask_bits=x_bits)
         if dx is not None:
             return dx
     up = 2 if cfg.in_upsample else 1
@@ -117,13 +131,13 @@ def _conv_dgrad(dy, x, rt, slot, cfg, res=None):
         # strided convolution: gather form of the transposed convolution with the UNflipped [Cin][r][s][Cout] image
         assert not (pool or cfg.in_upsample), "upsample / pooling fusion is stride-1 only"
         return conv2d_raw(dy, bank.w_dgrad(slot, rt), rt.rows_pad, Cin, cfg.R, cfg.S, cfg.stride, cfg.pad_h, cfg.pad_w, L.PIX_TRANSPOSED, 0,
-                          mask=x if cfg.in_relu else None, res=res, transposed_out_hw=(Hin, Win), ldx=dy.shape[3])
+                          mask=x if cfg.in_relu else None, res=res, transposed_out_hw=(Hin, Win), ldx=dy.shape[3], mask_bits=x_bits)
     pf = L.PIX_UPSAMPLE if pool else 0
     ef = L.EPI_POOL if cfg.in_upsample else 0
     # dy has rows_pad channels and the dgrad image is [cin_pad][R][S][rows_pad] (zero outside the real weights): the padded
     # channels ride along so the 16-byte loaders apply; dx comes out with cin_pad channels like x
     return conv2d_raw(dy, bank.w_dgrad(slot, rt), rt.rows_pad, Cin, cfg.R, cfg.S, 1, cfg.R - 1 - cfg.pad_h, cfg.S - 1 - cfg.pad_w, pf, ef,
-                      mask=x if cfg.in_relu else None, res=res, alpha=cfg.scale, ldx=dy.shape[3])
+                      mask=x if cfg.in_relu else None, res=res, alpha=cfg.scale, ldx=dy.shape[3], mask_bits=x_bits)
 
 
 class ConvDgradFn(torch.autograd.Function):
@@ -173,9 +187,12 @@ class ConvFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x, weight, bias, res, rt, slot, cfg, link=None):
+    def forward(ctx, x, weight, bias, res, rt, slot, cfg, link=None, x_plane=None, out_plane=None):
+        """x_plane: the SignPlane that came with x (its bits replace x as the data gradient's ReLU mask while they still describe x); out_plane: an empty
+        SignPlane for the result's plane -- asked for when the next reader of y applies ReLU on load and needs a backward"""
         bank = rt.bank()
         x = _c(x)
+        ctx.x_bits = x_plane.bits_for(x) if (x_plane is not None and cfg.in_relu) else None
         N, Hs, Ws, Cin = x.shape
         assert Cin == rt.cin_pad, f"conv input channels {Cin} != {rt.cin_pad}"
         ctx.link = link
@@ -188,7 +205,7 @@ class ConvFn(torch.autograd.Function):
             bias_k = zeros_small(rt.rows_pad, torch.float32, x.device)
             bias_k[:rt.rows].copy_(bias.detach())
         _tick()
-        y = _conv_fwd(x, rt, slot, cfg, bias_k, res, stats=cfg.stats)
+        y = _conv_fwd(x, rt, slot, cfg, bias_k, res, stats=cfg.stats, out_plane=out_plane)
         ctx.save_for_backward(x)
         ctx.rt, ctx.slot, ctx.cfg = rt, slot, cfg
         ctx.bias = bias
@@ -207,12 +224,12 @@ class ConvFn(torch.autograd.Function):
             if _param_grad_wanted(ctx.weight, ctx.bias):
                 raise NotImplementedError("create_graph=True is supported for input gradients only (WGAN-GP path)")
             dx = ConvDgradFn.apply(dy, x, ctx.weight, rt, slot, cfg) if ctx.needs_input_grad[0] else None
-            return dx, None, None, (dy if ctx.has_res else None), None, None, None, None
+            return dx, None, None, (dy if ctx.has_res else None), None, None, None, None, None, None
         dy = _c(dy)
         dx = None
         skip_dx = ctx.link.take() if ctx.link is not None else None     # the skip path's gradient w.r.t. this same input (GradLink)
         if ctx.needs_input_grad[0]:
-            dx = _conv_dgrad(dy, x, rt, slot, cfg, res=skip_dx)
+            dx = _dgrad(dy, x, rt, slot, cfg, res=skip_dx, x_bits=ctx.x_bits)
         elif skip_dx is not None:
             raise RuntimeError("GradLink: a skip gradient was handed over but this convolution's input needs no gradient")
         if ctx.link is not None and ctx.link.chain:
@@ -230,7 +247,7 @@ class ConvFn(torch.autograd.Function):
             rows = dy.shape[0] * dy.shape[1] * dy.shape[2]
             L.call("sg_colsum", L.dt(dy), L.ptr(dy), dy.shape[3], None, 0, rows, rt.rows, L.ptr(g), 1.0, L.stream())
         dres = dy if ctx.has_res else None
-        return dx, None, None, dres, None, None, None, None
+        return dx, None, None, dres, None, None, None, None, None, None
 
 
 class ConvSkipFn(torch.autograd.Function):
@@ -241,10 +258,13 @@ class ConvSkipFn(torch.autograd.Function):
     backward: the two data gradients and the two weight gradients of the unfused form (the fusion is forward-only)."""
 
     @staticmethod
-    def forward(ctx, h, x, w2, b2, w0, b0, rt2, rt0, slot, cfg2, cfg0, link=None):
+    def forward(ctx, h, x, w2, b2, w0, b0, rt2, rt0, slot, cfg2, cfg0, link=None, h_plane=None, x_plane=None, out_plane=None):
+        """h_plane / x_plane: the SignPlanes that came with h / x (ConvFn.forward); out_plane: an empty SignPlane for the block output's plane"""
         bank = rt2.bank()
         ctx.link = link
         h, x = _c(h), _c(x)
+        ctx.h_bits = h_plane.bits_for(h) if (h_plane is not None and cfg2.in_relu) else None
+        ctx.x_bits = x_plane.bits_for(x) if (x_plane is not None and cfg0.in_relu) else None
         _tick()
         # (cfg0.in_relu may differ from cfg2.in_relu: the first discriminator block's skip reads the image itself, big_resnet.py:177-192)
         assert cfg2.R == 3 and cfg0.R == 1 and cfg2.out_pool == cfg0.out_pool and not cfg2.in_upsample and (cfg0.in_relu == cfg2.in_relu or not cfg0.in_relu)
@@ -259,15 +279,15 @@ class ConvSkipFn(torch.autograd.Function):
             # (None: the kernel does not take the shape -- sg_conv2d_fwd_skip_ok includes the launcher's LDS limit -- and the two-launch form below runs;
             # a launch that fails after that is a real fault and propagates)
             y = conv2d_skip_raw(h, bank.w_fwd(slot, rt2), h.shape[3], rt2.rows, x, bank.w_fwd(slot, rt0), x.shape[3], cfg0.in_upsample, pf, ef,
-                                bias=b2, bias2=b0, alpha=al, stats=cfg2.stats and _BN_FUSED_STATS[0])
+                                bias=b2, bias2=b0, alpha=al, stats=cfg2.stats and _BN_FUSED_STATS[0], out_plane=out_plane)
         if y is None and plain and _quad_form(rt2, cfg2, h) == L.Q_POOL and _SKIP_FUSION[0] and (rt0.cin_pad % 32 == 0 or rt0.cin_pad == 8) and not cfg0.in_upsample:
             # pooled tail on the quad kernel with the skip as extra one-tap K-slices of the same launch (conv_q.h SKIP; an 8-channel skip input --
             # the image -- is ONE slice holding its four parity views, filter image mode 5)
             y = conv2d_q_raw(h, bank.w_quad(slot, rt2, L.Q_POOL), L.Q_POOL, h.shape[3], rt2.rows, pf, 0, bias=b2,
-                             x2=x, w2q_ptr=bank.w_quad(slot, rt0, 5 if rt0.cin_pad == 8 else 4), bias2=b0, x2_norelu=not same_relu)
+                             x2=x, w2q_ptr=bank.w_quad(slot, rt0, 5 if rt0.cin_pad == 8 else 4), bias2=b0, x2_norelu=not same_relu, out_plane=out_plane)
         if y is None:
             hh = _conv_fwd(h, rt2, slot, cfg2, b2)
-            y = conv2d_raw(x, bank.w_fwd(slot, rt0), x.shape[3], rt0.rows_pad, 1, 1, 1, 0, 0, cfg0.pix_flags(), ef, bias=b0, res=hh, alpha=al)
+            y = conv2d_raw(x, bank.w_fwd(slot, rt0), x.shape[3], rt0.rows_pad, 1, 1, 1, 0, 0, cfg0.pix_flags(), ef, bias=b0, res=hh, alpha=al, out_plane=out_plane)
         ctx.save_for_backward(h, x)
         ctx.rt2, ctx.rt0, ctx.slot, ctx.cfg2, ctx.cfg0 = rt2, rt0, slot, cfg2, cfg0
         ctx.w2, ctx.b2, ctx.w0, ctx.b0 = w2, b2, w0, b0
@@ -282,7 +302,7 @@ class ConvSkipFn(torch.autograd.Function):
                 raise NotImplementedError("create_graph=True is supported for input gradients only (WGAN-GP path)")
             dh = ConvDgradFn.apply(dy, h, ctx.w2, rt2, slot, cfg2) if ctx.needs_input_grad[0] else None
             dx = ConvDgradFn.apply(dy, x, ctx.w0, rt0, slot, cfg0) if ctx.needs_input_grad[1] else None
-            return (dh, dx) + (None,) * 10
+            return (dh, dx) + (None,) * 13
         dy = _c(dy)
         bank = rt2.bank()
         outs = []
@@ -295,7 +315,8 @@ class ConvSkipFn(torch.autograd.Function):
             shared_db = zeros_small(rt2.rows, torch.float32, dy.device)
         for inp, rt, cfg, w_i, b_i, wp, bp in ((h, rt2, cfg2, 2, 3, ctx.w2, ctx.b2), (x, rt0, cfg0, 4, 5, ctx.w0, ctx.b0)):
             k = 0 if inp is h else 1
-            outs.append(_conv_dgrad(dy, inp, rt, slot, cfg) if ctx.needs_input_grad[k] else None)
+            # (the 1x1 skip's data gradient runs on the streaming kernel, which reads the activation: its plane only rides along)
+            outs.append(_dgrad(dy, inp, rt, slot, cfg, x_bits=ctx.h_bits if k == 0 else ctx.x_bits) if ctx.needs_input_grad[k] else None)
             want_db = bp is not None and ctx.needs_input_grad[b_i]
             db_done = False
             if ctx.needs_input_grad[w_i]:
@@ -320,7 +341,7 @@ class ConvSkipFn(torch.autograd.Function):
             # the block's first operator consumes x as well and runs its backward after this one: it adds this gradient in its own launch
             ctx.link.dx = outs[1]
             outs[1] = None
-        return (outs[0], outs[1]) + (None,) * 10
+        return (outs[0], outs[1]) + (None,) * 13
 
 
 _SKIP_FUSION = [{"0": False, "all": "all"}.get(os.environ.get("SG_SKIP_FUSION", "1"), True)]      # tests / A-B runs: SG_SKIP_FUSION=0 (or functional._SKIP_FUSION[0] = False) forces the two-launch form
@@ -860,4 +881,4 @@ class SNEmbeddingFn(torch.autograd.Function):
         return None, None, None, None
 
 
-__all__ = ['CatConvDgradFn', 'CatConvFn', 'CbnAffineDgradFn', 'CbnAffineFn', 'CbnAffineGroupFn', 'cbn_prefetch', '_CBN_GROUP', 'ConvCfg', 'ConvDgradFn', 'ConvFn', 'ConvSkipFn', 'ConvTransposeFn', 'EmbeddingFn', 'GradLink', 'LinearDgradFn', 'LinearFn', 'SNEmbeddingFn', 'SliceUpBwdFn', 'SliceUpFn', '_GRAD_LINK', '_QUAD', '_SKIP_FUSION', '_conv_dgrad', '_conv_fwd', '_conv_wgrad', '_quad_form']
+__all__ = ['CatConvDgradFn', 'CatConvFn', 'CbnAffineDgradFn', 'CbnAffineFn', 'CbnAffineGroupFn', 'cbn_prefetch', '_CBN_GROUP', 'ConvCfg', 'ConvDgradFn', 'ConvFn', 'ConvSkipFn', 'ConvTransposeFn', 'EmbeddingFn', 'GradLink', 'LinearDgradFn', 'LinearFn', 'SNEmbeddingFn', 'SliceUpBwdFn', 'SliceUpFn', '_GRAD_LINK', '_QUAD', '_SKIP_FUSION', '_conv_dgrad', '_conv_dgrad_bits', '_dgrad', '_conv_fwd', '_conv_wgrad', '_quad_form']

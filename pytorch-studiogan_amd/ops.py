@@ -123,15 +123,16 @@ class Conv2d(_WeightLayerMixin, nn.Conv2d):
         self._sg_dgrad_noflip = self.stride[0] != 1     # strided conv: data gradient is a transposed gather (unflipped image)
         self._sg_setup("conv", out_channels, in_channels * kh * kw, in_channels, kh * kw, sn)
 
-    def forward_nhwc(self, x, slot=None, in_relu=False, in_upsample=False, out_pool=False, res=None, link=None, stats=False):
+    def forward_nhwc(self, x, slot=None, in_relu=False, in_upsample=False, out_pool=False, res=None, link=None, stats=False, x_plane=None, out_plane=None):
         """link: a functional.GradLink shared with the block's tail (conv_skip_nhwc): this convolution's data gradient then also adds the
-        gradient the same input receives through the skip path"""
+        gradient the same input receives through the skip path. x_plane / out_plane: functional.SignPlane carriers (the plane that came with x; an empty one
+        for the plane of the result), see functional.ConvFn"""
         rt = self._sg_rt
         slot = slot if slot is not None else rt.bank().current
         kh, kw = self.kernel_size
         # (stats: only a batch norm in batch-statistics mode takes the offer; a frozen network -- eval mode, the FID loop's generator -- reads running statistics)
         cfg = F.ConvCfg(kh, kw, self.stride[0], self.padding[0], self.padding[1], in_relu, in_upsample, out_pool, stats and self.training)
-        return F.ConvFn.apply(x, self.master_weight, self.bias, res, rt, slot, cfg, link)
+        return F.ConvFn.apply(x, self.master_weight, self.bias, res, rt, slot, cfg, link, x_plane, out_plane)
 
     def forward(self, x):
         slot = _standalone_slot(self, x)
@@ -142,14 +143,15 @@ class Conv2d(_WeightLayerMixin, nn.Conv2d):
         return to_nchw(y)
 
 
-def conv_skip_nhwc(conv_main, conv_skip, h, x, slot=None, in_relu=False, out_pool=False, skip_upsample=False, link=None, stats=False, skip_relu=None):
+def conv_skip_nhwc(conv_main, conv_skip, h, x, slot=None, in_relu=False, out_pool=False, skip_upsample=False, link=None, stats=False, skip_relu=None,
+                   h_plane=None, x_plane=None, out_plane=None):
     """Tail of a residual block: [pool](conv_main(relu?(h))) + [pool](conv_skip(up?(relu?(x)))) -- ONE fused launch when the kernel takes the
     shape (functional.ConvSkipFn), the two chained launches otherwise. conv_main: 3x3 / pad 1, conv_skip: 1x1."""
     rt2, rt0 = conv_main._sg_rt, conv_skip._sg_rt
     slot = slot if slot is not None else rt2.bank().current
     cfg2 = F.ConvCfg(3, 3, 1, 1, 1, in_relu, False, out_pool, stats)
     cfg0 = F.ConvCfg(1, 1, 1, 0, 0, in_relu if skip_relu is None else skip_relu, skip_upsample, out_pool)
-    return F.ConvSkipFn.apply(h, x, conv_main.master_weight, conv_main.bias, conv_skip.master_weight, conv_skip.bias, rt2, rt0, slot, cfg2, cfg0, link)
+    return F.ConvSkipFn.apply(h, x, conv_main.master_weight, conv_main.bias, conv_skip.master_weight, conv_skip.bias, rt2, rt0, slot, cfg2, cfg0, link, h_plane, x_plane, out_plane)
 
 
 class ConvTranspose2d(_WeightLayerMixin, nn.ConvTranspose2d):

@@ -1,7 +1,9 @@
 """Quad convolutions (csrc/conv_q.h, wgrad_q.h) against the direct 3x3 kernels on the BigGAN-128 (C3) layers that sit next to a 2x resampling,
 batch 256, bf16: forward, data gradient, weight gradient. TF = algorithmic (the 3x3 convolution over the fine grid) / time; the quad
 launches execute 16/36 of those FLOPs.
-    python tools/quad_bench.py [--batch 256] [--only 192-192-32]"""
+    python tools/quad_bench.py [--batch 256] [--only 192-192-32]
+    python tools/quad_bench.py --arms [--only 96-96-64,192-192-32]      the pooled layers' masked data gradient, three arms in one process: mask read from the
+        activation, from its sign plane (include/sgamd.h), and no mask at all (what SG_QB_NOMASK=1 measures); and the forward launch with and without writing a plane"""
 import argparse
 import os
 import sys
@@ -30,11 +32,62 @@ def timeit(fn, iters=5):
     return a.elapsed_time(b) / iters
 
 
+def plane_of(x):
+    """sign plane of a bf16 NHWC tensor, int32 [N, H, W, ceil(C / 32)] (torch arithmetic: the benchmark's operand, not a product path)"""
+    C = x.shape[3]
+    nw = (C + 31) // 32
+    pos = torch.zeros(tuple(x.shape[:3]) + (nw * 32,), dtype=torch.int64, device=x.device)
+    pos[..., :C] = x > 0
+    w = (pos.view(tuple(x.shape[:3]) + (nw, 32)) << torch.arange(32, dtype=torch.int64, device=x.device)).sum(-1)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32).contiguous()
+
+
+def arms(args):
+    """activation / plane / no mask on the pooled layers' data gradient (the UP form of the quad kernel), interleaved, best of `rounds`"""
+    dev, dt, N = torch.device("cuda:0"), torch.bfloat16, args.batch
+    print(f"{'layer':26s} | {'dgrad act':>9s} {'plane':>7s} {'no mask':>7s} {'recovered':>9s} | {'fwd':>7s} {'fwd+plane':>9s}   (ms, best of {args.rounds} x 10 launches)")
+    for form, Cin, Cout, Hl in SHAPES:
+        if form != "pool" or (args.only and f"{Cin}-{Cout}-{Hl}" not in args.only.split(",")):
+            continue
+        Hf = 2 * Hl
+        x = torch.randn(N, Hf, Hf, Cin, device=dev).to(dt)
+        gy = torch.randn(N, Hl, Hl, Cout, device=dev).to(dt)
+        w = (0.05 * torch.randn(Cout, 3, 3, Cin, device=dev)).to(dt)
+        wd = w.flip(1).flip(2).permute(3, 1, 2, 0).contiguous()
+        bias = torch.randn(Cout, device=dev)
+        qf = torch.empty(Cout, 16, Cin, dtype=dt, device=dev)
+        qd = torch.empty(Cin, 16, Cout, dtype=dt, device=dev)
+        F.quad_pack_raw(w.data_ptr(), qf, 0, Cout, Cin)
+        F.quad_pack_raw(wd.data_ptr(), qd, 2, Cin, Cout)
+        bits = plane_of(x)
+        a = F.conv2d_q_raw(gy, qd.data_ptr(), L.Q_UP, Cout, Cin, 0, 0, mask=x)
+        b = F.conv2d_q_raw(gy, qd.data_ptr(), L.Q_UP, Cout, Cin, 0, 0, mask=x, mask_bits=bits)
+        assert torch.equal(a.view(torch.int16), b.view(torch.int16)), "plane arm differs from the activation arm"
+        runs = {
+            "act": lambda: F.conv2d_q_raw(gy, qd.data_ptr(), L.Q_UP, Cout, Cin, 0, 0, mask=x),
+            "plane": lambda: F.conv2d_q_raw(gy, qd.data_ptr(), L.Q_UP, Cout, Cin, 0, 0, mask=x, mask_bits=bits),
+            "none": lambda: F.conv2d_q_raw(gy, qd.data_ptr(), L.Q_UP, Cout, Cin, 0, 0),
+            "fwd": lambda: F.conv2d_q_raw(x, qf.data_ptr(), L.Q_POOL, Cin, Cout, L.PIX_RELU, 0, bias=bias),
+            "fwd+plane": lambda: F.conv2d_q_raw(x, qf.data_ptr(), L.Q_POOL, Cin, Cout, L.PIX_RELU, 0, bias=bias, out_plane=F.SignPlane()),
+        }
+        best = {k: 1e9 for k in runs}
+        for _ in range(args.rounds):
+            for k, fn in runs.items():
+                best[k] = min(best[k], timeit(fn, 10))
+        gap = best["act"] - best["none"]
+        rec = (best["act"] - best["plane"]) / gap if gap > 0 else float("nan")
+        print(f"pool {Cin:5d}->{Cout:5d} @{Hl:3d}^2 | {best['act']:9.3f} {best['plane']:7.3f} {best['none']:7.3f} {rec:9.2f} | {best['fwd']:7.3f} {best['fwd+plane']:9.3f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--only", default="")
+    ap.add_argument("--arms", action="store_true")
+    ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
+    if args.arms:
+        return arms(args)
     dev, dt, N = torch.device("cuda:0"), torch.bfloat16, args.batch
     print(f"{'layer':26s} {'GFLOP':>7s} | {'fwd 3x3':>8s} {'quad':>7s} {'TF':>6s} {'x':>5s} | {'dgrad 3x3':>9s} {'quad':>7s} {'TF':>6s} {'x':>5s} | {'wgrad 3x3':>9s} {'quad':>7s} {'TF':>6s} {'x':>5s}")
     tot = [0.0] * 7
