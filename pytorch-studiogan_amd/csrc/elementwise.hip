@@ -752,13 +752,16 @@ extern "C" int sg_gp_fwd(int kind, const float* grads, int B, long long n, float
   return 0;
 }
 // d penalty / d grads[b,:] = gout * { (2/B) (1 - 1/norms[b]) | 1/B | 2 [b == argmax] } grads[b,:]
+// kind 0 at norms[b] == 0 (a sample whose gradient row is all zero): the 2-norm has no derivative there, and 1 - 1/0 = -inf times the zero row would be
+// NaN in every parameter. torch's convention for norm(2, dim=1) is the zero subgradient (the reference's grads.norm(2, dim=1) backpropagates exact zeros
+// into such a row), so the row's factor is 0.
 __global__ void k_gp_bwd(int kind, const float* grads, const float* norms, const float* gout, float* dgrads, int B, long long n, long long total) {
   const float go = gout[0];
   const int bmax = kind == 2 ? (int)norms[B] : -1;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int b = (int)(i / n);
     float f;
-    if (kind == 0) f = go * 2.f / (float)B * (1.f - 1.f / norms[b]);
+    if (kind == 0) f = norms[b] > 0.f ? go * 2.f / (float)B * (1.f - 1.f / norms[b]) : 0.f;
     else if (kind == 1) f = go / (float)B;
     else f = (b == bmax) ? 2.f * go : 0.f;
     dgrads[i] = f * grads[i];

@@ -154,22 +154,24 @@ __global__ __launch_bounds__(256) void k_contrastive_rows(int kind, const float*
   const long long yi = label[i];
   const float invT = 1.f / T, invB = 1.f / B;
   if (kind == 0) {
-    float all = 0.f, pos = 0.f;
+    // the negatives are summed on their own: den = num + neg, so loss = log(1 + neg / num) and 1/den - 1/num = -(neg / den) / num without the cancellation that
+    // num ~ den (few or far negatives, small T) would otherwise leave in the loss and in the gradients of the proxy and of the positives
+    float pos = 0.f, neg = 0.f;
     for (int j = lane; j < B; j += 64) {
       if (j == i) continue;
       const float e = expf(Si[j] * invT);
-      all += e;
-      if (label[j] == yi) pos += e;
+      if (label[j] == yi) pos += e; else neg += e;
     }
-    all = wave_sum(all); pos = wave_sum(pos);
+    pos = wave_sum(pos); neg = wave_sum(neg);
     const float a = expf(p[i] * invT);
-    const float num = a + pos, den = a + all;
-    if (lane == 0) { row_loss[i] = -logf(num / den); dp[i] = invB * a * invT * (1.f / den - 1.f / num); }
+    const float num = a + pos, den = num + neg;
+    const float pull = -(neg / den) / num;           // = 1/den - 1/num
+    if (lane == 0) { row_loss[i] = log1pf(neg / num); dp[i] = invB * a * invT * pull; }
     for (int j = lane; j < B; j += 64) {
       float g = 0.f;
       if (j != i) {
         const float e = expf(Si[j] * invT);
-        g = invB * e * invT * (1.f / den - (label[j] == yi ? 1.f / num : 0.f));
+        g = invB * e * invT * (label[j] == yi ? pull : 1.f / den);
       }
       dSi[j] = g;
     }

@@ -1,7 +1,11 @@
 """GPU: class-conditioning heads and losses (AC / TAC / ADC auxiliary classifiers, ContraGAN's 2C, ReACGAN's D2D-CE,
 multi-hinge, multi-discriminator) of the mirrors against tests/golden/heads.npz -- the outputs of the REAL reference's
 big_resnet.Discriminator + utils/losses.py combined as src/worker.py:281-317 does (oracle/make_golden_heads.py): head outputs, the
-discriminator-side loss and every parameter gradient, fp32 <= 1e-3."""
+discriminator-side loss and every parameter gradient, fp32 <= 1e-3.
+
+These are whole CIFAR10 networks at batch 8 with 10 (ADC: 20) classes and embedding width 16: they check how the heads are wired, not the kernels' shapes.
+The kernels of csrc/heads.hip at more than one trip of a lane-strided loop, partly filled blocks, arg-max ties and 256 x 256 similarity matrices are held to
+an fp64 restatement in tests/test_head_kernels_gpu.py (cases: tests/head_checks.py)."""
 import json
 import os
 
