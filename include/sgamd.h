@@ -661,6 +661,23 @@ int sg_upfirdn2d(int dtype, const void* x, const float* f, void* y, int planes, 
 int sg_filtered_lrelu(int dtype, const void* x, const float* fu, const float* fd, const void* b, void* y, int N, int C, int H, int W,
                       int fu_n, int fd_n, int up, int down, int px0, int px1, int py0, int py1, float gain, float slope, float clamp,
                       int flip_filter, sg_stream_t s);
+/* sg_filtered_lrelu_gate: sg_filtered_lrelu (bit-identical y) that also writes the gate plane of the activated intermediate,
+ * gate [N * C][AHt][(AWt + 3) / 4] bytes, AHt = H * up + py0 + py1 - (fu_n - 1), AWt likewise: 2 bits per element, element j of a row in bits
+ * 2 * (j & 3) of byte j / 4; 1 = positive (the backward scales by gain), 2 = negative (gain * slope), 0 = clamped or read by no output. The state comes
+ * from the fp32 accumulator the forward activates. Every byte is written, by exactly one workgroup, with plain stores.
+ * sg_filtered_lrelu_bwd: the FORWARD's arguments, dy [N][C][Ho][Wo] and that gate plane -> dx [N][C][H][W] = upfir_fu^T(gate (.) downfir_fd^T(dy)) in ONE
+ * launch, the intermediate in LDS (fp32). The dx tile: each axis in the fewest equal pieces of at most 16 (then 8, 4 while the LDS exceeds 64 KB); -3 when none
+ * fits: differentiate the chain instead. db = dx.sum over N, H, W.
+ * sg_filtered_lrelu_launches(what): launches so far of 0 the plain forward, 1 the gate-writing forward, 2 the backward; sg_upfirdn2d_launches likewise. */
+int sg_filtered_lrelu_gate(int dtype, const void* x, const float* fu, const float* fd, const void* b, void* y, void* gate, int N, int C, int H, int W,
+                           int fu_n, int fd_n, int up, int down, int px0, int px1, int py0, int py1, float gain, float slope, float clamp,
+                           int flip_filter, sg_stream_t s);
+int sg_filtered_lrelu_bwd(int dtype, const void* dy, const float* fu, const float* fd, const void* gate, void* dx, int N, int C, int H, int W,
+                          int fu_n, int fd_n, int up, int down, int px0, int px1, int py0, int py1, float gain, float slope, int flip_filter,
+                          sg_stream_t s);
+int sg_filtered_lrelu_bwd_tile(int cap);                   /* tools: cap (4 .. 16, default 16) of the backward's dx tile edge; returns the previous cap */
+long long sg_filtered_lrelu_launches(int what);
+long long sg_upfirdn2d_launches(void);
 /* sg_fir_bias_act_nhwc (csrc/style_fir.hip): a 2-D FIR of at most 4 x 4 taps on a dense channels-last tensor, x [N][Hi][Wi][C] -> y [N][Ho][Wo][C] of the
  * same dtype (fp32 / bf16), Ho = Hi + pady0 + pady1 - fh + 1, Wo likewise, with the tail of a StyleGAN2 synthesis layer on the fp32 accumulator:
  *   y = clamp( gain * act( filter_gain * sum F x  + noise[n][oy][ox] + bias[c] ) )

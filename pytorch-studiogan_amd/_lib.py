@@ -268,6 +268,11 @@ _PROTOS = {
     "sg_bias_act": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _i, _i, _i, _f, _f, _f, _vp],
     "sg_upfirdn2d": [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp],
     "sg_filtered_lrelu": [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _vp],
+    "sg_filtered_lrelu_gate": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _vp],
+    "sg_filtered_lrelu_bwd": [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _vp],
+    "sg_filtered_lrelu_bwd_tile": [_i],                    # returns the previous cap (call through lib(), not call())
+    "sg_filtered_lrelu_launches": [_i],                    # returns a count: 0 forward, 1 gate-writing forward, 2 backward
+    "sg_upfirdn2d_launches": [],                           # returns a count
     "sg_fir_bias_act_nhwc": [_i, _vp, _vp, _vp, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp],
     "sg_fir_bias_act_launches": [],                        # returns a count
     "sg_act_fir_nhwc": [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp],
@@ -341,6 +346,8 @@ def lib():
         l.sg_fir_bias_act_launches.restype = _ll
         l.sg_act_fir_launches.restype = _ll
         l.sg_mbstd_launches.restype = _ll
+        l.sg_filtered_lrelu_launches.restype = _ll
+        l.sg_upfirdn2d_launches.restype = _ll
         # SG_F32_MODE=bf16x3 | bf16x6: the generic engine's fp32 contractions process-wide on a split-precision path (functional.f32_mode is the scoped
         # form and says what each mode covers); default = exact fp32 MFMA
         f32_mode = {"bf16x3": 3, "bf16x6": 6}.get(os.environ.get("SG_F32_MODE", "exact"), 0)

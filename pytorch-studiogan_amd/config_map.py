@@ -77,19 +77,43 @@ def stylegan2_generator_args(y, mixed_precision=False):
                                   "conv_clamp": 256 if mixed_precision else None})
 
 
+def stylegan3_generator_args(y, mixed_precision=False):
+    """Keyword arguments of `backbones.stylegan3.Generator` for a `MODEL.backbone: stylegan3` configuration, as the reference builds it (src/models/model.py:26-36,
+    47-61): channel_base 32768 and channel_max 512 whatever the data set, both doubled with 1 x 1 kernels and radial filters for STYLEGAN.stylegan3_cfg = stylegan3-r;
+    magnitude_ema_beta = 0.5 ** (batch_size * acml_steps / 20e3), a half-life of 20k images; label-conditioned only under g_cond_mtd = cAdaIN; mixed precision =
+    the 4 highest resolutions in low precision with the layer outputs clamped to +-256. (`model_args` keeps refusing the StyleGAN backbones.)"""
+    import types
+    M, D, S, O = dict(y.get("MODEL") or {}), dict(y.get("DATA") or {}), dict(y.get("STYLEGAN") or {}), {**_OPT, **dict(y.get("OPTIMIZATION") or {})}
+    if M.get("backbone") != "stylegan3":
+        raise NotImplementedError(f"MODEL.backbone = {M.get('backbone')}: stylegan3_generator_args maps the stylegan3 generator only")
+    for sec, key in ((M, "w_dim"), (S, "mapping_network"), (S, "stylegan3_cfg")):
+        if sec.get(key, _N) == _N:
+            raise NotImplementedError(f"{'MODEL' if sec is M else 'STYLEGAN'}.{key} must be set for a stylegan3 generator")
+    if S["stylegan3_cfg"] not in ("stylegan3-t", "stylegan3-r"):
+        raise NotImplementedError(f"STYLEGAN.stylegan3_cfg = {S['stylegan3_cfg']} (stylegan3-t / stylegan3-r)")
+    rot = S["stylegan3_cfg"] == "stylegan3-r"
+    M = {**_MODEL, **M}
+    namespace = {k: M[k] for k in ("info_type", "g_info_injection", "info_num_discrete_c", "info_num_conti_c", "info_dim_discrete_c", "backbone")}
+    return dict(z_dim=M["z_dim"], c_dim=D.get("num_classes", 10) if M["g_cond_mtd"] == "cAdaIN" else 0, w_dim=M["w_dim"], img_resolution=D.get("img_size", 32),
+                img_channels=D.get("img_channels", 3), MODEL=types.SimpleNamespace(**namespace), mapping_kwargs={"num_layers": S["mapping_network"]},
+                synthesis_kwargs={"channel_base": 65536 if rot else 32768, "channel_max": 1024 if rot else 512, "num_fp16_res": 4 if mixed_precision else 0,
+                                  "conv_clamp": 256 if mixed_precision else None, "conv_kernel": 1 if rot else 3, "use_radial_filters": rot,
+                                  "magnitude_ema_beta": 0.5 ** (O["batch_size"] * O["acml_steps"] / (20 * 1e3))})
+
+
 def stylegan2_discriminator_args(y, mixed_precision=False):
     """Keyword arguments of `backbones.stylegan2_dis.Discriminator` for a `MODEL.backbone: stylegan2` configuration, as the reference builds it
     (src/models/model.py:26-36, 65-85): the generator's channel_base rule; label-conditioned (c_dim = num_classes) under d_cond_mtd PD / SPD / 2C / D2DCE;
     architecture and the minibatch-std group size from the STYLEGAN section; mixed precision as for the generator."""
     import types
     M, D, S = dict(y.get("MODEL") or {}), dict(y.get("DATA") or {}), dict(y.get("STYLEGAN") or {})
-    if M.get("backbone") != "stylegan2":
+    if M.get("backbone") not in ("stylegan2", "stylegan3"):      # (the reference pairs the stylegan3 generator with this discriminator, model.py:65)
         raise NotImplementedError(f"MODEL.backbone = {M.get('backbone')}: stylegan2_discriminator_args maps the stylegan2 discriminator only")
     for key in ("d_architecture", "d_epilogue_mbstd_group_size"):
         if S.get(key, _N) == _N:
             raise NotImplementedError(f"STYLEGAN.{key} must be set for a stylegan2 discriminator")
     img, name, ncls = D.get("img_size", 32), D.get("name", "CIFAR10"), D.get("num_classes", 10)
-    channel_base = 32768 if (img >= 512 or name in ("CIFAR10", "CIFAR100")) else 16384
+    channel_base = 32768 if (M["backbone"] == "stylegan3" or img >= 512 or name in ("CIFAR10", "CIFAR100")) else 16384
     M = {**_MODEL, **M}
     namespace = {k: M[k] for k in ("info_type", "g_info_injection", "info_num_discrete_c", "info_num_conti_c", "info_dim_discrete_c", "backbone")}
     return dict(c_dim=ncls if M["d_cond_mtd"] in ("PD", "SPD", "2C", "D2DCE") else 0, img_resolution=img, img_channels=D.get("img_channels", 3),
@@ -103,7 +127,7 @@ def stylegan2_r1_args(y):
     """The lazy R1 regulariser of a `MODEL.backbone: stylegan2` configuration and what it does to the discriminator's Adam (reference src/config.py:540-550):
     dict(r1_lambda, d_reg_interval, r1_place, lr, betas), lr and betas rescaled by d_ratio = d_reg_interval / (d_reg_interval + 1) (1 at an interval of 1)."""
     M, Ls, O, S = dict(y.get("MODEL") or {}), {**_LOSS, **dict(y.get("LOSS") or {})}, {**_OPT, **dict(y.get("OPTIMIZATION") or {})}, dict(y.get("STYLEGAN") or {})
-    if M.get("backbone") != "stylegan2":
+    if M.get("backbone") not in ("stylegan2", "stylegan3"):      # (a stylegan3 configuration trains the same discriminator)
         raise NotImplementedError(f"MODEL.backbone = {M.get('backbone')}: stylegan2_r1_args maps the stylegan2 discriminator only")
     if not Ls["apply_r1_reg"]:
         raise NotImplementedError("LOSS.apply_r1_reg must be set: stylegan2_r1_args maps the R1 regulariser")

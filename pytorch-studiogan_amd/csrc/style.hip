@@ -222,6 +222,8 @@ __global__ __launch_bounds__(256) void k_upfirdn2d(UpfirdnArgs a) {
     for (int e = 0; e < OPT; e++) if (xq * OPT + e < a.Wo) yp[e] = from_f<T>(acc[e]);
   }
 }
+static long long g_upfirdn_launches = 0;                  // tests: did the operator chain run
+extern "C" long long sg_upfirdn2d_launches() { return __atomic_load_n(&g_upfirdn_launches, __ATOMIC_RELAXED); }
 extern "C" int sg_upfirdn2d(int dtype, const void* x, const float* f, void* y, int planes, int H, int W, int fh, int fw, int upx, int upy,
                             int downx, int downy, int padx0, int padx1, int pady0, int pady1, int flip_filter, float gain, sg_stream_t s) {
   SG_CHECK(x && f && y && planes > 0 && H > 0 && W > 0, "sg_upfirdn2d: bad tensor arguments");
@@ -240,6 +242,7 @@ extern "C" int sg_upfirdn2d(int dtype, const void* x, const float* f, void* y, i
   else if (dtype == SG_DTYPE_BF16) hipLaunchKernelGGL((k_upfirdn2d<bf16_t, 4>), dim3((int)blocks), dim3(256), lds, (hipStream_t)s, a);
   else { sg_set_error("sg_upfirdn2d: fp32 / bf16 only"); return -1; }
   SG_LAUNCH_CHECK();
+  __atomic_fetch_add(&g_upfirdn_launches, 1, __ATOMIC_RELAXED);
   return 0;
 }
 
@@ -257,8 +260,15 @@ struct FlreluArgs {
   int fu_n, fd_n, up, down, px0, py0;
   int flip; float gain, slope, clamp;
   int TH, TW, AH, AW, IH, IW;          // tile extents: output, activated intermediate, input
+  unsigned char* gate; int AHt, AWt;   // GATE: the packed gate plane [planes][AHt][(AWt + 3) / 4] over the whole activated intermediate
 };
-template <typename T>
+// gate states, 2 bits per intermediate element, four elements per byte along x (element j in bits 2 * (j & 3)): what the backward multiplies by
+enum { FLR_ZERO = 0, FLR_POS = 1, FLR_NEG = 2 };       // 0 (clamped, or never computed), gain, gain * slope
+// GATE: the same arithmetic, and the state of every activated fp32 accumulator goes to a.gate for sg_filtered_lrelu_bwd. Neighbouring tiles recompute
+// overlapping intermediate rows / columns (AH > TH * down), so every element has ONE owner: the tile whose [j0, j0 + T * down) holds it, the last
+// tile of a row / column taking the tail up to AWt / AHt. Tile origins are multiples of 16 * down (a smaller tile is the only one of its axis), so an
+// owned span starts on a byte and ends on one or at the row's end: no byte has two writers, plain stores.
+template <typename T, bool GATE>
 __global__ __launch_bounds__(256) void k_filtered_lrelu(FlreluArgs a) {
   extern __shared__ float fl_sm[];
   float* s_fu = fl_sm;                                  // [fu_n] flipped as needed, x up (per-axis gain)
@@ -267,6 +277,7 @@ __global__ __launch_bounds__(256) void k_filtered_lrelu(FlreluArgs a) {
   float* s_t1 = s_in + a.IH * a.IW;                     // [IH][AW]
   float* s_mid = s_t1 + a.IH * a.AW;                    // [AH][AW]
   float* s_t2 = s_mid + a.AH * a.AW;                    // [AH][TW]
+  unsigned char* s_gs = (unsigned char*)(s_t2 + a.AH * a.TW);     // GATE: [AH][AW] states
   const int tid = threadIdx.x;
   for (int i = tid; i < a.fu_n; i += 256) s_fu[i] = a.fu[a.flip ? i : a.fu_n - 1 - i] * (float)a.up;
   for (int i = tid; i < a.fd_n; i += 256) s_fd[i] = a.fd[a.flip ? i : a.fd_n - 1 - i];
@@ -318,10 +329,25 @@ __global__ __launch_bounds__(256) void k_filtered_lrelu(FlreluArgs a) {
       acc += s_fu[t] * s_t1[r * a.AW + j];
     }
     float v = (acc > 0.f ? acc : acc * a.slope) * a.gain;
+    if (GATE) s_gs[e] = (a.clamp >= 0.f && !(v > -a.clamp && v < a.clamp)) ? FLR_ZERO : (acc > 0.f ? FLR_POS : FLR_NEG);     // sg_bias_act's gradient rule
     if (a.clamp >= 0.f) v = fminf(fmaxf(v, -a.clamp), a.clamp);
     s_mid[e] = v;
   }
   __syncthreads();
+  if (GATE) {
+    const int rows = (by == ty - 1 ? a.AHt : jy0 + a.TH * a.down) - jy0;                            // owned rows, and owned bytes of a row
+    const int gwb = (a.AWt + 3) / 4, q0 = jx0 / 4, nb = (bx == tx - 1 ? gwb : (jx0 + a.TW * a.down) / 4) - q0;
+    unsigned char* gp = a.gate + ((long long)pl * a.AHt + jy0) * gwb + q0;
+    for (int e = tid; e < rows * nb; e += 256) {
+      const int i = e / nb, q = e - i * nb;
+      unsigned v = 0;
+      for (int k = 0; k < 4; k++) {
+        const int j = q * 4 + k;
+        if (i < a.AH && j < a.AW && jx0 + j < a.AWt) v |= (unsigned)s_gs[i * a.AW + j] << (2 * k);   // beyond the tile's extent no output reads the element
+      }
+      gp[(long long)i * gwb + q] = (unsigned char)v;
+    }
+  }
   // horizontal down-FIR: t2[i][ox] = sum_t fd'[t] * mid[i][ox * down + t]
   for (int e = tid; e < a.AH * a.TW; e += 256) {
     const int i = e / a.TW, ox = e - i * a.TW;
@@ -342,9 +368,11 @@ __global__ __launch_bounds__(256) void k_filtered_lrelu(FlreluArgs a) {
 }
 // fu / fd: separable fp32 filters on the device (fu_n / fd_n taps, >= 1; a one-tap {1} filter is the identity). Returns -3 when the tile does
 // not fit the kernel's LDS budget (the caller then runs the chain of sg_bias_act / sg_upfirdn2d launches, which has no such limit).
-extern "C" int sg_filtered_lrelu(int dtype, const void* x, const float* fu, const float* fd, const void* b, void* y, int N, int C, int H, int W,
-                                 int fu_n, int fd_n, int up, int down, int px0, int px1, int py0, int py1, float gain, float slope, float clamp,
-                                 int flip_filter, sg_stream_t s) {
+static long long g_flr_launches[3] = {0, 0, 0};           // forward, gate-writing forward, backward
+extern "C" long long sg_filtered_lrelu_launches(int what) { return (what >= 0 && what < 3) ? __atomic_load_n(&g_flr_launches[what], __ATOMIC_RELAXED) : -1; }
+static int filtered_lrelu_fwd(int dtype, const void* x, const float* fu, const float* fd, const void* b, void* y, void* gate, int N, int C, int H, int W,
+                              int fu_n, int fd_n, int up, int down, int px0, int px1, int py0, int py1, float gain, float slope, float clamp,
+                              int flip_filter, sg_stream_t s) {
   SG_CHECK(x && fu && fd && y && N > 0 && C > 0 && H > 0 && W > 0, "sg_filtered_lrelu: bad tensor arguments");
   SG_CHECK(fu_n >= 1 && fd_n >= 1 && up >= 1 && down >= 1 && gain > 0.f && slope >= 0.f, "sg_filtered_lrelu: bad filter / factor / gain arguments");
   const int Wo = (W * up + px0 + px1 - (fu_n - 1) - (fd_n - 1) + (down - 1)) / down;
@@ -354,16 +382,170 @@ extern "C" int sg_filtered_lrelu(int dtype, const void* x, const float* fu, cons
   a.x = x; a.b = b; a.fu = fu; a.fd = fd; a.y = y; a.planes = N * C; a.C = C; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo;
   a.fu_n = fu_n; a.fd_n = fd_n; a.up = up; a.down = down; a.px0 = px0; a.py0 = py0; a.flip = flip_filter ? 1 : 0;
   a.gain = gain; a.slope = slope; a.clamp = clamp;
+  a.gate = (unsigned char*)gate; a.AHt = H * up + py0 + py1 - (fu_n - 1); a.AWt = W * up + px0 + px1 - (fu_n - 1);
   a.TH = Ho < 16 ? Ho : 16; a.TW = Wo < 16 ? Wo : 16;
   a.AH = (a.TH - 1) * down + fd_n; a.AW = (a.TW - 1) * down + fd_n;
   a.IH = (a.AH + fu_n - 1 + up - 1) / up + 1; a.IW = (a.AW + fu_n - 1 + up - 1) / up + 1;
-  const size_t lds = sizeof(float) * ((size_t)fu_n + fd_n + (size_t)a.IH * a.IW + (size_t)a.IH * a.AW + (size_t)a.AH * a.AW + (size_t)a.AH * a.TW);
+  const size_t lds = sizeof(float) * ((size_t)fu_n + fd_n + (size_t)a.IH * a.IW + (size_t)a.IH * a.AW + (size_t)a.AH * a.AW + (size_t)a.AH * a.TW) +
+                     (gate ? (size_t)a.AH * a.AW : 0);
   if (lds > 64 * 1024) { sg_set_error("sg_filtered_lrelu: tile does not fit the LDS budget (use the operator chain)"); return -3; }
   const long long blocks = (long long)a.planes * ((Ho + a.TH - 1) / a.TH) * ((Wo + a.TW - 1) / a.TW);
   SG_CHECK(blocks < (1ll << 31), "sg_filtered_lrelu: too many tiles");
-  if (dtype == SG_DTYPE_F32) hipLaunchKernelGGL(k_filtered_lrelu<float>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)s, a);
-  else if (dtype == SG_DTYPE_BF16) hipLaunchKernelGGL(k_filtered_lrelu<bf16_t>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)s, a);
-  else { sg_set_error("sg_filtered_lrelu: fp32 / bf16 only"); return -1; }
+  if (dtype == SG_DTYPE_F32) {
+    if (gate) hipLaunchKernelGGL((k_filtered_lrelu<float, true>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)s, a);
+    else hipLaunchKernelGGL((k_filtered_lrelu<float, false>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)s, a);
+  } else if (dtype == SG_DTYPE_BF16) {
+    if (gate) hipLaunchKernelGGL((k_filtered_lrelu<bf16_t, true>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)s, a);
+    else hipLaunchKernelGGL((k_filtered_lrelu<bf16_t, false>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)s, a);
+  } else { sg_set_error("sg_filtered_lrelu: fp32 / bf16 only"); return -1; }
   SG_LAUNCH_CHECK();
+  __atomic_fetch_add(&g_flr_launches[gate ? 1 : 0], 1, __ATOMIC_RELAXED);
+  return 0;
+}
+extern "C" int sg_filtered_lrelu(int dtype, const void* x, const float* fu, const float* fd, const void* b, void* y, int N, int C, int H, int W,
+                                 int fu_n, int fd_n, int up, int down, int px0, int px1, int py0, int py1, float gain, float slope, float clamp,
+                                 int flip_filter, sg_stream_t s) {
+  return filtered_lrelu_fwd(dtype, x, fu, fd, b, y, nullptr, N, C, H, W, fu_n, fd_n, up, down, px0, px1, py0, py1, gain, slope, clamp, flip_filter, s);
+}
+extern "C" int sg_filtered_lrelu_gate(int dtype, const void* x, const float* fu, const float* fd, const void* b, void* y, void* gate, int N, int C, int H,
+                                      int W, int fu_n, int fd_n, int up, int down, int px0, int px1, int py0, int py1, float gain, float slope,
+                                      float clamp, int flip_filter, sg_stream_t s) {
+  SG_CHECK(gate, "sg_filtered_lrelu_gate: no gate plane");
+  return filtered_lrelu_fwd(dtype, x, fu, fd, b, y, gate, N, C, H, W, fu_n, fd_n, up, down, px0, px1, py0, py1, gain, slope, clamp, flip_filter, s);
+}
+
+// ---- filtered_lrelu, backward, separable filters: ONE launch ------------------------------------------------------------------------------
+//   dx = upfir_fu^T( gate (.) downfir_fd^T(dy) )        (the reference runs its forward kernel with the roles swapped, filtered_lrelu.py:251-262)
+// with the forward's effective filters fu'[t] = up * fu[flip ? t : fu_n - 1 - t], fd'[t] likewise without the factor, per axis:
+//   dm[j] = sum_o fd'[j - o * down] dy[o]       (the fd_n / down taps of j's polyphase component)
+//   du    = scale(gate) * dm,  scale = gain | gain * slope | 0
+//   dx[k] = sum_t fu'[t] du[k * up + p0 - t]
+// Per workgroup: one dx tile of one (n, c) plane, everything between in LDS as fp32:
+//   dy [DH][DW] (zeros outside) -> horizontal fd^T -> t1 [DH][BW] -> vertical fd^T, times the gate -> mid [BH][BW] (zeros outside the intermediate)
+//   -> horizontal fu^T -> t2 [BH][TW] -> vertical fu^T -> dx tile [TH][TW]
+struct FlreluBwdArgs {
+  const void* dy; const float* fu; const float* fd; const unsigned char* gate; void* dx;
+  int planes, H, W, Ho, Wo, AHt, AWt;
+  int fu_n, fd_n, up, down, px0, py0;
+  int flip; float gain, slope;
+  int TH, TW, BH, BW, DH, DW;          // tile extents: dx, gated intermediate, dy
+};
+__device__ __forceinline__ int flr_floordiv(int v, int d) { return v >= 0 ? v / d : -((-v + d - 1) / d); }
+template <typename T>
+__global__ __launch_bounds__(256) void k_filtered_lrelu_bwd(FlreluBwdArgs a) {
+  extern __shared__ float fl_sm[];
+  float* s_fu = fl_sm;                                  // [fu_n] the forward's effective taps
+  float* s_fd = s_fu + a.fu_n;                          // [fd_n]
+  float* s_dy = s_fd + a.fd_n;                          // [DH][DW]
+  float* s_t1 = s_dy + a.DH * a.DW;                     // [DH][BW]
+  float* s_mid = s_t1 + a.DH * a.BW;                    // [BH][BW]
+  float* s_t2 = s_mid + a.BH * a.BW;                    // [BH][TW]
+  const int tid = threadIdx.x;
+  for (int i = tid; i < a.fu_n; i += 256) s_fu[i] = a.fu[a.flip ? i : a.fu_n - 1 - i] * (float)a.up;
+  for (int i = tid; i < a.fd_n; i += 256) s_fd[i] = a.fd[a.flip ? i : a.fd_n - 1 - i];
+  const int tx = (a.W + a.TW - 1) / a.TW, ty = (a.H + a.TH - 1) / a.TH;
+  int bid = blockIdx.x;
+  const int bx = bid % tx; bid /= tx;
+  const int by = bid % ty;
+  const int pl = bid / ty;
+  const int kx0 = bx * a.TW, ky0 = by * a.TH;
+  const int jx0 = kx0 * a.up + a.px0 - (a.fu_n - 1), jy0 = ky0 * a.up + a.py0 - (a.fu_n - 1);      // first intermediate coordinate the tile reads (may be < 0)
+  const int ox0 = flr_floordiv(jx0 - (a.fd_n - 1) + a.down - 1, a.down), oy0 = flr_floordiv(jy0 - (a.fd_n - 1) + a.down - 1, a.down);   // first dy coordinate
+  const T* dyp = (const T*)a.dy + (long long)pl * a.Ho * a.Wo;
+  for (int e = tid; e < a.DH * a.DW; e += 256) {
+    const int r = e / a.DW, c = e - r * a.DW;
+    const int oy = oy0 + r, ox = ox0 + c;
+    s_dy[e] = (oy >= 0 && oy < a.Ho && ox >= 0 && ox < a.Wo) ? to_f<T>(dyp[(long long)oy * a.Wo + ox]) : 0.f;
+  }
+  __syncthreads();
+  // horizontal fd^T: t1[r][j] = sum_o fd'[J - o * down] dy[r][o], J = jx0 + j
+  for (int e = tid; e < a.DH * a.BW; e += 256) {
+    const int r = e / a.BW, j = e - r * a.BW;
+    const int J = jx0 + j;
+    float acc = 0.f;
+    for (int t = ((J % a.down) + a.down) % a.down; t < a.fd_n; t += a.down) {
+      const int c = (J - t) / a.down - ox0;              // (J - t is a multiple of down)
+      if (c < 0) break;
+      if (c < a.DW) acc += s_fd[t] * s_dy[r * a.DW + c];
+    }
+    s_t1[e] = acc;
+  }
+  __syncthreads();
+  // vertical fd^T, then the gate
+  const int gwb = (a.AWt + 3) / 4;
+  const unsigned char* gp = a.gate + (long long)pl * a.AHt * gwb;
+  for (int e = tid; e < a.BH * a.BW; e += 256) {
+    const int i = e / a.BW, j = e - i * a.BW;
+    const int I = jy0 + i, J = jx0 + j;
+    float v = 0.f;
+    if (I >= 0 && I < a.AHt && J >= 0 && J < a.AWt) {
+      float acc = 0.f;
+      for (int t = ((I % a.down) + a.down) % a.down; t < a.fd_n; t += a.down) {
+        const int r = (I - t) / a.down - oy0;
+        if (r < 0) break;
+        if (r < a.DH) acc += s_fd[t] * s_t1[r * a.BW + j];
+      }
+      const unsigned g = (gp[(long long)I * gwb + (J >> 2)] >> (2 * (J & 3))) & 3u;
+      v = g == FLR_POS ? acc * a.gain : (g == FLR_NEG ? acc * (a.gain * a.slope) : 0.f);
+    }
+    s_mid[e] = v;
+  }
+  __syncthreads();
+  // horizontal fu^T: t2[i][kx] = sum_t fu'[t] mid[i][kx * up + fu_n - 1 - t]
+  for (int e = tid; e < a.BH * a.TW; e += 256) {
+    const int i = e / a.TW, kx = e - i * a.TW;
+    const float* m = s_mid + i * a.BW + kx * a.up + a.fu_n - 1;
+    float acc = 0.f;
+    for (int t = 0; t < a.fu_n; t++) acc += s_fu[t] * m[-t];
+    s_t2[e] = acc;
+  }
+  __syncthreads();
+  T* dxp = (T*)a.dx + (long long)pl * a.H * a.W;
+  for (int e = tid; e < a.TH * a.TW; e += 256) {
+    const int ky = e / a.TW, kx = e - ky * a.TW;
+    if (ky0 + ky >= a.H || kx0 + kx >= a.W) continue;
+    float acc = 0.f;
+    for (int t = 0; t < a.fu_n; t++) acc += s_fu[t] * s_t2[(ky * a.up + a.fu_n - 1 - t) * a.TW + kx];
+    dxp[(long long)(ky0 + ky) * a.W + kx0 + kx] = from_f<T>(acc);
+  }
+}
+// The FORWARD's arguments, dy [N][C][Ho][Wo], the gate plane sg_filtered_lrelu_gate wrote -> dx [N][C][H][W]. The dx tile: each axis is cut into the fewest
+// pieces of at most `cap` (16 unless sg_filtered_lrelu_bwd_tile set another) and the pieces are made equal, so a 38-wide plane runs as 3 x 13, not 3 x 16 with
+// a quarter of the last tile beyond the edge; the cap halves until the LDS fits 64 KB; -3 when not even 4 does (the caller differentiates the chain).
+static int g_flr_bwd_tile = 16;
+extern "C" int sg_filtered_lrelu_bwd_tile(int cap) {        // tools / A-B: the cap (4 .. 16) of the backward's tile edge; returns the previous one
+  const int old = g_flr_bwd_tile;
+  if (cap >= 4 && cap <= 16) g_flr_bwd_tile = cap;
+  return old;
+}
+extern "C" int sg_filtered_lrelu_bwd(int dtype, const void* dy, const float* fu, const float* fd, const void* gate, void* dx, int N, int C, int H, int W,
+                                     int fu_n, int fd_n, int up, int down, int px0, int px1, int py0, int py1, float gain, float slope,
+                                     int flip_filter, sg_stream_t s) {
+  SG_CHECK(dy && fu && fd && gate && dx && N > 0 && C > 0 && H > 0 && W > 0, "sg_filtered_lrelu_bwd: bad tensor arguments");
+  SG_CHECK(fu_n >= 1 && fd_n >= 1 && up >= 1 && down >= 1 && gain > 0.f && slope >= 0.f, "sg_filtered_lrelu_bwd: bad filter / factor / gain arguments");
+  FlreluBwdArgs a;
+  a.dy = dy; a.fu = fu; a.fd = fd; a.gate = (const unsigned char*)gate; a.dx = dx; a.planes = N * C; a.H = H; a.W = W;
+  a.AHt = H * up + py0 + py1 - (fu_n - 1); a.AWt = W * up + px0 + px1 - (fu_n - 1);
+  a.Ho = (a.AHt - (fd_n - 1) + (down - 1)) / down; a.Wo = (a.AWt - (fd_n - 1) + (down - 1)) / down;
+  SG_CHECK(a.Wo >= 1 && a.Ho >= 1, "sg_filtered_lrelu_bwd: empty output");
+  a.fu_n = fu_n; a.fd_n = fd_n; a.up = up; a.down = down; a.px0 = px0; a.py0 = py0; a.flip = flip_filter ? 1 : 0; a.gain = gain; a.slope = slope;
+  size_t lds = 0;
+  int tile = g_flr_bwd_tile;
+  for (; tile >= 4; tile /= 2) {
+    const int ny = (H + tile - 1) / tile, nx = (W + tile - 1) / tile;
+    a.TH = (H + ny - 1) / ny; a.TW = (W + nx - 1) / nx;
+    a.BH = (a.TH - 1) * up + fu_n; a.BW = (a.TW - 1) * up + fu_n;
+    a.DH = (a.BH + fd_n - 2) / down + 1; a.DW = (a.BW + fd_n - 2) / down + 1;
+    lds = sizeof(float) * ((size_t)fu_n + fd_n + (size_t)a.DH * a.DW + (size_t)a.DH * a.BW + (size_t)a.BH * a.BW + (size_t)a.BH * a.TW);
+    if (lds <= 64 * 1024) break;
+  }
+  if (tile < 4) { sg_set_error("sg_filtered_lrelu_bwd: no tile fits the LDS budget (differentiate the operator chain)"); return -3; }
+  const long long blocks = (long long)a.planes * ((H + a.TH - 1) / a.TH) * ((W + a.TW - 1) / a.TW);
+  SG_CHECK(blocks < (1ll << 31), "sg_filtered_lrelu_bwd: too many tiles");
+  if (dtype == SG_DTYPE_F32) hipLaunchKernelGGL(k_filtered_lrelu_bwd<float>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)s, a);
+  else if (dtype == SG_DTYPE_BF16) hipLaunchKernelGGL(k_filtered_lrelu_bwd<bf16_t>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)s, a);
+  else { sg_set_error("sg_filtered_lrelu_bwd: fp32 / bf16 only"); return -1; }
+  SG_LAUNCH_CHECK();
+  __atomic_fetch_add(&g_flr_launches[2], 1, __ATOMIC_RELAXED);
   return 0;
 }

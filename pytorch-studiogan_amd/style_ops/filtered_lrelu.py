@@ -3,9 +3,12 @@ reference src/utils/style_ops/filtered_lrelu.py:54-155). The reference ships a t
 take, the chain of its own bias_act / upfirdn2d operators (filtered_lrelu.py:140-146). Here:
   * forward with separable (1-D or absent) filters: ONE launch, csrc/style.hip sg_filtered_lrelu -- the up-sampled intermediate (up^2 times the
     input) stays in LDS instead of crossing HBM twice;
-  * 2-D filters, tiles beyond the LDS budget, and every BACKWARD: the chain of sg_bias_act / sg_upfirdn2d launches, each a differentiable
-    autograd Function, so gradients of any order come from the operators themselves (the backward re-runs the chain on the saved input:
-    the fused forward keeps no intermediate)."""
+  * first-order backward of that forward: ONE launch, sg_filtered_lrelu_bwd. When a gradient is needed the forward (sg_filtered_lrelu_gate, same y bit
+    for bit) also writes a 2-bit gate per activated intermediate element, taken from the fp32 accumulator it activates, and the backward reads it where
+    the forward applies the leaky ReLU (the reference's bit-packed sign tensor, filtered_lrelu.py:204-267);
+  * 2-D filters, tiles beyond the LDS budget, and every backward under create_graph: the chain of sg_bias_act / sg_upfirdn2d launches, each a
+    differentiable autograd Function, so gradients of any order come from the operators themselves (the backward re-runs the chain on the saved
+    input)."""
 import numpy as np
 import torch
 
@@ -70,6 +73,7 @@ def filtered_lrelu(x, fu=None, fd=None, b=None, up=1, down=1, padding=0, gain=np
 
 
 _FUSED = [True]        # tests / A-B: filtered_lrelu._FUSED[0] = False runs the operator chain for the forward as well
+_FUSED_BWD = [True]    # tests / A-B: False = the backward differentiates the operator chain (four launches each way) and the forward writes no gate
 
 
 def _chain(x, b, fu, fd, cfg):
@@ -97,25 +101,39 @@ class _FilteredLRelu(torch.autograd.Function):
         y = torch.empty((N, C, Ho, Wo), dtype=x.dtype, device=x.device)
         bc = None if b is None else b.to(x.dtype).contiguous()
         rc = 0
-        if N * C > 0:
+        gate = None
+        if _FUSED_BWD[0] and N * C > 0 and (ctx.needs_input_grad[0] or (b is not None and ctx.needs_input_grad[1])):
+            ah, aw = H * up + py0 + py1 - (fu_d.numel() - 1), W * up + px0 + px1 - (fu_d.numel() - 1)
+            gate = torch.empty((N * C, ah, (aw + 3) // 4), dtype=torch.uint8, device=x.device)      # the kernel writes every byte
+            rc = L.lib().sg_filtered_lrelu_gate(L.dt(xc), L.ptr(xc), L.ptr(fu_d), L.ptr(fd_d), L.ptr(bc), L.ptr(y), L.ptr(gate), N, C, H, W, fu_d.numel(),
+                                                fd_d.numel(), up, down, px0, px1, py0, py1, gain, slope, -1.0 if clamp is None else clamp,
+                                                1 if flip else 0, L.stream())
+        elif N * C > 0:
             rc = L.lib().sg_filtered_lrelu(L.dt(xc), L.ptr(xc), L.ptr(fu_d), L.ptr(fd_d), L.ptr(bc), L.ptr(y), N, C, H, W, fu_d.numel(), fd_d.numel(),
                                            up, down, px0, px1, py0, py1, gain, slope, -1.0 if clamp is None else clamp, 1 if flip else 0, L.stream())
         if rc == -3:                    # tile beyond the LDS budget: the chain has no such limit
+            gate = None
             with torch.no_grad():
                 y = _chain(x, b, fu, fd, cfg)
         elif rc != 0:
             raise RuntimeError("sg_filtered_lrelu: " + L.lib().sg_last_error().decode())
-        ctx.save_for_backward(x, b, fu, fd)
+        ctx.save_for_backward(x, b, fu, fd, gate, fu_d, fd_d)
         ctx.cfg = cfg
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, b, fu, fd = ctx.saved_tensors
+        x, b, fu, fd, gate, fu_d, fd_d = ctx.saved_tensors
         need_x, need_b = ctx.needs_input_grad[0], (b is not None and ctx.needs_input_grad[1])
         ctx.second_order = torch.is_grad_enabled()
         if not (need_x or need_b):
             return None, None, None, None, None
+        if gate is not None and not ctx.second_order and _FUSED_BWD[0]:
+            gx = _fused_backward(dy, x, gate, fu_d, fd_d, ctx.cfg)
+            if gx is not None:
+                # the bias enters before everything else, so its gradient is dx summed over the input-sized plane (fp32 accumulation)
+                gb = gx.sum([0, 2, 3], dtype=torch.float32).to(b.dtype) if need_b else None
+                return (gx if need_x else None), gb, None, None, None
         # re-run the differentiable operator chain on the saved input and differentiate it (the fused forward keeps no intermediate);
         # under create_graph the result stays differentiable through the operators' own backward Functions
         with torch.enable_grad():
@@ -128,3 +146,19 @@ class _FilteredLRelu(torch.autograd.Function):
         gx = gs.pop(0) if need_x else None
         gb = gs.pop(0) if need_b else None
         return gx, gb, None, None, None
+
+
+def _fused_backward(dy, x, gate, fu_d, fd_d, cfg):
+    """dx in one sg_filtered_lrelu_bwd launch from the gate plane the forward wrote; None when no tile fits the LDS budget (rc -3)"""
+    from .. import _lib as L
+    up, down, (px0, px1, py0, py1), gain, slope, clamp, flip = cfg
+    N, C, H, W = x.shape
+    dyc = dy.to(x.dtype).contiguous()
+    dx = torch.empty((N, C, H, W), dtype=x.dtype, device=x.device)
+    rc = L.lib().sg_filtered_lrelu_bwd(L.dt(dyc), L.ptr(dyc), L.ptr(fu_d), L.ptr(fd_d), L.ptr(gate), L.ptr(dx), N, C, H, W, fu_d.numel(), fd_d.numel(),
+                                       up, down, px0, px1, py0, py1, gain, slope, 1 if flip else 0, L.stream())
+    if rc == -3:
+        return None
+    if rc != 0:
+        raise RuntimeError("sg_filtered_lrelu_bwd: " + L.lib().sg_last_error().decode())
+    return dx

@@ -101,7 +101,9 @@ class _ModConvFn(torch.autograd.Function):
     transposed convolution, in front of the FIR"""
 
     @staticmethod
-    def forward(ctx, x, weight, styles, noise, up, demodulate, flip_weight):
+    def forward(ctx, x, weight, styles, noise, up, demodulate, flip_weight, post_gain=None):
+        """post_gain: None, or a one-element fp32 tensor g (a constant: no gradient) with y = g * d * conv(W, s * x): it rides in the per-[N, Cout] post-scale
+        table, g * d, or g alone without demodulation (StyleGAN3's input_gain; no elementwise pass of its own)"""
         N, C, H, W = x.shape
         Cout, k = weight.shape[0], weight.shape[2]
         xh = x.permute(0, 2, 3, 1).contiguous()                 # NHWC in memory: free for a channels_last x
@@ -120,15 +122,19 @@ class _ModConvFn(torch.autograd.Function):
         if noise is not None:
             nz = noise.detach().to(torch.float32).contiguous()
             nstride = H * W if nz.dim() == 4 else 0
-        y = _modconv_raw(xh, wimg, Cout, k, "same" if up == 1 else "up2", pre=s32, post=dco, noise=nz, noise_stride=nstride)
-        ctx.save_for_backward(xh, w32, s32, Q, dco, y, nz)
+        post = dco
+        if post_gain is not None:
+            g = post_gain.detach().to(torch.float32).reshape(1, 1)
+            post = dco * g if demodulate else g.expand(N, Cout).contiguous()
+        y = _modconv_raw(xh, wimg, Cout, k, "same" if up == 1 else "up2", pre=s32, post=post, noise=nz, noise_stride=nstride)
+        ctx.save_for_backward(xh, w32, s32, Q, dco, y, nz, post)
         ctx.cfg = (up, demodulate, flipped, k, weight.dtype, styles.dtype, None if noise is None else (noise.dtype, tuple(noise.shape)))
         return y.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, gy):
         _first_order_only("modulated_conv2d")
-        xh, w32, s32, Q, dco, y, nz = ctx.saved_tensors
+        xh, w32, s32, Q, dco, y, nz, post = ctx.saved_tensors       # post = g d (dco when there is no post_gain): what scales gy; d alone stays in gd d^3
         up, demodulate, flipped, k, w_dtype, s_dtype, noise_info = ctx.cfg
         N, H, W, C = xh.shape
         Cout = w32.shape[0]
@@ -139,17 +145,19 @@ class _ModConvFn(torch.autograd.Function):
         # gu = d gy, d gd = sum_p gy (y - noise), dnoise = sum_o gy: one pass over gy and y
         gu, dgd, gnoise = gyh, None, None
         if demodulate:
-            gu, dgd, gnoise = _reduce_raw(gyh, b=y, rowsub=nz, rowsub_stride=(H * W if (nz is not None and nz.dim() == 4) else 0), scale=dco,
+            gu, dgd, gnoise = _reduce_raw(gyh, b=y, rowsub=nz, rowsub_stride=(H * W if (nz is not None and nz.dim() == 4) else 0), scale=post,
                                           want_rowsum=need_noise)
+        elif post is not None:
+            gu, _, gnoise = _reduce_raw(gyh, scale=post, want_rowsum=need_noise)
         elif need_noise:
             _, _, gnoise = _reduce_raw(gyh, want_rowsum=True)
         # unscaled data gradient through the same kernel (d rides on gy as its pre-scale: fp32 product, one rounding), then dx = s gxs, sum_p x gxs
         if up == 1:
             wd = weff.flip(2, 3).permute(1, 2, 3, 0).contiguous().to(T)          # [C][2-r][2-s][Cout]
-            gxs = _modconv_raw(gyh, wd, C, k, "same", pre=dco)
+            gxs = _modconv_raw(gyh, wd, C, k, "same", pre=post)
         else:
             wd = weff.permute(1, 2, 3, 0).contiguous().to(T)                     # [C][r][s][Cout]: gxs[h,w] = sum gu[2h+r, 2w+s] W[r,s]
-            gxs = _modconv_raw(gyh, wd, C, k, "down2", pre=dco)
+            gxs = _modconv_raw(gyh, wd, C, k, "down2", pre=post)
         dx, ds, _ = _reduce_raw(gxs, b=xh, scale=s32)
         t = None
         if demodulate:
@@ -175,7 +183,7 @@ class _ModConvFn(torch.autograd.Function):
         if need_noise:
             dn = gnoise.reshape(N, 1, H, W) if len(noise_info[1]) == 4 else gnoise.sum(dim=0).reshape(H, W)
             dn = dn.to(noise_info[0])
-        return dx.permute(0, 3, 1, 2), dw, ds.to(s_dtype), dn, None, None, None
+        return dx.permute(0, 3, 1, 2), dw, ds.to(s_dtype), dn, None, None, None, None
 
 
 def modulated_conv2d(x, weight, styles, noise=None, up=1, down=1, padding=0, resample_filter=None, demodulate=True, flip_weight=True, fused_modconv=True):
