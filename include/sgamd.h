@@ -144,6 +144,21 @@ typedef struct {
 int sg_modconv2d_fwd(const sg_modconv_desc* d, sg_stream_t stream);
 int sg_modconv2d_ok(const sg_modconv_desc* d);             /* 1 when the kernel takes the problem, else 0 */
 long long sg_modconv_launches(void);                       /* launches so far (tests: which kernel ran) */
+/* sg_modconv2d_jvp: the forward-mode tangent of sg_modconv2d_fwd along (vx, vs), one launch (second order: path-length regularisation):
+ *   out[n,p,o] = post[n,o] * alpha * conv(w, pre[n,c] * vx + vs[n,c] * x)[n,p,o] + e[n,o] * ( y[n,p,o] - noise[n,p] )
+ * m: the forward's descriptor (conv.x = x, pre = the styles, post, and the noise the forward added to y) with conv.out the tangent; vx: x's layout and
+ * dtype; vs: fp32 [N][C]; y: the forward's stored result, pixel pitch ldy; e: fp32 [N][Cout], the tangent of the demodulation coefficient over the
+ * coefficient, or NULL (no demodulation: y and noise are not read). vs * x + pre * vx is formed in fp32 and rounded once to the MFMA operand; post and the
+ * second term meet the fp32 accumulator, one rounding on store. pre, vs and vx are required. */
+typedef struct {
+  sg_modconv_desc m;
+  const void* vx; const float* vs;
+  const void* y; const float* e;
+  int ldy; int pad_;
+} sg_modconv_jvp_desc;
+int sg_modconv2d_jvp(const sg_modconv_jvp_desc* d, sg_stream_t stream);
+int sg_modconv2d_jvp_ok(const sg_modconv_jvp_desc* d);     /* 1 when the kernel takes the problem, else 0 */
+long long sg_modconv_jvp_launches(void);                   /* launches so far (tests: one per second-order pass) */
 /* Q[o][c] = sum_{r,s} w[o][c][r][s]^2 from the fp32 [Cout][C][RS] weight; with styles s (fp32 [N][C]) also the demodulation coefficients
  * d[n][o] = (sum_c s[n][c]^2 Q[o][c] + 1e-8)^(-1/2). s and d both NULL: Q only. Always fp32, as the reference computes them. */
 int sg_modconv_dcoef(const float* w, const float* s, float* Q, float* d, int N, int C, int Cout, int RS, sg_stream_t stream);
@@ -689,7 +704,16 @@ long long sg_upfirdn2d_launches(void);
 int sg_fir_bias_act_nhwc(int dtype, const void* x, const float* f, void* y, const float* noise, long long noise_stride, const float* bias,
                          int N, int Hi, int Wi, int C, int fh, int fw, int padx0, int padx1, int pady0, int pady1, int flip_filter,
                          float filter_gain, int act, float alpha, float gain, float clamp, sg_stream_t s);
-long long sg_fir_bias_act_launches(void);                  /* launches so far (tests: which kernel ran) */
+/* sg_fir_bias_act_nhwc_gate: the second-order pass of sg_fir_bias_act_nhwc in one launch. The tail's backward is dx = FIR^T(m * dy), m the slope / gain /
+ * clamp gate taken from the kept output y; with cotangents v on dx, v_noise on dnoise, v_bias on dbias (the latter two fp32, optional, laid out as the forward's
+ * noise and bias):   out [N][Ho][Wo][C] = m(y) * ( FIR(v) + v_noise[n][oy][ox] + v_bias[c] ),   the FORWARD's filter, padding and flip. m = gain (gain * alpha
+ * where y / gain <= 0 under lrelu), 0 where y is at or beyond the clamp: sg_bias_act's gradient rule on (dy, y), so both passes decide every element alike.
+ * y: [N][Ho][Wo][C] of v's dtype; may be NULL when act = 1, gain = 1 and clamp < 0 -- the launch is then sg_fir_bias_act_nhwc's plain one bit for bit.
+ * Nothing flows to x, noise or bias (the activation is piecewise linear). Counted by sg_fir_bias_act_launches. */
+int sg_fir_bias_act_nhwc_gate(int dtype, const void* v, const void* y, const float* f, void* out, const float* v_noise, long long noise_stride,
+                              const float* v_bias, int N, int Hi, int Wi, int C, int fh, int fw, int padx0, int padx1, int pady0, int pady1,
+                              int flip_filter, float filter_gain, int act, float alpha, float gain, float clamp, sg_stream_t s);
+long long sg_fir_bias_act_launches(void);                  /* forward + gate launches so far (tests: which kernel ran) */
 /* sg_act_fir_nhwc (csrc/style_fir.hip): the head of a StyleGAN2 discriminator down layer, activation on the LOAD side of a decimating FIR. x [N][Hi][Wi][C]
  * dense channels-last -> y [N][Ho][Wo][C] of the same dtype (fp32 / bf16), Ho = (Hi + pady0 + pady1 - fh) / down + 1 (floor), Wo likewise:
  *   a = clamp( gain * act( x + bias[c] ) ) inside the image, 0 outside (never act(bias));   y = filter_gain * sum F a[oy * down - pady0 + fy][ox * down - padx0 + fx]

@@ -40,6 +40,10 @@ class ModConvDesc(C.Structure):
     _fields_ = [("conv", ConvFwdDesc), ("pre", _vp), ("post", _vp), ("noise", _vp), ("noise_stride", _ll)]
 
 
+class ModConvJvpDesc(C.Structure):
+    _fields_ = [("m", ModConvDesc), ("vx", _vp), ("vs", _vp), ("y", _vp), ("e", _vp), ("ldy", _i), ("pad_", _i)]
+
+
 class ConvWgradDesc(C.Structure):
     _fields_ = [("dtype", _i), ("N", _i), ("xHs", _i), ("xWs", _i), ("C", _i), ("ldx", _i), ("x_flags", _i), ("gHs", _i), ("gWs", _i),
                 ("Cout", _i), ("ldg", _i), ("g_flags", _i), ("Ho", _i), ("Wo", _i), ("R", _i), ("S", _i), ("stride", _i),
@@ -125,6 +129,9 @@ _PROTOS = {
     "sg_modconv2d_fwd": [C.POINTER(ModConvDesc), _vp],
     "sg_modconv2d_ok": [C.POINTER(ModConvDesc)],
     "sg_modconv_launches": [],                             # returns a count
+    "sg_modconv2d_jvp": [C.POINTER(ModConvJvpDesc), _vp],
+    "sg_modconv2d_jvp_ok": [C.POINTER(ModConvJvpDesc)],
+    "sg_modconv_jvp_launches": [],                         # returns a count
     "sg_modconv_dcoef": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "sg_modconv_reduce_slabs": [_i],                       # returns a count (call through lib(), not call())
     "sg_modconv_reduce": [_i, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -274,6 +281,7 @@ _PROTOS = {
     "sg_filtered_lrelu_launches": [_i],                    # returns a count: 0 forward, 1 gate-writing forward, 2 backward
     "sg_upfirdn2d_launches": [],                           # returns a count
     "sg_fir_bias_act_nhwc": [_i, _vp, _vp, _vp, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp],
+    "sg_fir_bias_act_nhwc_gate": [_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp],
     "sg_fir_bias_act_launches": [],                        # returns a count
     "sg_act_fir_nhwc": [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp],
     "sg_act_fir_nhwc_bwd": [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp],
@@ -337,6 +345,7 @@ def lib():
         l.sg_conv_rs_launches.restype = _ll
         l.sg_sign_plane_launches.restype = _ll
         l.sg_modconv_launches.restype = _ll
+        l.sg_modconv_jvp_launches.restype = _ll
         l.sg_tok_gemm_launches.restype = _ll
         l.sg_mha_launches.restype = _ll
         l.sg_f32_split_launches.restype = _ll

@@ -142,6 +142,30 @@ def stylegan2_r1_args(y):
     return dict(r1_lambda=Ls["r1_lambda"], d_reg_interval=interval, r1_place=Ls["r1_place"], lr=O["d_lr"] * ratio, betas=[O["beta1"] ** ratio, O["beta2"] ** ratio])
 
 
+def stylegan2_pl_args(y):
+    """The lazy path-length regulariser of a `MODEL.backbone: stylegan2` configuration and what its interval does to the generator's Adam (reference
+    src/config.py:311-325, 543-548; src/worker.py:115): dict(apply_pl_reg, pl_weight, g_reg_interval, style_mixing_p, pl_no_weight_grad, lr, betas), lr and
+    betas rescaled by g_ratio = g_reg_interval / (g_reg_interval + 1) (1 at an interval of 1). The companion of stylegan2_r1_args; a configuration that does
+    not regularise (CIFAR10's) still has the interval, the mixing probability and the rescaled optimiser."""
+    M, O, S = dict(y.get("MODEL") or {}), {**_OPT, **dict(y.get("OPTIMIZATION") or {})}, dict(y.get("STYLEGAN") or {})
+    if M.get("backbone") != "stylegan2":      # (no stylegan3 configuration applies the regulariser; its generator has no second-order pass)
+        raise NotImplementedError(f"MODEL.backbone = {M.get('backbone')}: stylegan2_pl_args maps the stylegan2 generator only")
+    interval, mixing = S.get("g_reg_interval", _N), S.get("style_mixing_p", _N)
+    if interval == _N:
+        raise NotImplementedError("STYLEGAN.g_reg_interval must be set for the lazy path-length regulariser")
+    if mixing == _N:
+        raise NotImplementedError("STYLEGAN.style_mixing_p must be set for a stylegan2 generator")
+    apply = bool(S.get("apply_pl_reg", False))
+    weight = S.get("pl_weight", _N)
+    if apply and weight == _N:
+        raise NotImplementedError("STYLEGAN.pl_weight must be set where STYLEGAN.apply_pl_reg is")
+    if O["type_"] != "Adam":
+        raise NotImplementedError(f"OPTIMIZATION.type_ = {O['type_']}: the reference rescales Adam only")
+    ratio = interval / (interval + 1) if interval != 1 else 1
+    return dict(apply_pl_reg=apply, pl_weight=weight, g_reg_interval=interval, style_mixing_p=mixing, pl_no_weight_grad=True, lr=O["g_lr"] * ratio,
+                betas=[O["beta1"] ** ratio, O["beta2"] ** ratio])
+
+
 def model_namespace(y):
     import types
     M = sections(y)[0]

@@ -37,6 +37,14 @@
 // evaluated from the kept raw x exactly as k_act_fir_nhwc_bwd evaluates it (the same expressions in the same order, so the two passes agree on every
 // element). v takes the place of x; x travels through the dy slot of FirArgs and costs one more vector of loads per tap column, issued with v's before the
 // first gate is evaluated. a is piecewise linear: d_x and d_bias are zero. With no gate x is never read and the launch is the plain FIR bit for bit.
+//
+// sg_fir_bias_act_nhwc_gate: the second-order pass of the TAIL (path-length regularisation through the generator). The tail's backward is
+// dx = FIR^T(m * dy) with m the slope / gain / clamp gate evaluated from the kept y: linear in dy, piecewise constant in x. A cotangent (v_x, v_noise,
+// v_bias) on (dx, dnoise, dbias) gives d_dy = m * (FIR(v_x) + v_noise + v_bias): the forward's strip walk on v_x, the fp32 v_noise / v_bias on the
+// accumulator, and at the store the gate read from y -- sg_bias_act's gradient evaluator (style.hip bias_act_eval, MODE 1) restated for linear / lrelu, the
+// same expressions in the same order, so the first-order backward (which runs that evaluator on (dy, y)) and this pass decide every element alike. y travels
+// through the dy slot of FirArgs; its vector is requested before the row's taps are summed. With act linear, gain 1 and no clamp y is never read and the
+// launch is the plain one bit for bit. A separate instantiation (EPI_STORE_GATE): the forward's registers do not change.
 #include "common.h"
 #include "../../include/sgamd.h"
 
@@ -44,8 +52,9 @@ static long long g_fir_launches = 0, g_act_fir_launches = 0;
 extern "C" long long sg_fir_bias_act_launches() { return __atomic_load_n(&g_fir_launches, __ATOMIC_RELAXED); }
 extern "C" long long sg_act_fir_launches() { return __atomic_load_n(&g_act_fir_launches, __ATOMIC_RELAXED); }
 
-enum FirMode { FIR_TAIL, FIR_HEAD, FIR_HEAD_BWD, FIR_HEAD_GATE };      // the four entry points
-enum { EPI_STORE, EPI_LOAD, EPI_LOAD_GATE };            // the side of the forward kernel's epilogue; LOAD_GATE: the second-order pass of the head (below)
+enum FirMode { FIR_TAIL, FIR_HEAD, FIR_HEAD_BWD, FIR_HEAD_GATE, FIR_TAIL_GATE };      // the five entry points
+// the side of the forward kernel's epilogue; LOAD_GATE: the second-order pass of the head, STORE_GATE: the second-order pass of the tail (below)
+enum { EPI_STORE, EPI_LOAD, EPI_LOAD_GATE, EPI_STORE_GATE };
 
 struct FirArgs {
   const void* x; const float* f; void* y; const float* noise; const float* bias; const void* dy;
@@ -109,6 +118,16 @@ __device__ __forceinline__ float fir_gate(float g, float v, const FirArgs& a) {
   return g;
 }
 
+// g * dy/dpre from the kept OUTPUT y of the tail: sg_bias_act's gradient rule (style.hip bias_act_eval<ACT, 1>: the side through y / gain, the gain, zero where
+// the forward output sits at or beyond the clamp)
+__device__ __forceinline__ float fir_gate_out(float g, float y, const FirArgs& a) {
+  const float yy = a.gain != 0.f ? y / a.gain : 0.f;
+  float r = a.act == 3 ? (yy > 0.f ? g : g * a.alpha) : g;
+  r *= a.gain;
+  if (a.clamp >= 0.f) r = (y > -a.clamp && y < a.clamp) ? r : 0.f;
+  return r;
+}
+
 // strip height of the row-walking kernel: as tall as leaves the chip ~half a million threads (the rows a strip re-reads from its neighbour are (fh - 1) / TY
 // of the input); -> workgroups of 256 threads for per_row threads per strip
 static unsigned fir_strip_grid(long long per_row, int Ho, int& TY, int& strips) {
@@ -142,7 +161,7 @@ __global__ __launch_bounds__(256) void k_fir_nhwc(FirArgs a) {
     const int oy0 = strip * a.TY, oy1 = oy0 + a.TY < a.Ho ? oy0 + a.TY : a.Ho;
     const T* xn = (const T*)a.x + (long long)n * a.Hi * a.Wi * a.C + c0;
     T* yn = (T*)a.y + (long long)n * a.Ho * a.Wo * a.C + c0;
-    const float* nz = SIDE == EPI_STORE && a.noise ? a.noise + (long long)n * a.noise_stride : nullptr;
+    const float* nz = (SIDE == EPI_STORE || SIDE == EPI_STORE_GATE) && a.noise ? a.noise + (long long)n * a.noise_stride : nullptr;
     float bv[V];
 #pragma unroll
     for (int e = 0; e < V; e++) bv[e] = a.bias ? a.bias[c0 + e] : 0.f;
@@ -154,6 +173,15 @@ __global__ __launch_bounds__(256) void k_fir_nhwc(FirArgs a) {
     const int ix0 = ox * DOWN - px;
     // (loading a row ahead of the one being summed was measured and lost: +16 / +32 VGPRs, 3187 against 4327 GB/s in fp32 at 128 x 256^2, no change in bf16)
     for (int p = oy0; p <= oy1 + NACC - 2; p++) {
+      float yk[V];      // EPI_STORE_GATE: the kept output at the element this iteration stores, in flight while the row's taps are summed
+      if constexpr (SIDE == EPI_STORE_GATE) {
+        const int oyk = p - (NACC - 1);
+        if (a.gate && oyk >= oy0) load_f<T, V>((const T*)a.dy + (long long)n * a.Ho * a.Wo * a.C + c0 + ((long long)oyk * a.Wo + ox) * a.C, yk);
+        else {
+#pragma unroll
+          for (int e = 0; e < V; e++) yk[e] = 0.f;
+        }
+      }
 #pragma unroll
       for (int s = 0; s < DOWN; s++) {
         const int iy = p * DOWN + s - py;
@@ -226,6 +254,16 @@ __global__ __launch_bounds__(256) void k_fir_nhwc(FirArgs a) {
             if (nz) v += nv;
             if (a.bias) v += bv[e];
             o[e] = fir_act<FirArgs>(v, a);
+          }
+        }
+        if constexpr (SIDE == EPI_STORE_GATE) {
+          const float nv = nz ? nz[(long long)oy * a.Wo + ox] : 0.f;
+#pragma unroll
+          for (int e = 0; e < V; e++) {
+            float v = o[e];
+            if (nz) v += nv;
+            if (a.bias) v += bv[e];
+            o[e] = a.gate ? fir_gate_out(v, yk[e], a) : v;
           }
         }
         *(vec_t<T, V>*)(yn + ((long long)oy * a.Wo + ox) * a.C) = pack_f<T, V>(o);
@@ -302,7 +340,10 @@ template <typename T, int V, int DOWN> static void fir_launch_v(const FirArgs& a
   if (mode == FIR_HEAD_BWD) hipLaunchKernelGGL((k_act_fir_nhwc_bwd<T, V, DOWN>), dim3(blocks), dim3(256), 0, st, a);
   else if (mode == FIR_HEAD_GATE) hipLaunchKernelGGL((k_fir_nhwc<T, V, DOWN, EPI_LOAD_GATE>), dim3(blocks), dim3(256), 0, st, a);
   else if (mode == FIR_HEAD) hipLaunchKernelGGL((k_fir_nhwc<T, V, DOWN, EPI_LOAD>), dim3(blocks), dim3(256), 0, st, a);
-  else if constexpr (DOWN == 1) hipLaunchKernelGGL((k_fir_nhwc<T, V, 1, EPI_STORE>), dim3(blocks), dim3(256), 0, st, a);      // (the tail has no down = 2)
+  else if constexpr (DOWN == 1) {      // (the tail has no down = 2)
+    if (mode == FIR_TAIL_GATE) hipLaunchKernelGGL((k_fir_nhwc<T, V, 1, EPI_STORE_GATE>), dim3(blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_fir_nhwc<T, V, 1, EPI_STORE>), dim3(blocks), dim3(256), 0, st, a);
+  }
 }
 
 // 16-byte vectors along C where the channels fill them and every tensor is aligned, one channel per thread otherwise; strips for the forward kernels
@@ -340,8 +381,10 @@ static int fir_run(const char* who, FirMode mode, int dtype, const void* x, cons
   const long long Ho = Hp / down + 1, Wo = Wp / down + 1;
   FIR_CHECK(Ho < (1 << 24) && Wo < (1 << 24), "image extent or padding too large");
   FIR_CHECK(!noise || noise_stride == 0 || noise_stride >= Ho * Wo, "noise_stride must be 0 (one shared plane) or >= Ho * Wo");
-  const bool gate = bias || act != 1 || gain != 1.f || clamp >= 0.f;
-  FIR_CHECK(mode == FIR_HEAD_BWD ? (dy && (x || !gate)) : mode == FIR_HEAD_GATE ? (x && (dy || !gate)) : x != nullptr, "bad tensor arguments");
+  // (the tail's gate is read from y, which carries the bias already: v_bias is a cotangent there and opens no gate)
+  const bool gate = (bias && mode != FIR_TAIL_GATE) || act != 1 || gain != 1.f || clamp >= 0.f;
+  FIR_CHECK(mode == FIR_HEAD_BWD ? (dy && (x || !gate)) : (mode == FIR_HEAD_GATE || mode == FIR_TAIL_GATE) ? (x && (dy || !gate)) : x != nullptr,
+            "bad tensor arguments");
 #undef FIR_CHECK
   FirArgs a;
   a.x = x; a.f = f; a.y = out; a.noise = noise; a.bias = bias; a.dy = dy; a.noise_stride = noise ? noise_stride : 0;
@@ -355,7 +398,7 @@ static int fir_run(const char* who, FirMode mode, int dtype, const void* x, cons
   if (dtype == SG_DTYPE_F32) { if (down == 1) fir_launch<float, 1>(a, mode, st); else fir_launch<float, 2>(a, mode, st); }
   else { if (down == 1) fir_launch<bf16_t, 1>(a, mode, st); else fir_launch<bf16_t, 2>(a, mode, st); }
   SG_LAUNCH_CHECK();
-  __atomic_fetch_add(mode == FIR_TAIL ? &g_fir_launches : &g_act_fir_launches, 1, __ATOMIC_RELAXED);
+  __atomic_fetch_add((mode == FIR_TAIL || mode == FIR_TAIL_GATE) ? &g_fir_launches : &g_act_fir_launches, 1, __ATOMIC_RELAXED);
   return 0;
 }
 
@@ -385,4 +428,11 @@ extern "C" int sg_act_fir_nhwc_gate(int dtype, const void* v, const void* x, con
                                     float gain, float clamp, sg_stream_t s) {
   return fir_run("sg_act_fir_nhwc_gate", FIR_HEAD_GATE, dtype, v, x, f, y, nullptr, 0, bias, N, Hi, Wi, C, fh, fw, down, padx0, padx1, pady0, pady1, flip_filter,
                  filter_gain, act, alpha, gain, clamp, (hipStream_t)s);
+}
+
+extern "C" int sg_fir_bias_act_nhwc_gate(int dtype, const void* v, const void* y, const float* f, void* out, const float* v_noise, long long noise_stride,
+                                         const float* v_bias, int N, int Hi, int Wi, int C, int fh, int fw, int padx0, int padx1, int pady0, int pady1,
+                                         int flip_filter, float filter_gain, int act, float alpha, float gain, float clamp, sg_stream_t s) {
+  return fir_run("sg_fir_bias_act_nhwc_gate", FIR_TAIL_GATE, dtype, v, y, f, out, v_noise, noise_stride, v_bias, N, Hi, Wi, C, fh, fw, 1, padx0, padx1, pady0,
+                 pady1, flip_filter, filter_gain, act, alpha, gain, clamp, (hipStream_t)s);
 }

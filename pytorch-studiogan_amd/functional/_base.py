@@ -13,32 +13,49 @@ from ..bank import ensure_grad
 # keeps raising, so that a caller who did not ask for the heavier graph (kept cotangents, grad-functions instead of in-place launches) never gets it silently.
 _SECOND_ORDER = [0]                 # nesting depth of second_order(); process-wide
 _SECOND_ORDER_LIFTS = ("act_fir", "conv2d_resample", "minibatch_std")
+# The StyleGAN2 generator's operators (path-length regularisation) have an opt-in of their own, second_order(generator=True): a plain second_order() -- R1
+# through the discriminator -- keeps refusing them, so that neither caller gets the other's heavier graph.
+_SECOND_ORDER_GEN = [0]             # nesting depth of second_order(generator=True); process-wide
+_SECOND_ORDER_GEN_LIFTS = ("modulated_conv2d", "fir_bias_act")
 
 
 class second_order:
     """with style_ops.second_order(): torch.autograd.grad(..., create_graph=True) through act_fir, conv2d_plain / conv2d_resample and minibatch_std records a
     differentiable backward (the reference wraps the same call of its R1 regulariser in conv2d_gradfix.no_weight_gradients()). The graph recorded inside stays
-    valid outside: penalty.backward() needs no context. Process-wide, re-entrant, restored on exit; every other first-order operator keeps refusing."""
+    valid outside: penalty.backward() needs no context. Process-wide, re-entrant, restored on exit; every other first-order operator keeps refusing.
+    second_order(generator=True) additionally lifts modulated_conv2d and fir_bias_act (path-length regularisation through the StyleGAN2 generator); it keeps
+    a depth counter of its own, and a plain second_order() inside or outside it lifts what it always did."""
+
+    def __init__(self, generator=False):
+        self.generator = bool(generator)
 
     def __enter__(self):
         _SECOND_ORDER[0] += 1
+        if self.generator:
+            _SECOND_ORDER_GEN[0] += 1
         return self
 
     def __exit__(self, *exc):
         _SECOND_ORDER[0] -= 1
+        if self.generator:
+            _SECOND_ORDER_GEN[0] -= 1
         return False
 
 
 def _first_order_only(name):
     """Functions without a differentiable backward refuse create_graph=True instead of silently cutting the graph. Returns True where the caller has a
-    differentiable route and is to take it (one of _SECOND_ORDER_LIFTS inside second_order()), False when no graph is being recorded."""
+    differentiable route and is to take it (one of _SECOND_ORDER_LIFTS inside second_order(), one of _SECOND_ORDER_GEN_LIFTS inside
+    second_order(generator=True)), False when no graph is being recorded."""
     if torch.is_grad_enabled():
         if _SECOND_ORDER[0] > 0 and name in _SECOND_ORDER_LIFTS:
+            return True
+        if _SECOND_ORDER_GEN[0] > 0 and name in _SECOND_ORDER_GEN_LIFTS:
             return True
         raise NotImplementedError(name + ": no differentiable backward (create_graph=True). Second-order passes exist for the discriminator's conv / BN / pooling / "
                                          "self-attention / head path (gradient penalties, R1) and for the ResNet / BigGAN / BigGAN-Deep generators incl. conditional "
                                          "batch norm (latent optimisation); not for third order, nor for the DCGAN generator's transposed convolutions. The "
-                                         "StyleGAN2 discriminator's operators (" + ", ".join(_SECOND_ORDER_LIFTS) + ") record theirs inside style_ops.second_order()")
+                                         "StyleGAN2 discriminator's operators (" + ", ".join(_SECOND_ORDER_LIFTS) + ") record theirs inside style_ops.second_order(), "
+                                         "the StyleGAN2 generator's (" + ", ".join(_SECOND_ORDER_GEN_LIFTS) + ") inside style_ops.second_order(generator=True)")
     return False
 
 

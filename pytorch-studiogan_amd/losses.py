@@ -1,5 +1,7 @@
 """Adversarial losses with the reference's names and call signature (reference src/utils/losses.py:197-239,
 wired by src/config.py:411-433 as cfgs.LOSS.{d_loss,g_loss}); forward + gradient in one small kernel each."""
+import math
+
 import torch
 import torch.distributed as dist
 from torch import autograd
@@ -232,6 +234,68 @@ def stylegan_d_reg_step(discriminator, real_images, real_labels, r1_lambda, d_re
     penalty = penalty * (d_reg_interval * r1_lambda / acml_steps)
     penalty.backward()
     return penalty.detach()
+
+
+class PathLengthRegularizer:
+    """Path-length regularisation of the StyleGAN2 generator, reference src/utils/losses.py:168-186: the penalty on the deviation of
+    ||d <images, pl_noise> / d ws|| from its running mean `pl_mean` (a 0-d tensor on `device`, updated by every call).
+
+    The first pass (the gradient for ws, create_graph=True) runs inside style_ops.second_order(generator=True), where modulated_conv2d and fir_bias_act record a
+    differentiable backward; the penalty's own backward() needs no context. pl_no_weight_grad is the reference's conv2d_gradfix.no_weight_gradients switch:
+    here the first pass asks for the latents' gradient alone and the operators launch no weight gradient for it either way, so the flag is kept for the
+    interface and changes nothing."""
+
+    def __init__(self, device, pl_decay=0.01, pl_weight=2, pl_no_weight_grad=False):
+        self.pl_decay = pl_decay
+        self.pl_weight = pl_weight
+        self.pl_mean = torch.zeros([], device=device)
+        self.pl_no_weight_grad = pl_no_weight_grad
+
+    def cal_pl_reg(self, fake_images, ws, pl_noise=None):
+        """fake_images: the synthesis network's output for `ws` ([N, num_ws, w_dim], part of its graph). pl_noise: None draws N(0, 1) / sqrt(H * W) in the
+        images' shape and dtype, as the reference does; a tensor is used as given."""
+        from .style_ops import second_order
+        if pl_noise is None:
+            pl_noise = torch.randn_like(fake_images) / math.sqrt(fake_images.shape[2] * fake_images.shape[3])
+        with second_order(generator=True):
+            pl_grads = autograd.grad(outputs=[(fake_images * pl_noise).sum()], inputs=[ws], create_graph=True, only_inputs=True)[0]
+        pl_lengths = pl_grads.square().sum(2).mean(1).sqrt()
+        pl_mean = self.pl_mean.lerp(pl_lengths.mean(), self.pl_decay)
+        self.pl_mean.copy_(pl_mean.detach())
+        pl_penalty = (pl_lengths - pl_mean).square()
+        return (pl_penalty * self.pl_weight).mean(0)
+
+
+def stylegan_generate_images(zs, fake_labels, num_classes, style_mixing_p, update_emas, generator_mapping, generator_synthesis, truncation_psi,
+                             truncation_cutoff):
+    """reference src/utils/sample.py:180-192: ws = mapping(zs, one_hot(labels)); with probability style_mixing_p the layers from a random cutoff on take the
+    latents of a second, freshly drawn z (cutoff and coin drawn on the device, no host synchronisation); images = synthesis(ws). truncation_psi == -1 means
+    no truncation (psi 1, the cutoff ignored). Host code only. -> (ws, fake_images)"""
+    one_hot = torch.nn.functional.one_hot(fake_labels, num_classes=num_classes) if num_classes > 0 else None      # (an unconditional mapping reads no label)
+    if truncation_psi == -1:
+        ws = generator_mapping(zs, one_hot, truncation_psi=1, update_emas=update_emas)
+    else:
+        ws = generator_mapping(zs, one_hot, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff, update_emas=update_emas)
+    if style_mixing_p > 0:
+        cutoff = torch.empty([], dtype=torch.int64, device=ws.device).random_(1, ws.shape[1])
+        cutoff = torch.where(torch.rand([], device=ws.device) < style_mixing_p, cutoff, torch.full_like(cutoff, ws.shape[1]))
+        ws[:, cutoff:] = generator_mapping(torch.randn_like(zs), one_hot, update_emas=False)[:, cutoff:]
+    fake_images = generator_synthesis(ws, update_emas=update_emas)
+    return ws, fake_images
+
+
+def stylegan_g_reg_step(generator, zs, labels, pl_reg, g_reg_interval, acml_steps=1, style_mixing_p=0.0, pl_noise=None, **synthesis_kwargs):
+    """One accumulation step of the lazy path-length regulariser (reference src/worker.py:636-671 for a stylegan2 generator): mapping -> optional style mixing
+    -> synthesis on `zs` (the worker draws batch_size // 2 of them), pl_reg.cal_pl_reg, + fake_images[:, 0, 0, 0].mean() * 0 (every output of the network in
+    the loss), x g_reg_interval / acml_steps, backward into the parameters' .grad (the caller zeroes them before and steps the optimiser after).
+    generator: backbones.stylegan2.Generator (.mapping, .synthesis, .c_dim); synthesis_kwargs go to its synthesis network (noise_mode='const' in the tests).
+    Returns the detached scaled loss."""
+    synthesis = (lambda ws, **kw: generator.synthesis(ws, **kw, **synthesis_kwargs)) if synthesis_kwargs else generator.synthesis
+    ws, fake_images = stylegan_generate_images(zs, labels, generator.c_dim, style_mixing_p, False, generator.mapping, synthesis, -1.0, None)
+    loss = pl_reg.cal_pl_reg(fake_images=fake_images, ws=ws, pl_noise=pl_noise) + fake_images[:, 0, 0, 0].mean() * 0
+    loss = loss * (g_reg_interval / acml_steps)
+    loss.backward()
+    return loss.detach()
 
 
 def l2_loss(a, b):

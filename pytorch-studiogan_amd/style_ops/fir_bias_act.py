@@ -9,7 +9,9 @@ accumulator; the only rounding is the store. act: 'linear' or 'lrelu'.
 Gradients (first order; y is kept, as bias_act keeps it):
     dpre   = sg_bias_act's gradient evaluator on (dy, y): gain * act'(.) dy, zero where the forward clamped
     dbias  = sum_{n,p} dpre,   dnoise = sum_c dpre (summed over n as well for a shared plane)
-    dx     = the same kernel in plain mode on dpre: filter flipped, the adjoint padding (upfirdn2d.py derives it)"""
+    dx     = the same kernel in plain mode on dpre: filter flipped, the adjoint padding (upfirdn2d.py derives it)
+Second order, inside style_ops.second_order(generator=True): all three are linear in dy, so cotangents (v_x, v_noise, v_bias) give
+    d_dy   = m (FIR(v_x) + v_noise + v_bias), m the gate of the kept y          (one sg_fir_bias_act_nhwc_gate launch; nothing flows to x, noise or bias)"""
 import torch
 
 from .. import _lib as L
@@ -46,30 +48,77 @@ class FirBiasActFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        _first_order_only("fir_bias_act")
+        differentiable = _first_order_only("fir_bias_act")
+        f2d, y = ctx.saved_tensors
+        needs = (ctx.needs_input_grad[0], ctx.cfg[8] is not None and ctx.needs_input_grad[2], ctx.cfg[9] is not None and ctx.needs_input_grad[3])
+        if differentiable:      # inside second_order(generator=True): the same launches, recorded as a grad-function with a backward of its own
+            dx, dn, db = _FirBiasActGradFn.apply(dy, f2d, y, ctx.cfg, needs)
+        else:
+            dx, dn, db = _first_order(dy, f2d, y, ctx.cfg, needs)
+        return dx, None, dn, db, None, None, None, None, None, None, None
+
+
+def _first_order(dy, f2d, y, cfg, needs):
+    """the tail's first-order backward: (dx, dnoise, dbias), each None where needs says so"""
+    (N, Hi, Wi, C), pad, flip_filter, filter_gain, act, alpha, gain, clamp, noise_info, bias_dtype = cfg
+    _, Ho, Wo, _ = y.shape
+    dpre = dy.to(y.dtype).permute(0, 2, 3, 1).contiguous()
+    if act != "linear" or gain != 1 or clamp >= 0:
+        out = torch.empty_like(dpre)
+        L.call("sg_bias_act", L.dt(dpre), L.ptr(dpre), None, None, L.ptr(y), None, L.ptr(out), dpre.numel(), 1, 1, 1, activation_funcs[act].cuda_idx,
+               float(alpha), float(gain), float(clamp), L.stream())
+        dpre = out
+    dx = dn = db = None
+    if needs[0]:
+        fh, fw = int(f2d.shape[0]), int(f2d.shape[1])
+        px0, _, py0, _ = pad
+        adj = (fw - px0 - 1, Wi - Wo + px0, fh - py0 - 1, Hi - Ho + py0)
+        dx = fir_nhwc_raw(dpre, f2d, adj, not flip_filter, filter_gain).permute(0, 3, 1, 2)
+    if needs[1]:
+        rows = torch.empty((N, Ho * Wo), dtype=torch.float32, device=dpre.device)
+        L.call("sg_modconv_reduce", L.dt(dpre), L.ptr(dpre), None, None, 0, None, None, None, L.ptr(rows), N, Ho * Wo, C, C, C, L.stream())
+        dn = rows.reshape(N, 1, Ho, Wo) if len(noise_info[1]) == 4 else rows.sum(dim=0).reshape(Ho, Wo)
+        dn = dn.to(noise_info[0])
+    if needs[2]:
+        db = dpre.sum(dim=(0, 1, 2), dtype=torch.float32).to(bias_dtype)
+    return dx, dn, db
+
+
+def fir_gate_raw(vh, y, f2d, pad, flip_filter=False, filter_gain=1.0, v_noise=None, noise_stride=0, v_bias=None, act="linear", alpha=0.0, gain=1.0, clamp=-1.0):
+    """one sg_fir_bias_act_nhwc_gate launch: m(y) * (FIR(vh) + v_noise + v_bias), the forward's filter and padding; vh [N, Hi, Wi, C], y [N, Ho, Wo, C]"""
+    out, (N, Hi, Wi, C, fh, fw) = nhwc_out("fir_bias_act", vh, f2d, pad)
+    assert tuple(out.shape) == tuple(y.shape) and y.dtype == vh.dtype and y.is_contiguous()
+    if out.numel():
+        L.call("sg_fir_bias_act_nhwc_gate", L.dt(vh), L.ptr(vh), L.ptr(y), L.ptr(f2d), L.ptr(out), L.ptr(v_noise), noise_stride, L.ptr(v_bias), N, Hi, Wi, C, fh, fw,
+               *epilogue_args(pad, flip_filter, filter_gain, act, alpha, gain, clamp))
+    return out
+
+
+class _FirBiasActGradFn(torch.autograd.Function):
+    """The tail's first-order backward as a differentiable function of dy. dx = FIR^T(m dy), dnoise = sum_c m dy, dbias = sum_{n,p} m dy with m the slope /
+    gain / clamp gate of the kept y: linear in dy, piecewise constant in x, noise and bias. Cotangents (v_x, v_noise, v_bias) give
+    d_dy = m (FIR(v_x) + v_noise + v_bias) in one sg_fir_bias_act_nhwc_gate launch; nothing flows anywhere else."""
+
+    @staticmethod
+    def forward(ctx, dy, f2d, y, cfg, needs):
+        ctx.save_for_backward(f2d, y)
+        ctx.cfg, ctx.dy_dtype = cfg, dy.dtype
+        ctx.set_materialize_grads(False)
+        return _first_order(dy, f2d, y, cfg, needs)
+
+    @staticmethod
+    def backward(ctx, vx, vn, vb):
+        _first_order_only("fir_bias_act (third order)")
         f2d, y = ctx.saved_tensors
         (N, Hi, Wi, C), pad, flip_filter, filter_gain, act, alpha, gain, clamp, noise_info, bias_dtype = ctx.cfg
-        _, Ho, Wo, _ = y.shape
-        dpre = dy.to(y.dtype).permute(0, 2, 3, 1).contiguous()
-        if act != "linear" or gain != 1 or clamp >= 0:
-            out = torch.empty_like(dpre)
-            L.call("sg_bias_act", L.dt(dpre), L.ptr(dpre), None, None, L.ptr(y), None, L.ptr(out), dpre.numel(), 1, 1, 1, activation_funcs[act].cuda_idx,
-                   float(alpha), float(gain), float(clamp), L.stream())
-            dpre = out
-        dx = dn = db = None
-        if ctx.needs_input_grad[0]:
-            fh, fw = int(f2d.shape[0]), int(f2d.shape[1])
-            px0, _, py0, _ = pad
-            adj = (fw - px0 - 1, Wi - Wo + px0, fh - py0 - 1, Hi - Ho + py0)
-            dx = fir_nhwc_raw(dpre, f2d, adj, not flip_filter, filter_gain).permute(0, 3, 1, 2)
-        if noise_info is not None and ctx.needs_input_grad[2]:
-            rows = torch.empty((N, Ho * Wo), dtype=torch.float32, device=dpre.device)
-            L.call("sg_modconv_reduce", L.dt(dpre), L.ptr(dpre), None, None, 0, None, None, None, L.ptr(rows), N, Ho * Wo, C, C, C, L.stream())
-            dn = rows.reshape(N, 1, Ho, Wo) if len(noise_info[1]) == 4 else rows.sum(dim=0).reshape(Ho, Wo)
-            dn = dn.to(noise_info[0])
-        if bias_dtype is not None and ctx.needs_input_grad[3]:
-            db = dpre.sum(dim=(0, 1, 2), dtype=torch.float32).to(bias_dtype)
-        return dx, None, dn, db, None, None, None, None, None, None, None
+        vh = torch.zeros((N, Hi, Wi, C), dtype=y.dtype, device=y.device) if vx is None else vx.to(y.dtype).permute(0, 2, 3, 1).contiguous()
+        vn32, nstride = None, 0
+        if vn is not None:
+            vn32 = vn.to(torch.float32).contiguous()
+            nstride = vn32.shape[-2] * vn32.shape[-1] if vn32.dim() == 4 else 0
+        vb32 = None if vb is None else vb.to(torch.float32).contiguous()
+        d_dy = fir_gate_raw(vh, y, f2d, pad, flip_filter, filter_gain, vn32, nstride, vb32, act, alpha, gain, clamp)
+        return d_dy.permute(0, 3, 1, 2).to(ctx.dy_dtype), None, None, None, None
 
 
 def fir_bias_act(x, f, padding, noise=None, bias=None, act="linear", alpha=None, gain=None, clamp=None, flip_filter=False, filter_gain=1.0):

@@ -20,7 +20,7 @@ materialised s x and gu; the two demodulation terms are [N x Cout]^T [N x C]-siz
 import torch
 
 from .. import _lib as L
-from ..functional._base import _first_order_only, conv2d_wgrad_raw
+from ..functional._base import _first_order_only, _param_grad_wanted, conv2d_wgrad_raw
 from . import upfirdn2d as _upfirdn2d
 
 
@@ -127,63 +127,211 @@ class _ModConvFn(torch.autograd.Function):
             g = post_gain.detach().to(torch.float32).reshape(1, 1)
             post = dco * g if demodulate else g.expand(N, Cout).contiguous()
         y = _modconv_raw(xh, wimg, Cout, k, "same" if up == 1 else "up2", pre=s32, post=post, noise=nz, noise_stride=nstride)
-        ctx.save_for_backward(xh, w32, s32, Q, dco, y, nz, post)
+        ctx.save_for_backward(xh, w32, s32, Q, dco, y, nz, post, x, weight, styles)     # (the last three: the graph's own tensors, for the second-order route)
         ctx.cfg = (up, demodulate, flipped, k, weight.dtype, styles.dtype, None if noise is None else (noise.dtype, tuple(noise.shape)))
         return y.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, gy):
-        _first_order_only("modulated_conv2d")
-        xh, w32, s32, Q, dco, y, nz, post = ctx.saved_tensors       # post = g d (dco when there is no post_gain): what scales gy; d alone stays in gd d^3
+        differentiable = _first_order_only("modulated_conv2d")
+        saved, (x, weight, styles) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        need_noise = saved[6] is not None and ctx.needs_input_grad[3]
+        if differentiable:
+            # inside second_order(generator=True): the same launches, recorded as a grad-function with a backward of its own. The weight gradient only where
+            # the running graph task wants it (path-length regularisation asks for the latents' alone, as the reference's no_weight_gradients does).
+            want_w = ctx.needs_input_grad[1] and _param_grad_wanted(weight)
+            dx, dw, ds, dn = _ModConvGradFn.apply(gy, x, weight, styles, ctx.cfg, want_w, need_noise, *saved)
+            return dx, dw, ds, dn, None, None, None, None
+        dx, dw, ds, dn, _ = _first_order(saved, ctx.cfg, gy, ctx.needs_input_grad[1], need_noise)
+        return dx, dw, ds, dn, None, None, None, None
+
+
+def _data_grad(gyh, weff, pre, up, k, C, T):
+    """K^T[pre * gy]: the unscaled data gradient through the same kernel (pre rides on gy as its pre-scale: fp32 product, one rounding)"""
+    if up == 1:
+        wd = weff.flip(2, 3).permute(1, 2, 3, 0).contiguous().to(T)          # [C][2-r][2-s][Cout]
+        return _modconv_raw(gyh, wd, C, k, "same", pre=pre)
+    wd = weff.permute(1, 2, 3, 0).contiguous().to(T)                         # [C][r][s][Cout]: gxs[h,w] = sum gu[2h+r, 2w+s] W[r,s]
+    return _modconv_raw(gyh, wd, C, k, "down2", pre=pre)
+
+
+def _wgrad_into(dwi, operand, gu, up, k, C, Cout, H, W):
+    """dwi += wgrad(operand, gu); dwi is [Cout, k, k, C] at up = 1 and [C, k, k, Cout] at up = 2, where the roles swap (the stride-2 convolution gu -> gxs
+    has the weight image [C][r][s][Cout])"""
+    if up == 1:
+        conv2d_wgrad_raw(operand, gu, L.ptr(dwi), C, Cout, k, k, H, W, 1, k // 2, k // 2)
+    else:
+        conv2d_wgrad_raw(gu, operand, L.ptr(dwi), Cout, C, k, k, H, W, 2, 0, 0)
+
+
+def _wgrad_image(up, k, C, Cout, device):
+    return torch.zeros((Cout, k, k, C) if up == 1 else (C, k, k, Cout), dtype=torch.float32, device=device)
+
+
+def _wgrad_as_weight(dwi, up, flipped):
+    dw = dwi.permute(0, 3, 1, 2) if up == 1 else dwi.permute(3, 0, 1, 2)
+    return dw.flip(2, 3) if flipped else dw
+
+
+def _first_order(saved, cfg, gy, need_w, need_noise):
+    """the operator's first-order backward: (dx NCHW view, dw, ds, dnoise, what a second-order pass keeps)"""
+    xh, w32, s32, Q, dco, y, nz, post = saved       # post = g d (dco when there is no post_gain): what scales gy; d alone stays in gd d^3
+    up, demodulate, flipped, k, w_dtype, s_dtype, noise_info = cfg
+    N, H, W, C = xh.shape
+    Cout = w32.shape[0]
+    T = xh.dtype
+    gyh = gy.to(T).permute(0, 2, 3, 1).contiguous()
+    weff = w32.flip(2, 3) if flipped else w32
+    # gu = d gy, d gd = sum_p gy (y - noise), dnoise = sum_o gy: one pass over gy and y
+    gu, dgd, gnoise = gyh, None, None
+    if demodulate:
+        gu, dgd, gnoise = _reduce_raw(gyh, b=y, rowsub=nz, rowsub_stride=(H * W if (nz is not None and nz.dim() == 4) else 0), scale=post,
+                                      want_rowsum=need_noise)
+    elif post is not None:
+        gu, _, gnoise = _reduce_raw(gyh, scale=post, want_rowsum=need_noise)
+    elif need_noise:
+        _, _, gnoise = _reduce_raw(gyh, want_rowsum=True)
+    # unscaled data gradient through the same kernel (d rides on gy as its pre-scale: fp32 product, one rounding), then dx = s gxs, sum_p x gxs
+    gxs = _data_grad(gyh, weff, post, up, k, C, T)
+    dx, ds, _ = _reduce_raw(gxs, b=xh, scale=s32)
+    t = None
+    if demodulate:
+        t = dgd * dco * dco                                                  # gd d^3
+        ds = ds - s32 * (t @ Q)
+    dw = None
+    if need_w:
+        xs, _, _ = _reduce_raw(xh, scale=s32)                                # s x, materialised for the weight-gradient kernel
+        dwi = _wgrad_image(up, k, C, Cout, xh.device)
+        _wgrad_into(dwi, xs, gu, up, k, C, Cout, H, W)
+        dw = _wgrad_as_weight(dwi, up, flipped)
+        if demodulate:
+            dw = dw - w32 * (t.t() @ (s32 * s32))[:, :, None, None]
+        dw = dw.to(w_dtype)
+    dn = None
+    if need_noise:
+        dn = gnoise.reshape(N, 1, H, W) if len(noise_info[1]) == 4 else gnoise.sum(dim=0).reshape(H, W)
+        dn = dn.to(noise_info[0])
+    return dx.permute(0, 3, 1, 2), dw, ds.to(s_dtype), dn, (gyh, gu, dgd, gxs)
+
+
+def _jvp_raw(xh, vxh, wimg, Cout, k, mode, s32, vs32, post, y, e, noise, noise_stride):
+    """one sg_modconv2d_jvp launch: post * K(W)[s vx + vs x] + e (y - noise), the forward's tangent along (vx, vs); geometry as _modconv_raw"""
+    N, Hs, Ws, C = xh.shape
+    j = L.ModConvJvpDesc()
+    c = j.m.conv
+    c.dtype = L.dt(xh)
+    c.N, c.Hs, c.Ws, c.C, c.ldx = N, Hs, Ws, C, C
+    c.R = c.S = k
+    if mode == "same":
+        Ho, Wo, c.stride, c.pad_h, c.pad_w, c.pix_flags = Hs, Ws, 1, k // 2, k // 2, 0
+    else:
+        Ho, Wo, c.stride, c.pad_h, c.pad_w, c.pix_flags = 2 * Hs + 1, 2 * Ws + 1, 2, 0, 0, L.PIX_TRANSPOSED
+    c.Ho, c.Wo, c.Cout = Ho, Wo, Cout
+    c.epi_flags, c.alpha, c.beta = 0, 1.0, 1.0
+    out = torch.empty((N, Ho, Wo, Cout), dtype=xh.dtype, device=xh.device)
+    c.x, c.w, c.out, c.ldo = L.ptr(xh), L.ptr(wimg), L.ptr(out), Cout
+    j.m.pre, j.m.post, j.m.noise, j.m.noise_stride = L.ptr(s32), L.ptr(post), L.ptr(noise), noise_stride
+    j.vx, j.vs, j.y, j.e, j.ldy = L.ptr(vxh), L.ptr(vs32), L.ptr(y), L.ptr(e), Cout
+    if L.lib().sg_modconv2d_jvp_ok(L.C.byref(j)) != 1:
+        raise RuntimeError("modulated_conv2d: sg_modconv2d_jvp_ok refused the problem (there is no other path)")
+    L.call("sg_modconv2d_jvp", j, L.stream())
+    return out
+
+
+# Which route the tangent d_gy takes. One sg_modconv2d_jvp launch where it does not lose to the composition it replaces (operand combine, sg_modconv2d_fwd,
+# multiply-add with y), measured at the layer shapes of a 256^2 network, batch 16 (profiles/stylegan2_pl_bench.txt): fp32 at up = 1 it wins 1.04-1.22x; at
+# up = 2 it loses (0.94x), and in bf16 it loses at every shape (0.44-0.92x: the second operand chunk costs the kernel a wave of occupancy and its unpacking
+# doubles the vector work of a loop the forward already spends on the styles). Those keep the composition.
+TANGENT_ROUTE = [None]      # None: by the rule; "fused" / "composition": forced (tests and tools/stylegan2_pl_bench.py run both everywhere)
+
+
+def tangent_fused(dtype, up):
+    if TANGENT_ROUTE[0] is not None:
+        return TANGENT_ROUTE[0] == "fused"
+    return dtype == torch.float32 and up == 1
+
+
+class _ModConvGradFn(torch.autograd.Function):
+    """The first-order backward of _ModConvFn as a differentiable function of (gy, x, weight, styles): what path-length regularisation differentiates.
+
+    With cotangents vx on dx and vs on ds, Psi = <vx, dx> + <vs, ds> = <gy, y'>, y' the forward-mode tangent of y along (x', s') = (vx, vs):
+        d_gy = y' = g d K(W)[s vx + vs x] + e (y - noise),     e = -d^2 r,  r = (s vs) Q^T          (one sg_modconv2d_jvp launch, or the composition: tangent_fused)
+    and Psi = g sum_o ( d a + d' b ) with d' = d e, a = sum_p gy K[s vx + vs x], b = sum_p gy K[s x]. Its other gradients, with
+    alpha = g d a = sum_p gy y' - e beta and beta = g d b = sum_p gy (y - noise) (kept from the first pass), so that nothing is divided by d or a style:
+        d_x = vs G + s G',          G = K^T[g d gy] (kept),  G' = K^T[g d' gy]                                      (the data-gradient route once more)
+        d_s = sum_p vx G + sum_p x G' + s (T1 Q) - vs (T2 Q),     T1 = -alpha d^2 + 3 beta d^4 r,  T2 = beta d^2        (dd'/ds = 3 d^5 s Q r - d^3 vs Q)
+        d_W = wgrad(s vx + vs x, g d gy) + wgrad(s x, g d' gy) + W ( T1^T s^2 - 2 T2^T (s vs) )
+    Without demodulation e = d' = 0 and only the first term of each is left. A cotangent on dW or dnoise is not a path of the reference and is refused."""
+
+    @staticmethod
+    def forward(ctx, gy, x, weight, styles, cfg, want_w, want_noise, *saved):
+        dx, dw, ds, dn, (gyh, gu, dgd, gxs) = _first_order(saved, cfg, gy, want_w, want_noise)
+        ctx.save_for_backward(*saved, gyh, gu, dgd, gxs)
+        ctx.cfg, ctx.gy_dtype, ctx.x_dtype = cfg, gy.dtype, x.dtype
+        ctx.set_materialize_grads(False)
+        return dx, dw, ds, dn
+
+    @staticmethod
+    def backward(ctx, vx, vw, vs, vn):
+        _first_order_only("modulated_conv2d (third order)")
+        if vw is not None or vn is not None:
+            raise NotImplementedError("modulated_conv2d: a second-order pass with a cotangent on the weight's or the noise's gradient is not supported "
+                                      "(path-length regularisation differentiates the gradient for the latents alone)")
+        xh, w32, s32, Q, dco, y, nz, post, gyh, gu, dgd, gxs = ctx.saved_tensors
         up, demodulate, flipped, k, w_dtype, s_dtype, noise_info = ctx.cfg
         N, H, W, C = xh.shape
         Cout = w32.shape[0]
         T = xh.dtype
-        gyh = gy.to(T).permute(0, 2, 3, 1).contiguous()
-        need_noise = nz is not None and ctx.needs_input_grad[3]
+        vxh = torch.zeros_like(xh) if vx is None else vx.to(T).permute(0, 2, 3, 1).contiguous()
+        vs32 = torch.zeros_like(s32) if vs is None else vs.to(torch.float32).contiguous()
         weff = w32.flip(2, 3) if flipped else w32
-        # gu = d gy, d gd = sum_p gy (y - noise), dnoise = sum_o gy: one pass over gy and y
-        gu, dgd, gnoise = gyh, None, None
+        wimg = weff.permute(0, 2, 3, 1).contiguous().to(T)
+        r = e = None
         if demodulate:
-            gu, dgd, gnoise = _reduce_raw(gyh, b=y, rowsub=nz, rowsub_stride=(H * W if (nz is not None and nz.dim() == 4) else 0), scale=post,
-                                          want_rowsum=need_noise)
-        elif post is not None:
-            gu, _, gnoise = _reduce_raw(gyh, scale=post, want_rowsum=need_noise)
-        elif need_noise:
-            _, _, gnoise = _reduce_raw(gyh, want_rowsum=True)
-        # unscaled data gradient through the same kernel (d rides on gy as its pre-scale: fp32 product, one rounding), then dx = s gxs, sum_p x gxs
-        if up == 1:
-            wd = weff.flip(2, 3).permute(1, 2, 3, 0).contiguous().to(T)          # [C][2-r][2-s][Cout]
-            gxs = _modconv_raw(gyh, wd, C, k, "same", pre=post)
-        else:
-            wd = weff.permute(1, 2, 3, 0).contiguous().to(T)                     # [C][r][s][Cout]: gxs[h,w] = sum gu[2h+r, 2w+s] W[r,s]
-            gxs = _modconv_raw(gyh, wd, C, k, "down2", pre=post)
-        dx, ds, _ = _reduce_raw(gxs, b=xh, scale=s32)
-        t = None
-        if demodulate:
-            t = dgd * dco * dco                                                  # gd d^3
-            ds = ds - s32 * (t @ Q)
-        dw = None
-        if ctx.needs_input_grad[1]:
-            xs, _, _ = _reduce_raw(xh, scale=s32)                                # s x, materialised for the weight-gradient kernel
-            if up == 1:
-                dwi = torch.zeros((Cout, k, k, C), dtype=torch.float32, device=xh.device)
-                conv2d_wgrad_raw(xs, gu, L.ptr(dwi), C, Cout, k, k, H, W, 1, k // 2, k // 2)
-                dw = dwi.permute(0, 3, 1, 2)
-            else:   # transposed: the roles swap (the stride-2 convolution gu -> gxs has the weight image [C][r][s][Cout])
-                dwi = torch.zeros((C, k, k, Cout), dtype=torch.float32, device=xh.device)
-                conv2d_wgrad_raw(gu, xs, L.ptr(dwi), Cout, C, k, k, H, W, 2, 0, 0)
-                dw = dwi.permute(3, 0, 1, 2)
-            if flipped:
-                dw = dw.flip(2, 3)
+            r = (s32 * vs32) @ Q.t()
+            e = -(dco * dco) * r
+        operand = None
+        if tangent_fused(T, up):
+            nstride = H * W if (nz is not None and nz.dim() == 4) else 0
+            ydot = _jvp_raw(xh, vxh, wimg, Cout, k, "same" if up == 1 else "up2", s32, vs32, post, y, e, nz, nstride)
+        else:       # the composition: the operand materialised (the weight's gradient below takes it too), the forward launch, one multiply-add with y
+            operand = _reduce_raw(vxh, scale=s32)[0] + _reduce_raw(xh, scale=vs32)[0]
+            ydot = _modconv_raw(operand, wimg, Cout, k, "same" if up == 1 else "up2", post=post)
             if demodulate:
-                dw = dw - w32 * (t.t() @ (s32 * s32))[:, :, None, None]
-            dw = dw.to(w_dtype)
-        dn = None
-        if need_noise:
-            dn = gnoise.reshape(N, 1, H, W) if len(noise_info[1]) == 4 else gnoise.sum(dim=0).reshape(H, W)
-            dn = dn.to(noise_info[0])
-        return dx.permute(0, 3, 1, 2), dw, ds.to(s_dtype), dn, None, None, None, None
+                u = y if nz is None else y - nz.reshape(-1, H, W, 1).to(T)
+                ydot = torch.addcmul(ydot, e.to(T)[:, None, None, :], u)
+        d_gy = ydot.permute(0, 3, 1, 2).to(ctx.gy_dtype) if ctx.needs_input_grad[0] else None
+        need_x, need_w, need_s = ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        if not (need_x or need_w or need_s):
+            return (d_gy, None, None, None) + (None,) * 11
+        # d_x and the pixel sums of d_s: G with the cotangents, then G' through the data-gradient route with the pre-table g d' = post e
+        vsG, sum_vxG, _ = _reduce_raw(gxs, b=vxh, scale=vs32)
+        d_x, d_s = vsG, sum_vxG
+        poste = None
+        if demodulate:
+            poste = post * e                                                    # g d'
+            g2 = _data_grad(gyh, weff, poste, up, k, C, T)
+            sG2, sum_xG2, _ = _reduce_raw(g2, b=xh, scale=s32)
+            d_x = d_x + sG2
+            _, s1, _ = _reduce_raw(gyh, b=ydot)                                 # sum_p gy y'
+            alpha, beta, d2 = s1 - e * dgd, dgd, dco * dco
+            t1, t2 = -alpha * d2 + 3.0 * beta * d2 * d2 * r, beta * d2
+            d_s = d_s + sum_xG2 + s32 * (t1 @ Q) - vs32 * (t2 @ Q)
+        d_w = None
+        if need_w:
+            if operand is None:
+                operand = _reduce_raw(vxh, scale=s32)[0] + _reduce_raw(xh, scale=vs32)[0]      # s vx + vs x, materialised for the weight-gradient kernel
+            dwi = _wgrad_image(up, k, C, Cout, xh.device)
+            _wgrad_into(dwi, operand, gu, up, k, C, Cout, H, W)
+            if demodulate:
+                xs, _, _ = _reduce_raw(xh, scale=s32)
+                gue, _, _ = _reduce_raw(gyh, scale=poste)                       # g d' gy
+                _wgrad_into(dwi, xs, gue, up, k, C, Cout, H, W)
+            d_w = _wgrad_as_weight(dwi, up, flipped)
+            if demodulate:
+                d_w = d_w + w32 * (t1.t() @ (s32 * s32) - 2.0 * (t2.t() @ (s32 * vs32)))[:, :, None, None]
+            d_w = d_w.to(w_dtype)
+        return (d_gy, d_x.permute(0, 3, 1, 2) if need_x else None, d_w, d_s.to(s_dtype) if need_s else None) + (None,) * 11
 
 
 def modulated_conv2d(x, weight, styles, noise=None, up=1, down=1, padding=0, resample_filter=None, demodulate=True, flip_weight=True, fused_modconv=True):
@@ -191,7 +339,8 @@ def modulated_conv2d(x, weight, styles, noise=None, up=1, down=1, padding=0, res
     float32 next to a bfloat16 x; noise: [N, 1, Ho, Wo] or one shared [Ho, Wo] plane. The result is channels_last. fused_modconv is accepted and has no
     effect: there is one route here. Supported: k = 1 or 3 with padding = k // 2, down = 1, up = 1, and up = 2 for k = 3 (transposed stride-2 convolution in
     the kernel, then upfirdn2d with gain 4, then the noise: conv2d_resample.py:81-125; resample_filter=None is the identity filter, plain zero insertion).
-    First-order gradients only."""
+    First-order gradients; second order (the gradient of <vx, dx> + <vs, ds> for gy, x, styles and weight: path-length regularisation) inside
+    style_ops.second_order(generator=True), _ModConvGradFn."""
     N, C, H, W, Cout, k = _validate(x, weight, styles, noise, up, down, padding, resample_filter)
     L.require_gpu(x.device)
     if up == 1:
@@ -213,7 +362,7 @@ def modulated_conv2d_act(x, weight, styles, noise=None, up=1, down=1, padding=0,
     up = 1: the convolution kernel (noise in its epilogue) and sg_bias_act, the two launches of the separate operators. up = 2: the transposed convolution to
     the [2H+1, 2W+1] core, then ONE sg_fir_bias_act_nhwc (style_ops/fir_bias_act.py): low-pass, noise, bias, activation, gain and clamp on the fp32
     accumulator, channels-last in and out. noise and bias enter in fp32 there, where the separate operators round both to x's dtype and round the activation
-    after the FIR and after the noise. act: 'linear' or 'lrelu' at up = 2. First-order gradients only."""
+    after the FIR and after the noise. act: 'linear' or 'lrelu' at up = 2. Second order as modulated_conv2d's (the tail's: fir_bias_act._FirBiasActGradFn)."""
     from .bias_act import bias_act
     from ._fir_common import ACTS, MAX_TAPS
     from .fir_bias_act import fir_bias_act
