@@ -11,40 +11,80 @@
 // fp32: v_mfma_f32_32x32x2_f32 (the exact chain) whatever sg_set_f32_mode says -- the operator's fp32 is a parity path.
 #include "conv_common.h"
 
-static long long g_modconv_launches = 0;
+static long long g_modconv_launches = 0, g_modconv_jvp_launches = 0;
 extern "C" long long sg_modconv_launches() { return __atomic_load_n(&g_modconv_launches, __ATOMIC_RELAXED); }
+extern "C" long long sg_modconv_jvp_launches() { return __atomic_load_n(&g_modconv_jvp_launches, __ATOMIC_RELAXED); }
 
-// pixel-side operand with the per-(sample, channel) factor folded in
-template <typename T, bool FAST> struct ModPixKC {
+// ---- the forward-mode tangent (second order: path-length regularisation), JVP = true below ------------------------------------------------------
+//   out[n,p,o] = post[n,o] * sum_{r,s,c} W[o][r][s][c] * ( pre[n,c] * vx[n,tap,c] + vs[n,c] * x[n,tap,c] )  +  e[n,o] * ( y[n,p,o] - noise[n,p] )
+// the tangent of the forward along (vx, vs): the operand of the contraction is the tangent of pre * x, the last term the tangent of the demodulation
+// coefficient riding on the stored result. Same engine, same policies: what the tangent adds to each sits in an `if constexpr (JVP)` and in members that are
+// empty for the plain instantiation. The kernels are the ones the two separate pairs of policies compiled to, instruction for instruction (20 of the 22; the
+// two bf16 16-byte-path tangent kernels differ by one s_nop per table read): the members keep their places among the kernel arguments and the table reads
+// their order, which is what the scheduler starts from -- both are written as they are for that reason (profiles/modconv_fold_resources.txt).
+
+// VEC factors of each of NT [N][C] table rows for the chunk that starts at channel c0: ONE walk over the chunk's channels reads every table
+template <int VEC, bool FAST, int NT> __device__ __forceinline__ void mod_factors(const float* const (&row)[NT], int c0, int C, float (&m)[NT][VEC]) {
+  if constexpr (FAST) {        // C % VEC == 0: the chunk is VEC consecutive channels of one tap; the tables are 16-byte aligned (launcher)
+#pragma unroll
+    for (int q = 0; q < VEC / 4; q++) {
+#pragma unroll
+      for (int k = 0; k < NT; k++) {
+        const f32x4 t = *(const f32x4*)(row[k] + c0 + 4 * q);
+        m[k][4 * q] = t[0]; m[k][4 * q + 1] = t[1]; m[k][4 * q + 2] = t[2]; m[k][4 * q + 3] = t[3];
+      }
+    }
+  } else {                     // the chunk may run over a tap boundary: the channel wraps (more than once when C < VEC)
+    int c = c0;
+#pragma unroll
+    for (int e = 0; e < VEC; e++) {
+#pragma unroll
+      for (int k = 0; k < NT; k++) m[k][e] = row[k][c];
+      c++; if (c == C) c = 0;
+    }
+  }
+}
+
+// a member only the tangent has: M with JVP, else an empty type of its own (ID) that [[no_unique_address]] gives no room, so that the plain instantiation's
+// kernel arguments are those of a struct without it, and the tangent's stand in the order M is declared at
+template <int ID> struct ModAbsent {};
+template <bool JVP, typename M, int ID> using mod_tangent_t = std::conditional_t<JVP, M, ModAbsent<ID>>;
+
+// pixel-side operand with the per-(sample, channel) factor folded in: pre * x, or its tangent vs * x + pre * vx; formed in fp32, rounded once to the MFMA operand
+template <typename T, bool FAST, bool JVP = false> struct ModPixKC {
   static constexpr bool KC = true;
-  static constexpr int VEC = ET<T>::VEC, BK = ET<T>::BK;
+  static constexpr int VEC = ET<T>::VEC, BK = ET<T>::BK, NT = JVP ? 2 : 1;
   typedef ConvPixKC<T, FAST> Base;
   typedef typename Base::Chunk Chunk;
-  Base b;
-  const float* pre;      // [N][C] fp32 or nullptr
+  Base b;                                                     // x
+  [[no_unique_address]] mod_tangent_t<JVP, Base, 0> bv;          // vx: the geometry of b, another base pointer
+  const float* pre;                                           // [N][C] fp32: the styles; the plain instantiation takes nullptr (the chunk passes as loaded)
+  [[no_unique_address]] mod_tangent_t<JVP, const float*, 1> vs;  // [N][C] fp32: the tangent of the styles
   __device__ __forceinline__ void set_batch(int) {}
   __device__ __forceinline__ void init(Chunk& ch, int row, int k) const { b.init(ch, row, k); }
   __device__ __forceinline__ void advance(Chunk& ch) const { b.advance(ch); }
   __device__ __forceinline__ u32x4 load(const Chunk& ch) const {
     const u32x4 v = b.load(ch);
-    if (!pre) return v;
-    // rows behind the problem hold zeros and have no sample (ch.n >= N): row 0 of the table stands in. ch.c is always inside [0, C).
-    const float* s = pre + (ch.valid ? (long long)ch.n * b.g.C : 0ll);
-    float f[VEC], m[VEC];
+    u32x4 vv;                  // the chunk of vx at the same geometry: both global loads are issued before either is unpacked
+    if constexpr (JVP) vv = bv.load(ch);
+    else if (!pre) return v;
+    // rows behind the problem hold zeros and have no sample (ch.n >= N): row 0 of the tables stands in. ch.c is always inside [0, C).
+    const long long row = ch.valid ? (long long)ch.n * b.g.C : 0ll;
+    const float* tab[NT];
+    tab[0] = pre + row;
+    if constexpr (JVP) tab[1] = vs + row;
+    float f[VEC], m[NT][VEC];
+    mod_factors<VEC, FAST, NT>(tab, ch.c, b.g.C, m);
     unpack16<T>(v, f);
-    if constexpr (FAST) {      // C % VEC == 0: the chunk is VEC consecutive channels of one tap; pre is 16-byte aligned (launcher)
+    if constexpr (JVP) {
+      float fv[VEC];
+      unpack16<T>(vv, fv);
 #pragma unroll
-      for (int q = 0; q < VEC / 4; q++) {
-        const f32x4 t = *(const f32x4*)(s + ch.c + 4 * q);
-        m[4 * q] = t[0]; m[4 * q + 1] = t[1]; m[4 * q + 2] = t[2]; m[4 * q + 3] = t[3];
-      }
-    } else {                   // the chunk may run over a tap boundary: the channel wraps (more than once when C < VEC)
-      int c = ch.c;
+      for (int e = 0; e < VEC; e++) f[e] = m[1][e] * f[e] + m[0][e] * fv[e];
+    } else {
 #pragma unroll
-      for (int e = 0; e < VEC; e++) { m[e] = s[c]; c++; if (c == b.g.C) c = 0; }
+      for (int e = 0; e < VEC; e++) f[e] *= m[0][e];
     }
-#pragma unroll
-    for (int e = 0; e < VEC; e++) f[e] *= m[e];
     if constexpr (sizeof(T) == 4) return pack16<float>(f);
     else {
       u32x4 o;
@@ -55,120 +95,59 @@ template <typename T, bool FAST> struct ModPixKC {
   }
 };
 
-// Epilogue + the per-(sample, cout) factor and the noise plane, both on the fp32 accumulator
-template <typename T> struct ModEpilogue : Epilogue<T> {
-  const float* post;       // [N][I] or nullptr
-  const float* noise;      // [.][HW] or nullptr
-  long long noise_stride;  // floats between samples; 0 = one plane for all
+// Epilogue + the per-(sample, cout) factor on the fp32 accumulator, then the noise plane or the tangent's e * (y - noise) from the stored forward result;
+// one rounding, on store
+template <typename T, bool JVP = false> struct ModEpilogue : Epilogue<T> {
+  const float* post;                                          // [N][I] or nullptr
+  [[no_unique_address]] mod_tangent_t<JVP, const float*, 2> e;   // [N][I] or nullptr (no demodulation: no second term, y is not read)
+  [[no_unique_address]] mod_tangent_t<JVP, const T*, 3> y;       // [J][ldy]: the forward's result
+  const float* noise;                                         // [.][HW] or nullptr; the tangent's: what the forward added to y
+  long long noise_stride;                                     // floats between samples; 0 = one plane for all
+  [[no_unique_address]] mod_tangent_t<JVP, int, 4> ldy;
   int HW;
-  int post_vec;            // post rows can be read as f32x4
+  int tab_vec;             // I % 4 == 0 and 16-byte aligned tables: a lane's four factors of a table row in one f32x4 load
+  static __device__ __forceinline__ void load4(const float* t, float d[4]) {
+    const f32x4 q = *(const f32x4*)t;
+    d[0] = q[0]; d[1] = q[1]; d[2] = q[2]; d[3] = q[3];
+  }
   __device__ __forceinline__ void store(int j, int i0, float v[4], float a) const {
     if (j < this->J && i0 < this->I) {
       const int n = j / HW, p = j - n * HW;
       const int ne = (this->I - i0) < 4 ? (this->I - i0) : 4;
-      const float z = noise ? noise[(long long)n * noise_stride + p] : 0.f;
       float d[4] = {1.f, 1.f, 1.f, 1.f};
-      if (post) {
-        const float* pr = post + (long long)n * this->I + i0;
-        if (post_vec) {        // I % 4 == 0 and a 16-byte aligned table: the lane's four factors in one load
-          const f32x4 t = *(const f32x4*)pr;
-          d[0] = t[0]; d[1] = t[1]; d[2] = t[2]; d[3] = t[3];
+      // The two table fetches below do the same thing and are NOT written as one: the tangent branches on tab_vec first and on each table inside, the plain
+      // one on post first, and either shape given to the other changes that kernel's instruction stream (tried both ways).
+      if constexpr (JVP) {
+        float c[4] = {0.f, 0.f, 0.f, 0.f}, u[4] = {0.f, 0.f, 0.f, 0.f};
+        const long long row = (long long)n * this->I + i0;
+        if (tab_vec) {
+          if (post) load4(post + row, d);
+          if (e) load4(e + row, c);
         } else {
 #pragma unroll
-          for (int e = 0; e < 4; e++) if (e < ne) d[e] = pr[e];
+          for (int q = 0; q < 4; q++) if (q < ne) { if (post) d[q] = post[row + q]; if (e) c[q] = e[row + q]; }
         }
-      }
+        if (e) {               // (without e the launcher passes no noise either)
+          const float z = noise ? noise[(long long)n * noise_stride + p] : 0.f;
+          const T* yr = y + (long long)j * ldy + i0;
 #pragma unroll
-      for (int e = 0; e < 4; e++) v[e] = v[e] * a * d[e] + z;
-    }
-    Epilogue<T>::store(j, i0, v, 1.f);      // (rows / columns behind the problem: nothing is written)
-  }
-};
-
-// ---- the forward-mode tangent (second order: path-length regularisation) ---------------------------------------------------------------------
-//   out[n,p,o] = post[n,o] * sum_{r,s,c} W[o][r][s][c] * ( pre[n,c] * vx[n,tap,c] + vs[n,c] * x[n,tap,c] )  +  e[n,o] * ( y[n,p,o] - noise[n,p] )
-// the tangent of the forward along (vx, vs): the operand of the contraction is the tangent of pre * x, the last term the tangent of the demodulation
-// coefficient riding on the stored result. Same engine, same tile table; only the two policies below differ from the plain instantiation.
-
-// pixel-side operand: the chunk of x and the chunk of vx at the same geometry from two base pointers. Both loads are issued before either is unpacked;
-// vs * x + pre * vx in fp32, rounded once to the MFMA operand as ModPixKC::load rounds pre * x.
-template <typename T, bool FAST> struct ModJvpPixKC {
-  static constexpr bool KC = true;
-  static constexpr int VEC = ET<T>::VEC, BK = ET<T>::BK;
-  typedef ConvPixKC<T, FAST> Base;
-  typedef typename Base::Chunk Chunk;
-  Base b;                // x
-  Base bv;               // vx: the geometry of b, another base pointer
-  const float* pre;      // [N][C] fp32: the styles
-  const float* vs;       // [N][C] fp32: their tangent
-  __device__ __forceinline__ void set_batch(int) {}
-  __device__ __forceinline__ void init(Chunk& ch, int row, int k) const { b.init(ch, row, k); }
-  __device__ __forceinline__ void advance(Chunk& ch) const { b.advance(ch); }
-  __device__ __forceinline__ u32x4 load(const Chunk& ch) const {
-    const u32x4 vx16 = b.load(ch);
-    const u32x4 vv16 = bv.load(ch);
-    // rows behind the problem hold zeros and have no sample (ch.n >= N): row 0 of the tables stands in. ch.c is always inside [0, C).
-    const long long row = ch.valid ? (long long)ch.n * b.g.C : 0ll;
-    const float* s = pre + row;
-    const float* t = vs + row;
-    float fx[VEC], fv[VEC], ms[VEC], mt[VEC];
-    if constexpr (FAST) {      // C % VEC == 0: the chunk is VEC consecutive channels of one tap; both tables are 16-byte aligned (launcher)
+          for (int q = 0; q < 4; q++) if (q < ne) u[q] = to_f<T>(yr[q]) - z;
+        }
 #pragma unroll
-      for (int q = 0; q < VEC / 4; q++) {
-        const f32x4 a = *(const f32x4*)(s + ch.c + 4 * q);
-        const f32x4 c = *(const f32x4*)(t + ch.c + 4 * q);
-        ms[4 * q] = a[0]; ms[4 * q + 1] = a[1]; ms[4 * q + 2] = a[2]; ms[4 * q + 3] = a[3];
-        mt[4 * q] = c[0]; mt[4 * q + 1] = c[1]; mt[4 * q + 2] = c[2]; mt[4 * q + 3] = c[3];
-      }
-    } else {                   // the chunk may run over a tap boundary: the channel wraps (more than once when C < VEC)
-      int c = ch.c;
-#pragma unroll
-      for (int e = 0; e < VEC; e++) { ms[e] = s[c]; mt[e] = t[c]; c++; if (c == b.g.C) c = 0; }
-    }
-    unpack16<T>(vx16, fx);
-    unpack16<T>(vv16, fv);
-#pragma unroll
-    for (int e = 0; e < VEC; e++) fx[e] = mt[e] * fx[e] + ms[e] * fv[e];
-    if constexpr (sizeof(T) == 4) return pack16<float>(fx);
-    else {
-      u32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; e++) o[e] = pack2bf(fx[2 * e], fx[2 * e + 1]);
-      return o;
-    }
-  }
-};
-
-// Epilogue + post on the fp32 accumulator + e * (y - noise) from the stored forward result; one rounding, on store
-template <typename T> struct ModJvpEpilogue : Epilogue<T> {
-  const float* post;       // [N][I] or nullptr
-  const float* e;          // [N][I] or nullptr (no demodulation: no second term, y is not read)
-  const T* y;              // [J][ldy]: the forward's result
-  const float* noise;      // what the forward added to y: [.][HW] or nullptr
-  long long noise_stride;
-  int ldy, HW;
-  int tab_vec;             // post and e rows can be read as f32x4
-  __device__ __forceinline__ void store(int j, int i0, float v[4], float a) const {
-    if (j < this->J && i0 < this->I) {
-      const int n = j / HW, p = j - n * HW;
-      const int ne = (this->I - i0) < 4 ? (this->I - i0) : 4;
-      float d[4] = {1.f, 1.f, 1.f, 1.f}, c[4] = {0.f, 0.f, 0.f, 0.f}, u[4] = {0.f, 0.f, 0.f, 0.f};
-      const long long row = (long long)n * this->I + i0;
-      if (tab_vec) {           // I % 4 == 0 and 16-byte aligned tables: the lane's four factors in one load each
-        if (post) { const f32x4 t = *(const f32x4*)(post + row); d[0] = t[0]; d[1] = t[1]; d[2] = t[2]; d[3] = t[3]; }
-        if (e) { const f32x4 t = *(const f32x4*)(e + row); c[0] = t[0]; c[1] = t[1]; c[2] = t[2]; c[3] = t[3]; }
+        for (int q = 0; q < 4; q++) v[q] = v[q] * a * d[q] + c[q] * u[q];
       } else {
-#pragma unroll
-        for (int q = 0; q < 4; q++) if (q < ne) { if (post) d[q] = post[row + q]; if (e) c[q] = e[row + q]; }
-      }
-      if (e) {
         const float z = noise ? noise[(long long)n * noise_stride + p] : 0.f;
-        const T* yr = y + (long long)j * ldy + i0;
+        if (post) {
+          const float* pr = post + (long long)n * this->I + i0;
+          if (tab_vec) load4(pr, d);
+          else {
 #pragma unroll
-        for (int q = 0; q < 4; q++) if (q < ne) u[q] = to_f<T>(yr[q]) - z;
+            for (int e = 0; e < 4; e++) if (e < ne) d[e] = pr[e];
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; e++) v[e] = v[e] * a * d[e] + z;
       }
-#pragma unroll
-      for (int q = 0; q < 4; q++) v[q] = v[q] * a * d[q] + c[q] * u[q];
     }
     Epilogue<T>::store(j, i0, v, 1.f);      // (rows / columns behind the problem: nothing is written)
   }
@@ -206,52 +185,6 @@ static bool modconv_ok(const sg_modconv_desc* m) {
 }
 extern "C" int sg_modconv2d_ok(const sg_modconv_desc* m) { return modconv_ok(m) ? 1 : 0; }
 
-template <typename T, bool FAST>
-static void modconv_launch(const sg_modconv_desc* m, int I, int J, int K, hipStream_t st) {
-  const sg_conv_fwd_desc* d = &m->conv;
-  typedef StridedKC<T, FAST> LP;
-  typedef ModPixKC<T, FAST> LQ;
-  typedef ModEpilogue<T> EP;
-  LP lp;
-  lp.base = (const T*)d->w; lp.bstride = 0; lp.ld = K; lp.rows = I; lp.K = K;
-  lp.vec_ok = (K % ET<T>::VEC == 0) && aligned16(d->w);
-  LQ lq;
-  fill_geom<T>(lq.b.g, d->x, d->N, d->Hs, d->Ws, d->C, d->ldx, d->Ho, d->Wo, d->R, d->S, d->stride, d->pad_h, d->pad_w, d->pix_flags);
-  lq.b.rows = J; lq.b.K = K; lq.pre = m->pre;
-  EP e;
-  static_cast<Epilogue<T>&>(e) = make_epilogue<T>(d, I, J);
-  e.post = m->post; e.noise = m->noise; e.noise_stride = m->noise_stride; e.HW = d->Ho * d->Wo;
-  e.post_vec = m->post && (I % 4 == 0) && aligned16(m->post);
-  conv_fwd_tiles<T, LP, LQ, 0, EP>(lp, lq, e, I, J, K, st);      // the generic engine's tile table, exact fp32 MFMA
-}
-
-template <typename T> static int modconv_t(const sg_modconv_desc* m, hipStream_t st) {
-  const sg_conv_fwd_desc* d = &m->conv;
-  const int K = d->R * d->S * d->C, I = d->Cout, J = d->N * d->Ho * d->Wo;
-  const bool w_vec = (K % ET<T>::VEC == 0) && aligned16(d->w);
-  const bool x_vec = (d->C % ET<T>::VEC == 0) && (d->ldx % ET<T>::VEC == 0) && aligned16(d->x) && (!m->pre || aligned16(m->pre));
-  const int prof = sg_prof_begin(st, 2.0 * (double)I * (double)J * (double)K, 0);
-  if (w_vec && x_vec) modconv_launch<T, true>(m, I, J, K, st);
-  else modconv_launch<T, false>(m, I, J, K, st);
-  sg_prof_tag(prof, SG_ENG_CONV_GEMM, (double)sizeof(T) * ((double)d->N * d->Hs * d->Ws * d->C + (double)I * K + (double)J * I));
-  sg_prof_end(st, prof);
-  SG_LAUNCH_CHECK();
-  __atomic_fetch_add(&g_modconv_launches, 1, __ATOMIC_RELAXED);
-  return 0;
-}
-
-extern "C" int sg_modconv2d_fwd(const sg_modconv_desc* m, sg_stream_t stream) {
-  SG_CHECK(m && m->conv.x && m->conv.w && m->conv.out, "sg_modconv2d_fwd: null pointer");
-  SG_CHECK(modconv_ok(m), "sg_modconv2d_fwd: problem not served (ask sg_modconv2d_ok first): fp32 / bf16; 1x1 or 3x3 at stride 1 and pad k/2, the 3x3 stride-2 "
-                          "transposed gather, or the plain 3x3 stride-2 convolution; no mask / residual / epilogue flags");
-  if (m->conv.dtype == SG_DTYPE_F32) return modconv_t<float>(m, (hipStream_t)stream);
-  return modconv_t<bf16_t>(m, (hipStream_t)stream);
-}
-
-// ---- sg_modconv2d_jvp ---------------------------------------------------------------------------------------------------------------------------
-static long long g_modconv_jvp_launches = 0;
-extern "C" long long sg_modconv_jvp_launches() { return __atomic_load_n(&g_modconv_jvp_launches, __ATOMIC_RELAXED); }
-
 static bool modconv_jvp_ok(const sg_modconv_jvp_desc* j) {
   if (!j || !modconv_ok(&j->m)) return false;
   const sg_conv_fwd_desc* d = &j->m.conv;
@@ -261,54 +194,78 @@ static bool modconv_jvp_ok(const sg_modconv_jvp_desc* j) {
 }
 extern "C" int sg_modconv2d_jvp_ok(const sg_modconv_jvp_desc* j) { return modconv_jvp_ok(j) ? 1 : 0; }
 
-template <typename T, bool FAST>
-static void modconv_jvp_launch(const sg_modconv_jvp_desc* j, int I, int J, int K, hipStream_t st) {
-  const sg_modconv_desc* m = &j->m;
+// ---- one launcher for both entry points: p is the sg_modconv_desc, or with JVP the sg_modconv_jvp_desc that holds one ---------------------------------
+template <bool JVP> using modconv_desc_t = std::conditional_t<JVP, sg_modconv_jvp_desc, sg_modconv_desc>;
+static const sg_modconv_desc* forward_desc(const sg_modconv_desc* m) { return m; }
+static const sg_modconv_desc* forward_desc(const sg_modconv_jvp_desc* j) { return &j->m; }
+
+template <typename T, bool FAST, bool JVP>
+static void modconv_launch(const modconv_desc_t<JVP>* p, int I, int J, int K, hipStream_t st) {
+  const sg_modconv_desc* m = forward_desc(p);
   const sg_conv_fwd_desc* d = &m->conv;
   typedef StridedKC<T, FAST> LP;
-  typedef ModJvpPixKC<T, FAST> LQ;
-  typedef ModJvpEpilogue<T> EP;
+  typedef ModPixKC<T, FAST, JVP> LQ;
+  typedef ModEpilogue<T, JVP> EP;
   LP lp;
   lp.base = (const T*)d->w; lp.bstride = 0; lp.ld = K; lp.rows = I; lp.K = K;
   lp.vec_ok = (K % ET<T>::VEC == 0) && aligned16(d->w);
   LQ lq;
   fill_geom<T>(lq.b.g, d->x, d->N, d->Hs, d->Ws, d->C, d->ldx, d->Ho, d->Wo, d->R, d->S, d->stride, d->pad_h, d->pad_w, d->pix_flags);
-  fill_geom<T>(lq.bv.g, j->vx, d->N, d->Hs, d->Ws, d->C, d->ldx, d->Ho, d->Wo, d->R, d->S, d->stride, d->pad_h, d->pad_w, d->pix_flags);
-  lq.b.rows = lq.bv.rows = J; lq.b.K = lq.bv.K = K; lq.pre = m->pre; lq.vs = j->vs;
+  lq.b.rows = J; lq.b.K = K; lq.pre = m->pre;
   EP e;
   static_cast<Epilogue<T>&>(e) = make_epilogue<T>(d, I, J);
-  e.post = m->post; e.e = j->e; e.y = (const T*)j->y; e.ldy = j->ldy; e.noise = j->e ? m->noise : nullptr; e.noise_stride = m->noise_stride;
-  e.HW = d->Ho * d->Wo;
-  e.tab_vec = (I % 4 == 0) && (!m->post || aligned16(m->post)) && (!j->e || aligned16(j->e));
-  // fp32: the generic engine's tile table, as the forward. bf16: without its 96 x 256 tile -- with the second operand chunk and the second table in flight
-  // that instantiation needs 280 VGPRs + 96 AGPRs and spills 448 bytes (profiles/modconv_jvp_resources.txt); a ragged cout tile of 128 x 128 costs idle MFMA
-  // rows, not scratch traffic in the k-loop.
-  if constexpr (sizeof(T) == 4) conv_fwd_tiles<T, LP, LQ, 0, EP>(lp, lq, e, I, J, K, st);
+  e.post = m->post; e.noise = m->noise; e.noise_stride = m->noise_stride; e.HW = d->Ho * d->Wo;
+  if constexpr (JVP) {
+    fill_geom<T>(lq.bv.g, p->vx, d->N, d->Hs, d->Ws, d->C, d->ldx, d->Ho, d->Wo, d->R, d->S, d->stride, d->pad_h, d->pad_w, d->pix_flags);
+    lq.bv.rows = J; lq.bv.K = K; lq.vs = p->vs;
+    e.e = p->e; e.y = (const T*)p->y; e.ldy = p->ldy;
+    if (!p->e) e.noise = nullptr;      // the noise enters through e * (y - noise) alone
+    e.tab_vec = (I % 4 == 0) && (!m->post || aligned16(m->post)) && (!p->e || aligned16(p->e));
+  } else {
+    e.tab_vec = m->post && (I % 4 == 0) && aligned16(m->post);
+  }
+  // The generic engine's tile table, exact fp32 MFMA. The tangent in bf16: without its 96 x 256 tile -- with the second operand chunk and the second table in
+  // flight that instantiation needs 280 VGPRs + 96 AGPRs and spills 448 bytes (profiles/modconv_jvp_resources.txt); a ragged cout tile of 128 x 128 costs idle
+  // MFMA rows, not scratch traffic in the k-loop.
+  if constexpr (!JVP || sizeof(T) == 4) conv_fwd_tiles<T, LP, LQ, 0, EP>(lp, lq, e, I, J, K, st);
   else if (I <= 32) sg_launch_gemm<T, LP, LQ, 32, 256, 1, 4, true, 0, EP>(lp, lq, e, I, J, K, 1, 1, st);
   else sg_launch_gemm<T, LP, LQ, 128, 128, 2, 2, true, 0, EP>(lp, lq, e, I, J, K, 1, 1, st);
 }
 
-template <typename T> static int modconv_jvp_t(const sg_modconv_jvp_desc* j, hipStream_t st) {
-  const sg_conv_fwd_desc* d = &j->m.conv;
+template <typename T, bool JVP> static int modconv_t(const modconv_desc_t<JVP>* p, hipStream_t st) {
+  const sg_modconv_desc* m = forward_desc(p);
+  const sg_conv_fwd_desc* d = &m->conv;
   const int K = d->R * d->S * d->C, I = d->Cout, J = d->N * d->Ho * d->Wo;
   const bool w_vec = (K % ET<T>::VEC == 0) && aligned16(d->w);
-  const bool x_vec = (d->C % ET<T>::VEC == 0) && (d->ldx % ET<T>::VEC == 0) && aligned16(d->x) && aligned16(j->vx) && aligned16(j->m.pre) && aligned16(j->vs);
+  bool x_vec = (d->C % ET<T>::VEC == 0) && (d->ldx % ET<T>::VEC == 0) && aligned16(d->x) && (!m->pre || aligned16(m->pre));
+  double x_reads = 1.0, out_passes = 1.0;      // what the tangent moves more: the second operand, and y wherever e is given
+  if constexpr (JVP) {
+    x_vec = x_vec && aligned16(p->vx) && aligned16(p->vs);
+    x_reads = 2.0; out_passes = p->e ? 2.0 : 1.0;
+  }
   const int prof = sg_prof_begin(st, 2.0 * (double)I * (double)J * (double)K, 0);
-  if (w_vec && x_vec) modconv_jvp_launch<T, true>(j, I, J, K, st);
-  else modconv_jvp_launch<T, false>(j, I, J, K, st);
-  sg_prof_tag(prof, SG_ENG_CONV_GEMM, (double)sizeof(T) * (2.0 * (double)d->N * d->Hs * d->Ws * d->C + (double)I * K + (j->e ? 2.0 : 1.0) * (double)J * I));
+  if (w_vec && x_vec) modconv_launch<T, true, JVP>(p, I, J, K, st);
+  else modconv_launch<T, false, JVP>(p, I, J, K, st);
+  sg_prof_tag(prof, SG_ENG_CONV_GEMM, (double)sizeof(T) * (x_reads * (double)d->N * d->Hs * d->Ws * d->C + (double)I * K + out_passes * (double)J * I));
   sg_prof_end(st, prof);
   SG_LAUNCH_CHECK();
-  __atomic_fetch_add(&g_modconv_jvp_launches, 1, __ATOMIC_RELAXED);
+  __atomic_fetch_add(JVP ? &g_modconv_jvp_launches : &g_modconv_launches, 1, __ATOMIC_RELAXED);
   return 0;
 }
 
+extern "C" int sg_modconv2d_fwd(const sg_modconv_desc* m, sg_stream_t stream) {
+  SG_CHECK(m && m->conv.x && m->conv.w && m->conv.out, "sg_modconv2d_fwd: null pointer");
+  SG_CHECK(modconv_ok(m), "sg_modconv2d_fwd: problem not served (ask sg_modconv2d_ok first): fp32 / bf16; 1x1 or 3x3 at stride 1 and pad k/2, the 3x3 stride-2 "
+                          "transposed gather, or the plain 3x3 stride-2 convolution; no mask / residual / epilogue flags");
+  if (m->conv.dtype == SG_DTYPE_F32) return modconv_t<float, false>(m, (hipStream_t)stream);
+  return modconv_t<bf16_t, false>(m, (hipStream_t)stream);
+}
 extern "C" int sg_modconv2d_jvp(const sg_modconv_jvp_desc* j, sg_stream_t stream) {
   SG_CHECK(j && j->m.conv.x && j->m.conv.w && j->m.conv.out && j->vx && j->vs && j->m.pre, "sg_modconv2d_jvp: null pointer");
   SG_CHECK(modconv_jvp_ok(j), "sg_modconv2d_jvp: problem not served (ask sg_modconv2d_jvp_ok first): sg_modconv2d_fwd's problems with both tables, both "
                               "operands, and the stored result wherever e is given");
-  if (j->m.conv.dtype == SG_DTYPE_F32) return modconv_jvp_t<float>(j, (hipStream_t)stream);
-  return modconv_jvp_t<bf16_t>(j, (hipStream_t)stream);
+  if (j->m.conv.dtype == SG_DTYPE_F32) return modconv_t<float, true>(j, (hipStream_t)stream);
+  return modconv_t<bf16_t, true>(j, (hipStream_t)stream);
 }
 
 // ---- demodulation coefficients: Q[o][c] = sum_{r,s} W[o][c][r][s]^2,  d[n][o] = ( sum_c s[n][c]^2 Q[o][c] + 1e-8 )^(-1/2), all fp32 ------------

@@ -18,6 +18,7 @@ from .. import _lib as L
 from ..functional._base import _first_order_only
 from ._fir_common import ACTS, MAX_TAPS, check_args, epilogue_args, epilogue_defaults, filter_2d, nhwc_out, out_size  # noqa: F401  (ACTS, MAX_TAPS, filter_2d: this module's public names)
 from .bias_act import activation_funcs
+from .modulated_conv2d import _reduce_raw, dnoise_of, noise_plane
 
 
 def fir_nhwc_raw(xh, f2d, pad, flip_filter=False, filter_gain=1.0, noise=None, noise_stride=0, bias=None, act="linear", alpha=0.0, gain=1.0, clamp=-1.0):
@@ -35,10 +36,7 @@ class FirBiasActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, f2d, noise, bias, pad, flip_filter, filter_gain, act, alpha, gain, clamp):
         xh = x.permute(0, 2, 3, 1).contiguous()                 # free for a channels_last x
-        nz, nstride = None, 0
-        if noise is not None:
-            nz = noise.detach().to(torch.float32).contiguous()
-            nstride = nz.shape[-2] * nz.shape[-1] if nz.dim() == 4 else 0
+        nz, nstride = noise_plane(None if noise is None else noise.detach())
         b32 = None if bias is None else bias.detach().to(torch.float32).contiguous()
         y = fir_nhwc_raw(xh, f2d, pad, flip_filter, filter_gain, nz, nstride, b32, act, alpha, gain, clamp)
         ctx.save_for_backward(f2d, y)
@@ -75,10 +73,7 @@ def _first_order(dy, f2d, y, cfg, needs):
         adj = (fw - px0 - 1, Wi - Wo + px0, fh - py0 - 1, Hi - Ho + py0)
         dx = fir_nhwc_raw(dpre, f2d, adj, not flip_filter, filter_gain).permute(0, 3, 1, 2)
     if needs[1]:
-        rows = torch.empty((N, Ho * Wo), dtype=torch.float32, device=dpre.device)
-        L.call("sg_modconv_reduce", L.dt(dpre), L.ptr(dpre), None, None, 0, None, None, None, L.ptr(rows), N, Ho * Wo, C, C, C, L.stream())
-        dn = rows.reshape(N, 1, Ho, Wo) if len(noise_info[1]) == 4 else rows.sum(dim=0).reshape(Ho, Wo)
-        dn = dn.to(noise_info[0])
+        dn = dnoise_of(_reduce_raw(dpre, want_rowsum=True)[2], noise_info)
     if needs[2]:
         db = dpre.sum(dim=(0, 1, 2), dtype=torch.float32).to(bias_dtype)
     return dx, dn, db
@@ -112,10 +107,7 @@ class _FirBiasActGradFn(torch.autograd.Function):
         f2d, y = ctx.saved_tensors
         (N, Hi, Wi, C), pad, flip_filter, filter_gain, act, alpha, gain, clamp, noise_info, bias_dtype = ctx.cfg
         vh = torch.zeros((N, Hi, Wi, C), dtype=y.dtype, device=y.device) if vx is None else vx.to(y.dtype).permute(0, 2, 3, 1).contiguous()
-        vn32, nstride = None, 0
-        if vn is not None:
-            vn32 = vn.to(torch.float32).contiguous()
-            nstride = vn32.shape[-2] * vn32.shape[-1] if vn32.dim() == 4 else 0
+        vn32, nstride = noise_plane(vn)
         vb32 = None if vb is None else vb.to(torch.float32).contiguous()
         d_dy = fir_gate_raw(vh, y, f2d, pad, flip_filter, filter_gain, vn32, nstride, vb32, act, alpha, gain, clamp)
         return d_dy.permute(0, 3, 1, 2).to(ctx.dy_dtype), None, None, None, None

@@ -17,6 +17,8 @@ Gradients (gy = dL/dy; u = the convolution before demodulation, so y = d u + noi
 The backward keeps y, not u: sum_p gy (y - noise) = d gd, so gd d^3 = d^2 sum_p gy (y - noise) and nothing is ever divided by a style or a coefficient
 (styles may be exactly zero). The data gradient runs through the same kernel (pre-scale d on gy), the weight gradient through sg_conv2d_wgrad on the
 materialised s x and gu; the two demodulation terms are [N x Cout]^T [N x C]-sized products in plain torch."""
+import collections
+
 import torch
 
 from .. import _lib as L
@@ -24,28 +26,40 @@ from ..functional._base import _first_order_only, _param_grad_wanted, conv2d_wgr
 from . import upfirdn2d as _upfirdn2d
 
 
-def _validate(x, weight, styles, noise, up, down, padding, resample_filter):
-    """every refusal of the operator, before any device work; -> (N, C, H, W, Cout, k)"""
+def _validate_operands(op, x, weight, styles):
+    """the refusals every route of the operator shares (op: the name they speak under): tensor ranks, shape agreement, dtype; -> (N, C, H, W, Cout, kh, kw)"""
     if not (isinstance(x, torch.Tensor) and x.dim() == 4):
-        raise AssertionError("modulated_conv2d: x must be a 4-D NCHW tensor")
+        raise AssertionError(f"{op}: x must be a 4-D NCHW tensor")
     if not (isinstance(weight, torch.Tensor) and weight.dim() == 4):
-        raise AssertionError("modulated_conv2d: weight must be [out_channels, in_channels, kh, kw]")
+        raise AssertionError(f"{op}: weight must be [out_channels, in_channels, kh, kw]")
     N, C, H, W = x.shape
     Cout, Cw, kh, kw = weight.shape
     if Cw != C or not (isinstance(styles, torch.Tensor) and tuple(styles.shape) == (N, C)):
-        raise AssertionError("modulated_conv2d: weight [O, I, kh, kw], x [N, I, H, W] and styles [N, I] do not agree")
+        raise AssertionError(f"{op}: weight [O, I, kh, kw], x [N, I, H, W] and styles [N, I] do not agree")
     if x.dtype not in (torch.float32, torch.bfloat16):      # float16 included: the reference's pre-normalisation for it is not carried over
-        raise NotImplementedError(f"modulated_conv2d: x of dtype {x.dtype} is not supported (float32 / bfloat16)")
+        raise NotImplementedError(f"{op}: x of dtype {x.dtype} is not supported (float32 / bfloat16)")
+    return N, C, H, W, Cout, kh, kw
+
+
+def _validate_kernel(op, kh, kw):
+    """the shared refusal of anything but a square 1 x 1 or 3 x 3 kernel; -> k"""
+    if kh != kw or kh not in (1, 3):
+        raise NotImplementedError(f"{op}: weight with a {kh} x {kw} kernel is not supported (square 1 x 1 or 3 x 3)")
+    return kh
+
+
+def _validate(x, weight, styles, noise, up, down, padding, resample_filter):
+    """every refusal of the operator, before any device work; -> (N, C, H, W, Cout, k)"""
+    N, C, H, W, Cout, kh, kw = _validate_operands("modulated_conv2d", x, weight, styles)
     if down != 1:
         raise NotImplementedError(f"modulated_conv2d: down={down} is not supported (down=1 only)")
     if up not in (1, 2):
         raise NotImplementedError(f"modulated_conv2d: up={up} is not supported (up=1 or up=2)")
-    if kh != kw or kh not in (1, 3):
-        raise NotImplementedError(f"modulated_conv2d: weight with a {kh} x {kw} kernel is not supported (square 1 x 1 or 3 x 3)")
-    if up == 2 and kh == 1:
+    k = _validate_kernel("modulated_conv2d", kh, kw)
+    if up == 2 and k == 1:
         raise NotImplementedError("modulated_conv2d: up=2 with a 1 x 1 weight is not supported")
-    if padding != kh // 2:
-        raise NotImplementedError(f"modulated_conv2d: padding={padding} is not supported (padding = kernel_size // 2 = {kh // 2})")
+    if padding != k // 2:
+        raise NotImplementedError(f"modulated_conv2d: padding={padding} is not supported (padding = kernel_size // 2 = {k // 2})")
     if resample_filter is not None and not (isinstance(resample_filter, torch.Tensor) and resample_filter.dim() in (1, 2) and resample_filter.dtype == torch.float32):
         raise AssertionError("modulated_conv2d: resample_filter must be None (no low-pass) or a float32 vector / matrix from upfirdn2d.setup_filter")
     if noise is not None:
@@ -53,15 +67,45 @@ def _validate(x, weight, styles, noise, up, down, padding, resample_filter):
         if not (isinstance(noise, torch.Tensor) and (tuple(noise.shape) == (N, 1, Ho, Wo) or tuple(noise.shape) == (Ho, Wo))):
             raise NotImplementedError(f"modulated_conv2d: noise of shape {tuple(noise.shape) if isinstance(noise, torch.Tensor) else noise!r} is not supported "
                                       f"([N, 1, {Ho}, {Wo}] per sample or one shared [{Ho}, {Wo}] plane)")
-    return N, C, H, W, Cout, kh
+    return N, C, H, W, Cout, k
 
 
-def _modconv_raw(x, wimg, Cout, k, mode, pre=None, post=None, noise=None, noise_stride=0):
-    """one sg_modconv2d_fwd launch. x: dense [N,Hs,Ws,C] NHWC; wimg: [Cout][k*k*C] of x.dtype. mode 'same' (stride 1, pad k//2), 'up2' (transposed stride-2
-    gather, [N,2Hs+1,2Ws+1,Cout]) or 'down2' (plain stride 2, pad 0). Returns the NHWC result."""
+def _up2_fir_padding(padding, k, resample_filter, up=2):
+    """[padx0, padx1, pady0, pady1] of the low-pass behind the transposed convolution (conv2d_resample.py:81-125)"""
+    fw, fh = _upfirdn2d._get_filter_size(resample_filter)
+    return [padding + (fw + up - 1) // 2 - (k - 1), padding + (fw - up) // 2 - (k - up), padding + (fh + up - 1) // 2 - (k - 1), padding + (fh - up) // 2 - (k - up)]
+
+
+def noise_plane(noise):
+    """(the fp32 contiguous values, floats between two samples' planes) of a noise tensor as the kernels take it: [N, 1, Ho, Wo] per sample, or one shared
+    [Ho, Wo] plane (stride 0); (None, 0) without noise. A forward hands its argument over detached."""
+    if noise is None:
+        return None, 0
+    nz = noise.to(torch.float32).contiguous()
+    return nz, (nz.shape[-2] * nz.shape[-1] if nz.dim() == 4 else 0)
+
+
+def dnoise_of(rowsum, noise_info):
+    """the noise's gradient from the per-pixel sums over the channels (fp32 [N, Ho * Wo]): per sample, or summed over the batch for one shared plane;
+    noise_info: (dtype, shape) of the noise tensor"""
+    dtype, shape = noise_info
+    return (rowsum if len(shape) == 4 else rowsum.sum(dim=0)).reshape(shape).to(dtype)
+
+
+def _weight_image(w32, flipped, up, dtype, data_grad=False):
+    """the image the kernel reads, of dtype, from the fp32 weight [Cout, C, k, k] (flipped: its taps turned round). The forward's: [Cout][r][s][C]. The data
+    gradient's: [C][r][s][Cout], at up = 1 with the taps turned round once more ([C][2-r][2-s][Cout], a `same` convolution), at up = 2 as they are (`down2`:
+    gxs[h,w] = sum gu[2h+r, 2w+s] W[r,s])"""
+    weff = w32.flip(2, 3) if flipped else w32
+    if not data_grad:
+        return weff.permute(0, 2, 3, 1).contiguous().to(dtype)
+    return (weff.flip(2, 3) if up == 1 else weff).permute(1, 2, 3, 0).contiguous().to(dtype)
+
+
+def _fill_conv(c, x, wimg, Cout, k, mode):
+    """fills the sg_conv_fwd_desc c of a modulated-convolution launch and allocates its NHWC result. x: dense [N,Hs,Ws,C] NHWC; wimg: [Cout][k*k*C] of x.dtype.
+    mode 'same' (stride 1, pad k//2), 'up2' (transposed stride-2 gather, [N,2Hs+1,2Ws+1,Cout]) or 'down2' (plain stride 2, pad 0)."""
     N, Hs, Ws, C = x.shape
-    d = L.ModConvDesc()
-    c = d.conv
     c.dtype = L.dt(x)
     c.N, c.Hs, c.Ws, c.C, c.ldx = N, Hs, Ws, C, C
     c.R = c.S = k
@@ -75,10 +119,29 @@ def _modconv_raw(x, wimg, Cout, k, mode, pre=None, post=None, noise=None, noise_
     c.epi_flags, c.alpha, c.beta = 0, 1.0, 1.0
     out = torch.empty((N, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
     c.x, c.w, c.out, c.ldo = L.ptr(x), L.ptr(wimg), L.ptr(out), Cout
+    return out
+
+
+def _modconv_raw(x, wimg, Cout, k, mode, pre=None, post=None, noise=None, noise_stride=0):
+    """one sg_modconv2d_fwd launch; x, wimg and mode as _fill_conv takes them. Returns the NHWC result."""
+    d = L.ModConvDesc()
+    out = _fill_conv(d.conv, x, wimg, Cout, k, mode)
     d.pre, d.post, d.noise, d.noise_stride = L.ptr(pre), L.ptr(post), L.ptr(noise), noise_stride
     if L.lib().sg_modconv2d_ok(L.C.byref(d)) != 1:
         raise RuntimeError("modulated_conv2d: sg_modconv2d_ok refused the problem (there is no other path)")
     L.call("sg_modconv2d_fwd", d, L.stream())
+    return out
+
+
+def _jvp_raw(xh, vxh, wimg, Cout, k, mode, s32, vs32, post, y, e, noise, noise_stride):
+    """one sg_modconv2d_jvp launch: post * K(W)[s vx + vs x] + e (y - noise), the forward's tangent along (vx, vs); geometry as _modconv_raw"""
+    j = L.ModConvJvpDesc()
+    out = _fill_conv(j.m.conv, xh, wimg, Cout, k, mode)
+    j.m.pre, j.m.post, j.m.noise, j.m.noise_stride = L.ptr(s32), L.ptr(post), L.ptr(noise), noise_stride
+    j.vx, j.vs, j.y, j.e, j.ldy = L.ptr(vxh), L.ptr(vs32), L.ptr(y), L.ptr(e), Cout
+    if L.lib().sg_modconv2d_jvp_ok(L.C.byref(j)) != 1:
+        raise RuntimeError("modulated_conv2d: sg_modconv2d_jvp_ok refused the problem (there is no other path)")
+    L.call("sg_modconv2d_jvp", j, L.stream())
     return out
 
 
@@ -94,6 +157,14 @@ def _reduce_raw(a, b=None, rowsub=None, rowsub_stride=0, scale=None, want_rowsum
     L.call("sg_modconv_reduce", L.dt(a), L.ptr(a), L.ptr(b), L.ptr(rowsub), rowsub_stride, L.ptr(scale), L.ptr(out), L.ptr(part), L.ptr(rowsum),
            N, P, C, C, C, L.stream())
     return out, (part.sum(dim=1) if part is not None else None), rowsum
+
+
+# what a forward leaves for its backward. noise_info: None, or (dtype, shape) of the noise tensor; noise_stride: of the saved plane nz (noise_plane)
+_Cfg = collections.namedtuple("_Cfg", "up demodulate flipped k w_dtype s_dtype noise_info noise_stride")
+# the saved tensors the first-order backward reads, in the order they are saved and handed to _ModConvGradFn; the graph's own x, weight and styles follow
+# them. post = g d (dco when there is no post_gain): what scales gy; d alone stays in gd d^3
+_Saved = collections.namedtuple("_Saved", "xh w32 s32 Q dco y nz post")
+_N_SAVED = len(_Saved._fields)
 
 
 class _ModConvFn(torch.autograd.Function):
@@ -116,26 +187,21 @@ class _ModConvFn(torch.autograd.Function):
         # taps of the image the kernel reads: correlation at up = 1, the gather of the transposed convolution at up = 2 (conv2d_resample.py:124 passes
         # `not flip_weight` on, and conv_transpose2d scatters with the taps as given)
         flipped = (k > 1) and ((up == 1) != bool(flip_weight))
-        weff = w32.flip(2, 3) if flipped else w32
-        wimg = weff.permute(0, 2, 3, 1).contiguous().to(x.dtype)         # [Cout][r][s][C]
-        nz, nstride = None, 0
-        if noise is not None:
-            nz = noise.detach().to(torch.float32).contiguous()
-            nstride = H * W if nz.dim() == 4 else 0
+        nz, nstride = noise_plane(None if noise is None else noise.detach())
         post = dco
         if post_gain is not None:
             g = post_gain.detach().to(torch.float32).reshape(1, 1)
             post = dco * g if demodulate else g.expand(N, Cout).contiguous()
-        y = _modconv_raw(xh, wimg, Cout, k, "same" if up == 1 else "up2", pre=s32, post=post, noise=nz, noise_stride=nstride)
-        ctx.save_for_backward(xh, w32, s32, Q, dco, y, nz, post, x, weight, styles)     # (the last three: the graph's own tensors, for the second-order route)
-        ctx.cfg = (up, demodulate, flipped, k, weight.dtype, styles.dtype, None if noise is None else (noise.dtype, tuple(noise.shape)))
+        y = _modconv_raw(xh, _weight_image(w32, flipped, up, x.dtype), Cout, k, "same" if up == 1 else "up2", pre=s32, post=post, noise=nz, noise_stride=nstride)
+        ctx.save_for_backward(*_Saved(xh, w32, s32, Q, dco, y, nz, post), x, weight, styles)     # (the last three: for the second-order route)
+        ctx.cfg = _Cfg(up, demodulate, flipped, k, weight.dtype, styles.dtype, None if noise is None else (noise.dtype, tuple(noise.shape)), nstride)
         return y.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, gy):
         differentiable = _first_order_only("modulated_conv2d")
-        saved, (x, weight, styles) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
-        need_noise = saved[6] is not None and ctx.needs_input_grad[3]
+        saved, (x, weight, styles) = _Saved(*ctx.saved_tensors[:_N_SAVED]), ctx.saved_tensors[_N_SAVED:]
+        need_noise = saved.nz is not None and ctx.needs_input_grad[3]
         if differentiable:
             # inside second_order(generator=True): the same launches, recorded as a grad-function with a backward of its own. The weight gradient only where
             # the running graph task wants it (path-length regularisation asks for the latents' alone, as the reference's no_weight_gradients does).
@@ -146,13 +212,14 @@ class _ModConvFn(torch.autograd.Function):
         return dx, dw, ds, dn, None, None, None, None
 
 
-def _data_grad(gyh, weff, pre, up, k, C, T):
+def _data_grad(gyh, w32, pre, cfg, C):
     """K^T[pre * gy]: the unscaled data gradient through the same kernel (pre rides on gy as its pre-scale: fp32 product, one rounding)"""
-    if up == 1:
-        wd = weff.flip(2, 3).permute(1, 2, 3, 0).contiguous().to(T)          # [C][2-r][2-s][Cout]
-        return _modconv_raw(gyh, wd, C, k, "same", pre=pre)
-    wd = weff.permute(1, 2, 3, 0).contiguous().to(T)                         # [C][r][s][Cout]: gxs[h,w] = sum gu[2h+r, 2w+s] W[r,s]
-    return _modconv_raw(gyh, wd, C, k, "down2", pre=pre)
+    return _modconv_raw(gyh, _weight_image(w32, cfg.flipped, cfg.up, gyh.dtype, data_grad=True), C, cfg.k, "same" if cfg.up == 1 else "down2", pre=pre)
+
+
+def _tangent_operand(xh, vxh, s32, vs32):
+    """s vx + vs x, materialised: what the composition convolves and what the weight-gradient kernel takes"""
+    return _reduce_raw(vxh, scale=s32)[0] + _reduce_raw(xh, scale=vs32)[0]
 
 
 def _wgrad_into(dwi, operand, gu, up, k, C, Cout, H, W):
@@ -173,69 +240,37 @@ def _wgrad_as_weight(dwi, up, flipped):
     return dw.flip(2, 3) if flipped else dw
 
 
-def _first_order(saved, cfg, gy, need_w, need_noise):
-    """the operator's first-order backward: (dx NCHW view, dw, ds, dnoise, what a second-order pass keeps)"""
-    xh, w32, s32, Q, dco, y, nz, post = saved       # post = g d (dco when there is no post_gain): what scales gy; d alone stays in gd d^3
-    up, demodulate, flipped, k, w_dtype, s_dtype, noise_info = cfg
-    N, H, W, C = xh.shape
-    Cout = w32.shape[0]
-    T = xh.dtype
-    gyh = gy.to(T).permute(0, 2, 3, 1).contiguous()
-    weff = w32.flip(2, 3) if flipped else w32
+def _first_order(sv, cfg, gy, need_w, need_noise):
+    """the operator's first-order backward from the saved tensors sv (_Saved): (dx NCHW view, dw, ds, dnoise, what a second-order pass keeps)"""
+    N, H, W, C = sv.xh.shape
+    Cout = sv.w32.shape[0]
+    gyh = gy.to(sv.xh.dtype).permute(0, 2, 3, 1).contiguous()
     # gu = d gy, d gd = sum_p gy (y - noise), dnoise = sum_o gy: one pass over gy and y
     gu, dgd, gnoise = gyh, None, None
-    if demodulate:
-        gu, dgd, gnoise = _reduce_raw(gyh, b=y, rowsub=nz, rowsub_stride=(H * W if (nz is not None and nz.dim() == 4) else 0), scale=post,
-                                      want_rowsum=need_noise)
-    elif post is not None:
-        gu, _, gnoise = _reduce_raw(gyh, scale=post, want_rowsum=need_noise)
+    if cfg.demodulate:
+        gu, dgd, gnoise = _reduce_raw(gyh, b=sv.y, rowsub=sv.nz, rowsub_stride=cfg.noise_stride, scale=sv.post, want_rowsum=need_noise)
+    elif sv.post is not None:
+        gu, _, gnoise = _reduce_raw(gyh, scale=sv.post, want_rowsum=need_noise)
     elif need_noise:
         _, _, gnoise = _reduce_raw(gyh, want_rowsum=True)
     # unscaled data gradient through the same kernel (d rides on gy as its pre-scale: fp32 product, one rounding), then dx = s gxs, sum_p x gxs
-    gxs = _data_grad(gyh, weff, post, up, k, C, T)
-    dx, ds, _ = _reduce_raw(gxs, b=xh, scale=s32)
+    gxs = _data_grad(gyh, sv.w32, sv.post, cfg, C)
+    dx, ds, _ = _reduce_raw(gxs, b=sv.xh, scale=sv.s32)
     t = None
-    if demodulate:
-        t = dgd * dco * dco                                                  # gd d^3
-        ds = ds - s32 * (t @ Q)
+    if cfg.demodulate:
+        t = dgd * sv.dco * sv.dco                                            # gd d^3
+        ds = ds - sv.s32 * (t @ sv.Q)
     dw = None
     if need_w:
-        xs, _, _ = _reduce_raw(xh, scale=s32)                                # s x, materialised for the weight-gradient kernel
-        dwi = _wgrad_image(up, k, C, Cout, xh.device)
-        _wgrad_into(dwi, xs, gu, up, k, C, Cout, H, W)
-        dw = _wgrad_as_weight(dwi, up, flipped)
-        if demodulate:
-            dw = dw - w32 * (t.t() @ (s32 * s32))[:, :, None, None]
-        dw = dw.to(w_dtype)
-    dn = None
-    if need_noise:
-        dn = gnoise.reshape(N, 1, H, W) if len(noise_info[1]) == 4 else gnoise.sum(dim=0).reshape(H, W)
-        dn = dn.to(noise_info[0])
-    return dx.permute(0, 3, 1, 2), dw, ds.to(s_dtype), dn, (gyh, gu, dgd, gxs)
-
-
-def _jvp_raw(xh, vxh, wimg, Cout, k, mode, s32, vs32, post, y, e, noise, noise_stride):
-    """one sg_modconv2d_jvp launch: post * K(W)[s vx + vs x] + e (y - noise), the forward's tangent along (vx, vs); geometry as _modconv_raw"""
-    N, Hs, Ws, C = xh.shape
-    j = L.ModConvJvpDesc()
-    c = j.m.conv
-    c.dtype = L.dt(xh)
-    c.N, c.Hs, c.Ws, c.C, c.ldx = N, Hs, Ws, C, C
-    c.R = c.S = k
-    if mode == "same":
-        Ho, Wo, c.stride, c.pad_h, c.pad_w, c.pix_flags = Hs, Ws, 1, k // 2, k // 2, 0
-    else:
-        Ho, Wo, c.stride, c.pad_h, c.pad_w, c.pix_flags = 2 * Hs + 1, 2 * Ws + 1, 2, 0, 0, L.PIX_TRANSPOSED
-    c.Ho, c.Wo, c.Cout = Ho, Wo, Cout
-    c.epi_flags, c.alpha, c.beta = 0, 1.0, 1.0
-    out = torch.empty((N, Ho, Wo, Cout), dtype=xh.dtype, device=xh.device)
-    c.x, c.w, c.out, c.ldo = L.ptr(xh), L.ptr(wimg), L.ptr(out), Cout
-    j.m.pre, j.m.post, j.m.noise, j.m.noise_stride = L.ptr(s32), L.ptr(post), L.ptr(noise), noise_stride
-    j.vx, j.vs, j.y, j.e, j.ldy = L.ptr(vxh), L.ptr(vs32), L.ptr(y), L.ptr(e), Cout
-    if L.lib().sg_modconv2d_jvp_ok(L.C.byref(j)) != 1:
-        raise RuntimeError("modulated_conv2d: sg_modconv2d_jvp_ok refused the problem (there is no other path)")
-    L.call("sg_modconv2d_jvp", j, L.stream())
-    return out
+        xs, _, _ = _reduce_raw(sv.xh, scale=sv.s32)                          # s x, materialised for the weight-gradient kernel
+        dwi = _wgrad_image(cfg.up, cfg.k, C, Cout, sv.xh.device)
+        _wgrad_into(dwi, xs, gu, cfg.up, cfg.k, C, Cout, H, W)
+        dw = _wgrad_as_weight(dwi, cfg.up, cfg.flipped)
+        if cfg.demodulate:
+            dw = dw - sv.w32 * (t.t() @ (sv.s32 * sv.s32))[:, :, None, None]
+        dw = dw.to(cfg.w_dtype)
+    dn = dnoise_of(gnoise, cfg.noise_info) if need_noise else None
+    return dx.permute(0, 3, 1, 2), dw, ds.to(cfg.s_dtype), dn, (gyh, gu, dgd, gxs)
 
 
 # Which route the tangent d_gy takes. One sg_modconv2d_jvp launch where it does not lose to the composition it replaces (operand combine, sg_modconv2d_fwd,
@@ -265,8 +300,8 @@ class _ModConvGradFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, gy, x, weight, styles, cfg, want_w, want_noise, *saved):
-        dx, dw, ds, dn, (gyh, gu, dgd, gxs) = _first_order(saved, cfg, gy, want_w, want_noise)
-        ctx.save_for_backward(*saved, gyh, gu, dgd, gxs)
+        dx, dw, ds, dn, kept = _first_order(_Saved(*saved), cfg, gy, want_w, want_noise)
+        ctx.save_for_backward(*saved, *kept)
         ctx.cfg, ctx.gy_dtype, ctx.x_dtype = cfg, gy.dtype, x.dtype
         ctx.set_materialize_grads(False)
         return dx, dw, ds, dn
@@ -277,40 +312,40 @@ class _ModConvGradFn(torch.autograd.Function):
         if vw is not None or vn is not None:
             raise NotImplementedError("modulated_conv2d: a second-order pass with a cotangent on the weight's or the noise's gradient is not supported "
                                       "(path-length regularisation differentiates the gradient for the latents alone)")
-        xh, w32, s32, Q, dco, y, nz, post, gyh, gu, dgd, gxs = ctx.saved_tensors
-        up, demodulate, flipped, k, w_dtype, s_dtype, noise_info = ctx.cfg
+        sv, (gyh, gu, dgd, gxs) = _Saved(*ctx.saved_tensors[:_N_SAVED]), ctx.saved_tensors[_N_SAVED:]
+        xh, w32, s32, Q, dco, post, cfg = sv.xh, sv.w32, sv.s32, sv.Q, sv.dco, sv.post, ctx.cfg
+        up, k, demodulate = cfg.up, cfg.k, cfg.demodulate
         N, H, W, C = xh.shape
         Cout = w32.shape[0]
         T = xh.dtype
+        no_grads = (None,) * (3 + _N_SAVED)      # cfg, want_w, want_noise and the saved tensors of forward's signature
         vxh = torch.zeros_like(xh) if vx is None else vx.to(T).permute(0, 2, 3, 1).contiguous()
         vs32 = torch.zeros_like(s32) if vs is None else vs.to(torch.float32).contiguous()
-        weff = w32.flip(2, 3) if flipped else w32
-        wimg = weff.permute(0, 2, 3, 1).contiguous().to(T)
+        wimg = _weight_image(w32, cfg.flipped, up, T)
         r = e = None
         if demodulate:
             r = (s32 * vs32) @ Q.t()
             e = -(dco * dco) * r
         operand = None
         if tangent_fused(T, up):
-            nstride = H * W if (nz is not None and nz.dim() == 4) else 0
-            ydot = _jvp_raw(xh, vxh, wimg, Cout, k, "same" if up == 1 else "up2", s32, vs32, post, y, e, nz, nstride)
+            ydot = _jvp_raw(xh, vxh, wimg, Cout, k, "same" if up == 1 else "up2", s32, vs32, post, sv.y, e, sv.nz, cfg.noise_stride)
         else:       # the composition: the operand materialised (the weight's gradient below takes it too), the forward launch, one multiply-add with y
-            operand = _reduce_raw(vxh, scale=s32)[0] + _reduce_raw(xh, scale=vs32)[0]
+            operand = _tangent_operand(xh, vxh, s32, vs32)
             ydot = _modconv_raw(operand, wimg, Cout, k, "same" if up == 1 else "up2", post=post)
             if demodulate:
-                u = y if nz is None else y - nz.reshape(-1, H, W, 1).to(T)
+                u = sv.y if sv.nz is None else sv.y - sv.nz.reshape(-1, H, W, 1).to(T)
                 ydot = torch.addcmul(ydot, e.to(T)[:, None, None, :], u)
         d_gy = ydot.permute(0, 3, 1, 2).to(ctx.gy_dtype) if ctx.needs_input_grad[0] else None
         need_x, need_w, need_s = ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         if not (need_x or need_w or need_s):
-            return (d_gy, None, None, None) + (None,) * 11
+            return (d_gy, None, None, None) + no_grads
         # d_x and the pixel sums of d_s: G with the cotangents, then G' through the data-gradient route with the pre-table g d' = post e
         vsG, sum_vxG, _ = _reduce_raw(gxs, b=vxh, scale=vs32)
         d_x, d_s = vsG, sum_vxG
         poste = None
         if demodulate:
             poste = post * e                                                    # g d'
-            g2 = _data_grad(gyh, weff, poste, up, k, C, T)
+            g2 = _data_grad(gyh, w32, poste, cfg, C)
             sG2, sum_xG2, _ = _reduce_raw(g2, b=xh, scale=s32)
             d_x = d_x + sG2
             _, s1, _ = _reduce_raw(gyh, b=ydot)                                 # sum_p gy y'
@@ -320,18 +355,18 @@ class _ModConvGradFn(torch.autograd.Function):
         d_w = None
         if need_w:
             if operand is None:
-                operand = _reduce_raw(vxh, scale=s32)[0] + _reduce_raw(xh, scale=vs32)[0]      # s vx + vs x, materialised for the weight-gradient kernel
+                operand = _tangent_operand(xh, vxh, s32, vs32)
             dwi = _wgrad_image(up, k, C, Cout, xh.device)
             _wgrad_into(dwi, operand, gu, up, k, C, Cout, H, W)
             if demodulate:
                 xs, _, _ = _reduce_raw(xh, scale=s32)
                 gue, _, _ = _reduce_raw(gyh, scale=poste)                       # g d' gy
                 _wgrad_into(dwi, xs, gue, up, k, C, Cout, H, W)
-            d_w = _wgrad_as_weight(dwi, up, flipped)
+            d_w = _wgrad_as_weight(dwi, up, cfg.flipped)
             if demodulate:
                 d_w = d_w + w32 * (t1.t() @ (s32 * s32) - 2.0 * (t2.t() @ (s32 * vs32)))[:, :, None, None]
-            d_w = d_w.to(w_dtype)
-        return (d_gy, d_x.permute(0, 3, 1, 2) if need_x else None, d_w, d_s.to(s_dtype) if need_s else None) + (None,) * 11
+            d_w = d_w.to(cfg.w_dtype)
+        return (d_gy, d_x.permute(0, 3, 1, 2) if need_x else None, d_w, d_s.to(cfg.s_dtype) if need_s else None) + no_grads
 
 
 def modulated_conv2d(x, weight, styles, noise=None, up=1, down=1, padding=0, resample_filter=None, demodulate=True, flip_weight=True, fused_modconv=True):
@@ -347,10 +382,7 @@ def modulated_conv2d(x, weight, styles, noise=None, up=1, down=1, padding=0, res
         return _ModConvFn.apply(x, weight, styles, noise, 1, bool(demodulate), bool(flip_weight))
     # d commutes with the per-channel FIR, so it stays in the kernel's epilogue; the noise comes after the FIR
     core = _ModConvFn.apply(x, weight, styles, None, 2, bool(demodulate), bool(flip_weight))
-    fw, fh = _upfirdn2d._get_filter_size(resample_filter)
-    px0, px1, py0, py1 = (padding + (fw + up - 1) // 2 - (k - 1), padding + (fw - up) // 2 - (k - up),
-                          padding + (fh + up - 1) // 2 - (k - 1), padding + (fh - up) // 2 - (k - up))
-    y = _upfirdn2d.upfirdn2d(core, resample_filter, padding=[px0, px1, py0, py1], gain=up ** 2)
+    y = _upfirdn2d.upfirdn2d(core, resample_filter, padding=_up2_fir_padding(padding, k, resample_filter), gain=up ** 2)
     if noise is not None:
         y = y + noise.to(y.dtype)
     return y.contiguous(memory_format=torch.channels_last)
@@ -376,5 +408,5 @@ def modulated_conv2d_act(x, weight, styles, noise=None, up=1, down=1, padding=0,
         y = _ModConvFn.apply(x, weight, styles, noise, 1, bool(demodulate), bool(flip_weight))
         return bias_act(y, None if bias is None else bias.to(y.dtype), act=act, gain=gain, clamp=clamp)
     core = _ModConvFn.apply(x, weight, styles, None, 2, bool(demodulate), bool(flip_weight))
-    pad = [padding + (fw + up - 1) // 2 - (k - 1), padding + (fw - up) // 2 - (k - up), padding + (fh + up - 1) // 2 - (k - 1), padding + (fh - up) // 2 - (k - up)]
-    return fir_bias_act(core, resample_filter, pad, noise=noise, bias=bias, act=act, gain=gain, clamp=clamp, filter_gain=up ** 2)
+    return fir_bias_act(core, resample_filter, _up2_fir_padding(padding, k, resample_filter), noise=noise, bias=bias, act=act, gain=gain, clamp=clamp,
+                        filter_gain=up ** 2)

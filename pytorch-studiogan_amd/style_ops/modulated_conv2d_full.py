@@ -12,30 +12,21 @@ import torch
 import torch.nn.functional as F
 
 from .. import _lib as L
-from .modulated_conv2d import _ModConvFn
+from .modulated_conv2d import _ModConvFn, _validate_kernel, _validate_operands
 
 
 def modulated_conv2d(x, w, s, demodulate=True, padding=0, input_gain=None):
     """The reference's signature. x: [N, I, H, W] float32 or bfloat16; w: [O, I, k, k], k = 1 or 3; s: [N, I]; padding: k - 1; input_gain: None or a scalar
     tensor (a per-channel or per-sample gain is refused: the networks pass magnitude_ema.rsqrt()). The result is channels_last."""
-    if not (isinstance(x, torch.Tensor) and x.dim() == 4 and isinstance(w, torch.Tensor) and w.dim() == 4):
-        raise AssertionError("modulated_conv2d (full): x must be [N, I, H, W] and w [O, I, k, k]")
-    N, C, H, W = x.shape
-    Cout, Cw, kh, kw = w.shape
-    if Cw != C or not (isinstance(s, torch.Tensor) and tuple(s.shape) == (N, C)):
-        raise AssertionError("modulated_conv2d (full): w [O, I, k, k], x [N, I, H, W] and s [N, I] do not agree")
-    if x.dtype not in (torch.float32, torch.bfloat16):
-        raise NotImplementedError(f"modulated_conv2d (full): x of dtype {x.dtype} is not supported (float32 / bfloat16)")
-    if kh != kw or kh not in (1, 3):
-        raise NotImplementedError(f"modulated_conv2d (full): a {kh} x {kw} kernel is not supported (square 1 x 1 or 3 x 3)")
-    if padding != kh - 1:
-        raise NotImplementedError(f"modulated_conv2d (full): padding={padding} is not supported (padding = kernel_size - 1 = {kh - 1})")
+    k = _validate_kernel("modulated_conv2d (full)", *_validate_operands("modulated_conv2d (full)", x, w, s)[-2:])
+    if padding != k - 1:
+        raise NotImplementedError(f"modulated_conv2d (full): padding={padding} is not supported (padding = kernel_size - 1 = {k - 1})")
     if input_gain is not None and not (isinstance(input_gain, torch.Tensor) and input_gain.numel() == 1):
         raise NotImplementedError("modulated_conv2d (full): input_gain must be a scalar tensor")
     L.require_gpu(x.device)
     if demodulate:
         w = w * w.square().mean([1, 2, 3], keepdim=True).rsqrt()
         s = s * s.square().mean().rsqrt()
-    if kh == 3:
+    if k == 3:
         x = F.pad(x, [1, 1, 1, 1])
     return _ModConvFn.apply(x, w, s, None, 1, bool(demodulate), True, input_gain)

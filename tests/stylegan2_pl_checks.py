@@ -15,8 +15,10 @@ from util import check
 
 CL = torch.channels_last
 # the seven operator geometries of tests/modconv_ref.py, and one whose 72 output channels take the engine's 96-row tile in fp32 (bf16 has no such tangent
-# instantiation and runs it as a ragged 128-row tile)
-OP_CASES = dict(R.OP_CASES, h=(2, 16, 72, 6, 3, 1, True, "sample", True))
+# instantiation and runs it as a ragged 128-row tile). i, j: 6 input channels, no multiple of the 16-byte vector in either dtype, so the operand policy's
+# wrap-around table read runs (more than once per chunk in bf16, 6 < 8): i at up = 1 with 36 output channels (the 128 x 128 tile, ragged) on an odd map, j
+# at up = 2 through the transposed gather and the stride-2 data gradient, per-sample noise. (Appended: the seeds are 6100 + index.)
+OP_CASES = dict(R.OP_CASES, h=(2, 16, 72, 6, 3, 1, True, "sample", True), i=(2, 6, 36, 5, 3, 1, True, "shared", True), j=(2, 6, 8, 4, 3, 2, True, "sample", False))
 MODCONV_CASES = list(OP_CASES)
 TAIL_EPI = {      # the fused tail's epilogues: (act, gain, clamp)
     "lrelu": ("lrelu", S.SQRT2, None),
