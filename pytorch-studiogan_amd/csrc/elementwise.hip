@@ -411,7 +411,7 @@ template <typename T> __global__ __launch_bounds__(256) void k_colsum_stream(con
   float acc[V];
 #pragma unroll
   for (int e = 0; e < V; e++) acc[e] = 0.f;
-  long long r = r0 + pl;                                    // four loads in flight per lane (norm.hip, k_bn_apply_stream); same summation order
+  long long r = r0 + pl;                                    // four loads in flight per lane (norm.hip, bn_walk); same summation order
   for (; r + 3ll * lanes_p < r1; r += 4ll * lanes_p) {
     u32x4 raw[4];
 #pragma unroll

@@ -13,6 +13,7 @@ extern "C" long long sg_bn_path_launches(int path) {
   if (path < 0 || path >= SG_BN_PATH_COUNT) return -1;
   return __atomic_load_n(&g_bn_path_launches[path], __ATOMIC_RELAXED);
 }
+static inline double elem_bytes(int dtype) { return dtype == SG_DTYPE_BF16 ? 2.0 : 4.0; }
 
 // The arithmetic that the kernels of one entry point, and the forward and the backward of one layer, have to share BIT FOR BIT, written once with the fused
 // multiply-adds spelled out and no contraction beyond them. Left to the compiler, a * b + c was fused in one instantiation and not in another (in the bf16
@@ -35,6 +36,118 @@ __device__ __forceinline__ float bn_add(float a, float b) {
 #pragma clang fp contract(off)
   return a + b;
 }
+// The fused ReLU's gate: does the element pass. THE predicate of every backward's mask; the forward clamps with fmaxf(bn_pre, 0), which is 0 exactly where
+// the gate is shut (a NaN pre-activation included)
+__device__ __forceinline__ bool bn_gate(int relu, float xh, float ga, float bi) { return !(relu && !(bn_pre(xh, ga, bi) > 0.f)); }
+// mean / invstd / gain / bias of the V channels from c0 on, for sample n: a null gain is 1, a null bias 0, rows of pitch gsn (0: one row for every sample);
+// with k0 / k1, also the batch-statistics terms of bn_dx
+template <int V> __device__ __forceinline__ void bn_coef(const float* mean, const float* invstd, const float* gain, const float* bias, int gsn, int n, int c0, float* mu, float* is, float* ga, float* bi,
+                                                         const double* chan = nullptr, int use_batch = 0, float* k0 = nullptr, float* k1 = nullptr) {
+#pragma unroll
+  for (int e = 0; e < V; e++) {
+    const int c = c0 + e;
+    mu[e] = mean[c]; is[e] = invstd[c];
+    ga[e] = gain ? gain[(long long)n * gsn + c] : 1.f;
+    bi[e] = bias ? bias[(long long)n * gsn + c] : 0.f;
+    if (k0) {
+      k0[e] = use_batch ? (float)chan[2 * c] : 0.f;
+      k1[e] = use_batch ? (float)chan[2 * c + 1] : 0.f;
+    }
+  }
+}
+// the per-element bodies, one per stage, on the V channels a thread holds. Forward: xv -> relu(gain xhat + bias)
+template <int V> __device__ __forceinline__ void bn_apply_elems(float* xv, const float* mu, const float* is, const float* ga, const float* bi, int relu) {
+#pragma unroll
+  for (int e = 0; e < V; e++) {
+    float v = bn_pre(bn_xhat(xv[e], mu[e], is[e]), ga[e], bi[e]);   // the same evaluation as the backward's recomputation
+    if (relu) v = fmaxf(v, 0.f);
+    xv[e] = v;
+  }
+}
+// backward stage 1: s1 += dy', s2 += dy' xhat with dy' = dy behind the gate
+template <int V> __device__ __forceinline__ void bn_bwd_sum_elems(const float* xv, const float* gv, const float* mu, const float* is, const float* ga, const float* bi, int relu, float* s1, float* s2) {
+#pragma unroll
+  for (int e = 0; e < V; e++) {
+    const float xh = bn_xhat(xv[e], mu[e], is[e]);
+    float g = gv[e];
+    if (!bn_gate(relu, xh, ga[e], bi[e])) g = 0.f;
+    s1[e] += g; s2[e] += g * xh;
+  }
+}
+// backward stage 3: xv -> dx (bn_dx) [+ the V elements at res, the gradient the same input received through a residual block's skip path; null: none]
+template <typename T, int V> __device__ __forceinline__ void bn_bwd_apply_elems(float* xv, const float* gv, const T* res, const float* mu, const float* is, const float* ga, const float* bi, const float* k0, const float* k1, float invc, int relu, int use_batch) {
+#pragma unroll
+  for (int e = 0; e < V; e++) {
+    const float xh = bn_xhat(xv[e], mu[e], is[e]);
+    float g = gv[e];
+    if (!bn_gate(relu, xh, ga[e], bi[e])) g = 0.f;
+    xv[e] = bn_dx(g, xh, ga[e], is[e], k0[e], k1[e], invc, use_batch);
+  }
+  if (res) {
+    float rv[V];
+    load_f<T, V>(res, rv);
+#pragma unroll
+    for (int e = 0; e < V; e++) xv[e] = bn_add(xv[e], rv[e]);
+  }
+}
+// Column reduce of a (64 channels x 4 row phases) block: every thread stores its K accumulators into sm[K][4][64] (declared by the kernel), and after the
+// barrier row phase 0 combines the four of a channel, left to right or PAIRWISE (a + b) + (c + d), whichever the kernel has always had.
+template <int K, typename A> __device__ __forceinline__ void bn_col_store(A (&sm)[K][4][64], const A* s, int ry, int cx) {
+#pragma unroll
+  for (int k = 0; k < K; k++) sm[k][ry][cx] = s[k];
+  __syncthreads();
+}
+template <bool PAIRWISE, typename A> __device__ __forceinline__ A bn_col_sum(const A (&p)[4][64], int cx) {
+  return PAIRWISE ? (p[0][cx] + p[1][cx]) + (p[2][cx] + p[3][cx]) : p[0][cx] + p[1][cx] + p[2][cx] + p[3][cx];
+}
+__device__ __forceinline__ void bn_atomic_add(double* p, double v) { atomicAdd(p, v); }
+__device__ __forceinline__ void bn_atomic_add(float* p, float v) { unsafeAtomicAdd(p, v); }
+
+// Streaming ownership (grid (pixel chunks, N[, channel-vector tiles]); block = lanes_p pixel lanes x cvt channel vectors): thread -> its channel vector cv of
+// sample n = blockIdx.y, its pixel lane pl, the pixels [p0, p1) of its block and the element offset `base` of (n, pixel 0, channel cv * V)
+struct BnOwn { int cv, pl, lanes_p; long long p0, p1, base; };
+__device__ __forceinline__ BnOwn bn_own(int cv0, int cvt, int lanes_p, int V, long long HW, int C, int ppb) {
+  BnOwn w;
+  w.lanes_p = lanes_p;
+  w.cv = cv0 + threadIdx.x % cvt; w.pl = threadIdx.x / cvt;
+  w.p0 = (long long)blockIdx.x * ppb;
+  w.p1 = w.p0 + ppb; if (w.p1 > HW) w.p1 = HW;
+  w.base = (long long)blockIdx.y * HW * C + w.cv * V;
+  return w;
+}
+// The walk of a block's pixels by its lanes: UN pixels per trip, all UN x NIN 16-byte loads issued before the first use, then a one-pixel tail.
+// load(k, pix, unrolled) -> input k's vector at pix; body(r, pix) consumes the NIN vectors of one pixel. With one 16-byte load in flight per lane the 32 resident
+// waves of a CU hold 32 KB, which at ~2 us of HBM latency is 4.2 TB/s for the chip -- exactly what the r02 roofline_hbm leg measured for the batch-norm family
+// (0.53 of peak). Same arithmetic per element and same pixel order as a one-pixel walk, so results are unchanged.
+template <int UN, int NIN, typename Load, typename Body> __device__ __forceinline__ void bn_walk(const BnOwn& w, Load load, Body body) {
+  long long pix = w.p0 + w.pl;
+  for (; pix + (long long)(UN - 1) * w.lanes_p < w.p1; pix += (long long)UN * w.lanes_p) {
+    u32x4 r[UN][NIN];
+#pragma unroll
+    for (int i = 0; i < UN; i++)
+#pragma unroll
+      for (int k = 0; k < NIN; k++) r[i][k] = load(k, pix + (long long)i * w.lanes_p, true);
+#pragma unroll
+    for (int i = 0; i < UN; i++) body(r[i], pix + (long long)i * w.lanes_p);
+  }
+  for (; pix < w.p1; pix += w.lanes_p) {
+    u32x4 r[NIN];
+#pragma unroll
+    for (int k = 0; k < NIN; k++) r[k] = load(k, pix, false);
+    body(r, pix);
+  }
+}
+// The tail of a streaming reduce: the lanes' sums {s1, s2} of every channel meet in sm[lanes_p][C][2] (dynamic LDS), one atomic per channel, sum and block
+template <int V, typename A> __device__ __forceinline__ void bn_lane_combine(A* sm, const A* s1, const A* s2, int pl, int cv, int lanes_p, int C, A* out) {
+#pragma unroll
+  for (int e = 0; e < V; e++) { sm[((long long)pl * C + cv * V + e) * 2] = s1[e]; sm[((long long)pl * C + cv * V + e) * 2 + 1] = s2[e]; }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
+    A a = 0;
+    for (int l = 0; l < lanes_p; l++) a += sm[(long long)l * C * 2 + i];
+    bn_atomic_add(out + i, a);
+  }
+}
 
 // ---- statistics ------------------------------------------------------------------------------------------
 template <typename T> __global__ __launch_bounds__(256) void k_bn_partial(const T* x, int ldx, long long rows, int C, double* partial, long long rpb) {
@@ -42,18 +155,17 @@ template <typename T> __global__ __launch_bounds__(256) void k_bn_partial(const 
   const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + cx;
   long long r0 = blockIdx.y * rpb, r1 = r0 + rpb; if (r1 > rows) r1 = rows;
-  double s1 = 0.0, s2 = 0.0;
+  double s[2] = {0.0, 0.0};
   if (c < C) {
     for (long long r = r0 + ry; r < r1; r += 4) {
       const double v = (double)to_f<T>(x[r * ldx + c]);
-      s1 += v; s2 += v * v;
+      s[0] += v; s[1] += v * v;
     }
   }
-  sm[0][ry][cx] = s1; sm[1][ry][cx] = s2;
-  __syncthreads();
+  bn_col_store(sm, s, ry, cx);
   if (ry == 0 && c < C) {
-    atomicAdd(partial + 2 * c, sm[0][0][cx] + sm[0][1][cx] + sm[0][2][cx] + sm[0][3][cx]);
-    atomicAdd(partial + 2 * c + 1, sm[1][0][cx] + sm[1][1][cx] + sm[1][2][cx] + sm[1][3][cx]);
+#pragma unroll
+    for (int k = 0; k < 2; k++) bn_atomic_add(partial + 2 * c + k, bn_col_sum<false>(sm[k], cx));
   }
 }
 // Streaming variant: a thread owns one 16-byte channel vector and walks pixels (16-byte loads instead of 2-byte ones);
@@ -73,7 +185,7 @@ template <typename T> __global__ __launch_bounds__(256) void k_bn_partial_stream
     float s1[V], s2[V];
 #pragma unroll
     for (int e = 0; e < V; e++) { s1[e] = 0.f; s2[e] = 0.f; }
-    for (int k = 0; k < 32; k += 4) {                        // four loads in flight per lane (see k_bn_apply_stream); same summation order
+    for (int k = 0; k < 32; k += 4) {                        // four loads in flight per lane (see bn_walk); same summation order
       u32x4 raw[4];
 #pragma unroll
       for (int i = 0; i < 4; i++) {
@@ -92,17 +204,10 @@ template <typename T> __global__ __launch_bounds__(256) void k_bn_partial_stream
 #pragma unroll
     for (int e = 0; e < V; e++) { d1[e] += (double)s1[e]; d2[e] += (double)s2[e]; }
   }
-#pragma unroll
-  for (int e = 0; e < V; e++) { smd[((long long)pl * C + cv * V + e) * 2] = d1[e]; smd[((long long)pl * C + cv * V + e) * 2 + 1] = d2[e]; }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
-    double a = 0.0;
-    for (int l = 0; l < lanes_p; l++) a += smd[(long long)l * C * 2 + i];
-    atomicAdd(partial + i, a);
-  }
+  bn_lane_combine<V>(smd, d1, d2, pl, cv, lanes_p, C, partial);
 }
 extern "C" int sg_bn_partial_stats(int dtype, const void* x, int ldx, long long rows, int C, double* partial, sg_stream_t s) {
-  SgProfScope prof((hipStream_t)s, (double)rows * C * (dtype == SG_DTYPE_BF16 ? 2.0 : 4.0), 4);
+  SgProfScope prof((hipStream_t)s, (double)rows * C * elem_bytes(dtype), 4);
   SG_CHECK(x && partial && rows > 0 && C > 0, "sg_bn_partial_stats: bad args");
   bool done = false;
   DISPATCH_T(dtype, {
@@ -136,18 +241,17 @@ __global__ __launch_bounds__(256) void k_bn_stats_from_tiles(const float* stats,
   const int c = blockIdx.x * 64 + cx;
   int r0 = blockIdx.y * rpb, r1 = r0 + rpb;
   if (r1 > nrows) r1 = nrows;
-  double s1 = 0.0, s2 = 0.0;
+  double s[2] = {0.0, 0.0};
   if (c < C) {
     for (int r = r0 + ry; r < r1; r += 4) {
       const float2 v = *(const float2*)(stats + ((long long)r * C + c) * 2);
-      s1 += (double)v.x; s2 += (double)v.y;
+      s[0] += (double)v.x; s[1] += (double)v.y;
     }
   }
-  sm[0][ry][cx] = s1; sm[1][ry][cx] = s2;
-  __syncthreads();
+  bn_col_store(sm, s, ry, cx);
   if (ry == 0 && c < C) {
-    atomicAdd(partial + 2 * c, (sm[0][0][cx] + sm[0][1][cx]) + (sm[0][2][cx] + sm[0][3][cx]));
-    atomicAdd(partial + 2 * c + 1, (sm[1][0][cx] + sm[1][1][cx]) + (sm[1][2][cx] + sm[1][3][cx]));
+#pragma unroll
+    for (int k = 0; k < 2; k++) bn_atomic_add(partial + 2 * c + k, bn_col_sum<true>(sm[k], cx));
   }
 }
 extern "C" int sg_bn_stats_from_tiles(const float* stats, int nrows, int C, double* partial, sg_stream_t s) {
@@ -203,25 +307,33 @@ template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_bn_app
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int cv = (int)(i % CV); const long long pix = i / CV; const int n = (int)(pix / HW);
     const int c0 = cv * V;
-    float xv[V];
-    if (VECP) unpack16<T>(*(const u32x4*)(x + pix * C + c0), xv); else xv[0] = to_f<T>(x[pix * C + c0]);
-#pragma unroll
-    for (int e = 0; e < V; e++) {
-      const int c = c0 + e;
-      // the same evaluation as the backward's recomputation (bn_xhat, bn_pre)
-      const float xh = bn_xhat(xv[e], mean[c], invstd[c]);
-      const float ga = gain ? gain[(long long)n * gsn + c] : 1.f;
-      const float bi = bias ? bias[(long long)n * gsn + c] : 0.f;
-      float v = bn_pre(xh, ga, bi);
-      if (relu) v = fmaxf(v, 0.f);
-      xv[e] = v;
-    }
-    if (VECP) *(u32x4*)(y + pix * C + c0) = pack16<T>(xv); else y[pix * C + c0] = from_f<T>(xv[0]);
+    float xv[V], mu[V], is[V], ga[V], bi[V];
+    load_f<T, V>(x + pix * C + c0, xv);
+    bn_coef<V>(mean, invstd, gain, bias, gsn, n, c0, mu, is, ga, bi);
+    bn_apply_elems<V>(xv, mu, is, ga, bi, relu);
+    *(vec_t<T, V>*)(y + pix * C + c0) = pack_f<T, V>(xv);
   }
 }
 static inline int grid_for(long long total) { long long b = (total + 255) / 256; if (b > 256 * 32) b = 256 * 32; if (b < 1) b = 1; return (int)b; }
 template <typename T> static bool vec_ok(const void* a, const void* b, int C) {
   return (C % ET<T>::VEC == 0) && ((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0;
+}
+// a call takes its streaming kernel: 16-byte operands (`vec`), a sample's channel vectors within one block, the batch within grid.y, at least 16 pixels
+// (HW 64 -> 16: the 4 x 4 maps of a generator's first block took the generic kernel at 0.56 TB/s, 45 us for 25 MB)
+template <typename T> static bool bn_streams(bool vec, int N, long long HW, int C) { return vec && C / ET<T>::VEC <= 256 && N <= 65535 && HW >= 16; }
+// streaming geometry: `want` workgroups over `slabs` (samples [x channel-vector tiles]) -> pixels per block, at least `floor_pix` per lane; returns grid.x
+static inline int bn_stream_geom(long long HW, long long slabs, int lanes_p, long long want, int floor_pix, int* ppb) {
+  long long chunks = want / slabs; if (chunks < 1) chunks = 1;
+  long long p = (HW + chunks - 1) / chunks; if (p < floor_pix * lanes_p) p = floor_pix * lanes_p;
+  *ppb = (int)p;
+  return (int)((HW + p - 1) / p);
+}
+// grid (channel tiles, row groups, N) of the generic per-sample reduces (64 channels x 4 row phases per block): about 2048 blocks, at least 16 rows per block
+static inline dim3 bn_col_grid(int N, long long HW, int C, long long* rpb) {
+  const int ct = (C + 63) / 64;
+  long long want = 2048 / ((long long)ct * N); if (want < 1) want = 1;
+  *rpb = (HW + want - 1) / want; if (*rpb < 16) *rpb = 16;
+  return dim3(ct, (int)((HW + *rpb - 1) / *rpb), N);
 }
 // Streaming variant: grid (pixel chunks, N). A thread owns ONE 16-byte channel vector of ONE sample, so its
 // scale/shift (8 or 4 channels) are computed once and the loop body is load -> fma -> store (the generic kernel
@@ -229,45 +341,20 @@ template <typename T> static bool vec_ok(const void* a, const void* b, int C) {
 template <typename T, int UN, bool NT> __global__ __launch_bounds__(256) void k_bn_apply_stream(const T* x, T* y, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, int gsn, int relu, int ppb) {
   constexpr int V = ET<T>::VEC;
   const int CV = C / V;
-  const int n = blockIdx.y;
-  const int lanes_p = blockDim.x / CV;                // pixels per block iteration (blockDim.x == CV * lanes_p)
-  const int cv = threadIdx.x % CV, pl = threadIdx.x / CV;
+  const BnOwn w = bn_own(0, CV, blockDim.x / CV, V, HW, C, ppb);      // blockDim.x == CV * lanes_p
   float mu[V], is[V], ga[V], bi[V];
-#pragma unroll
-  for (int e = 0; e < V; e++) {
-    const int c = cv * V + e;
-    mu[e] = mean[c]; is[e] = invstd[c];
-    ga[e] = gain ? gain[(long long)n * gsn + c] : 1.f;
-    bi[e] = bias ? bias[(long long)n * gsn + c] : 0.f;
-  }
-  const long long p0 = (long long)blockIdx.x * ppb;
-  long long p1 = p0 + ppb; if (p1 > HW) p1 = HW;
-  const T* xs = x + (long long)n * HW * C + cv * V;
-  T* ys = y + (long long)n * HW * C + cv * V;
-  // Four pixels per trip, all four loads issued before the first use: with one 16-byte load in flight per lane the 32 resident waves
-  // of a CU hold 32 KB, which at ~2 us of HBM latency is 4.2 TB/s for the chip -- exactly what the r02 roofline_hbm leg measured for
-  // the batch-norm family (0.53 of peak). Same arithmetic per element, so results are unchanged.
-  auto one = [&](const u32x4& raw, long long pix) {
-    float xv[V];
-    unpack16<T>(raw, xv);
-#pragma unroll
-    for (int e = 0; e < V; e++) {
-      float v = bn_pre(bn_xhat(xv[e], mu[e], is[e]), ga[e], bi[e]);   // the same evaluation as the backward's recomputation
-      if (relu) v = fmaxf(v, 0.f);
-      xv[e] = v;
-    }
-    const u32x4 o = pack16<T>(xv);
-    if (NT) __builtin_nontemporal_store(o, (u32x4*)(ys + pix * C)); else *(u32x4*)(ys + pix * C) = o;
-  };
-  long long pix = p0 + pl;
-  for (; pix + (long long)(UN - 1) * lanes_p < p1; pix += (long long)UN * lanes_p) {
-    u32x4 r[UN];
-#pragma unroll
-    for (int i = 0; i < UN; i++) r[i] = NT ? __builtin_nontemporal_load((const u32x4*)(xs + (pix + (long long)i * lanes_p) * C)) : *(const u32x4*)(xs + (pix + (long long)i * lanes_p) * C);
-#pragma unroll
-    for (int i = 0; i < UN; i++) one(r[i], pix + (long long)i * lanes_p);
-  }
-  for (; pix < p1; pix += lanes_p) one(*(const u32x4*)(xs + pix * C), pix);
+  bn_coef<V>(mean, invstd, gain, bias, gsn, blockIdx.y, w.cv * V, mu, is, ga, bi);
+  const T* xs = x + (long long)blockIdx.y * HW * C + w.cv * V;      // (= x + w.base with the sample's uniform part added first, as this kernel has always formed it:
+  T* ys = y + (long long)blockIdx.y * HW * C + w.cv * V;            //  from w.base the fp32 instantiations take four more registers)
+  bn_walk<UN, 1>(w,
+    [&](int, long long pix, bool unrolled) { return NT && unrolled ? __builtin_nontemporal_load((const u32x4*)(xs + pix * C)) : *(const u32x4*)(xs + pix * C); },
+    [&](const u32x4* r, long long pix) {
+      float xv[V];
+      unpack16<T>(r[0], xv);
+      bn_apply_elems<V>(xv, mu, is, ga, bi, relu);
+      const u32x4 o = pack16<T>(xv);
+      if (NT) __builtin_nontemporal_store(o, (u32x4*)(ys + pix * C)); else *(u32x4*)(ys + pix * C) = o;
+    });
 }
 // one instantiation launched and counted under the variant number its template arguments stand for (not the one that was asked for)
 template <typename T, int UN, bool NT> static void bn_apply_stream_go(dim3 grid, dim3 blk, hipStream_t st, const T* x, T* y, long long HW, int C, const float* mean, const float* invstd, const float* gain,
@@ -298,11 +385,11 @@ static void bn_apply_config(int* variant, long long* want) {
   if (sv >= 0) { *variant = sv; if (sw > 0) *want = sw; }
 }
 extern "C" int sg_bn_apply(int dtype, const void* x, void* y, int N, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, int gb_stride_n, int relu, sg_stream_t s) {
-  SgProfScope prof((hipStream_t)s, 2.0 * N * (double)HW * C * (dtype == SG_DTYPE_BF16 ? 2.0 : 4.0), 4);
+  SgProfScope prof((hipStream_t)s, 2.0 * N * (double)HW * C * elem_bytes(dtype), 4);
   SG_CHECK(x && y && mean && invstd, "sg_bn_apply: null");
   DISPATCH_T(dtype, {
     const int CV = C / ET<T>::VEC;
-    if (vec_ok<T>(x, y, C) && CV <= 256 && N <= 65535 && HW >= 16) {      // (HW 64 -> 16: the 4 x 4 maps of a generator's first block took the generic kernel at 0.56 TB/s, 45 us for 25 MB)
+    if (bn_streams<T>(vec_ok<T>(x, y, C), N, HW, C)) {
       const int lanes_p = 256 / CV;
       // Variant 0 = four loads in flight, 1 = eight, 2 = four + non-temporal accesses, 3 = eight + non-temporal; `want` workgroups (SG_BN_APPLY="<variant><workgroups / 1024>", A/B).
       // Measured (tools/bn_bench.py, profiles/r06_bn_apply_variants_r7f.txt): ALONE, this pass streams tensors far beyond the 256 MB Infinity Cache 7-12 % faster with non-temporal
@@ -310,12 +397,10 @@ extern "C" int sg_bn_apply(int dtype, const void* x, void* y, int N, long long H
       // alternations read +1.0 ms for the non-temporal arm (profiles/r06_bn_apply_step_ab_r7l.txt), but an ABBA series showed every second PROCESS on such a box running 1.5 ms
       // faster whatever the variant (profiles/r06_bn_apply_reverse_walk_r7r.txt): corrected, the effect lies between -0.9 and +0.2 ms. Unresolved, so the default stays variant 0
       // (the pass's output is the next convolution's input; what it leaves in the Infinity Cache may matter as much as its own 0.1 ms).
-      int variant; long long want;
+      int variant, ppb; long long want;
       bn_apply_config(&variant, &want);
-      long long chunks = want / N; if (chunks < 1) chunks = 1;
-      long long ppb = (HW + chunks - 1) / chunks; if (ppb < 4 * lanes_p) ppb = 4 * lanes_p;
-      const int gx = (int)((HW + ppb - 1) / ppb);
-      bn_apply_stream_launch<T>(variant, dim3(gx, N), dim3(CV * lanes_p), (hipStream_t)s, (const T*)x, (T*)y, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, (int)ppb);
+      const int gx = bn_stream_geom(HW, N, lanes_p, want, 4, &ppb);
+      bn_apply_stream_launch<T>(variant, dim3(gx, N), dim3(CV * lanes_p), (hipStream_t)s, (const T*)x, (T*)y, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, ppb);
       bn_path_count(SG_BN_PATH_APPLY_STREAM);
     } else if (vec_ok<T>(x, y, C)) {
       hipLaunchKernelGGL((k_bn_apply<T, true>), dim3(grid_for((long long)N * HW * C / ET<T>::VEC)), dim3(256), 0, (hipStream_t)s, (const T*)x, (T*)y, N, HW, C, mean, invstd, gain, bias, gb_stride_n, relu);
@@ -337,26 +422,22 @@ template <typename T> __global__ __launch_bounds__(256) void k_bn_bwd_reduce(con
   const int c = blockIdx.x * 64 + cx;
   const int n = blockIdx.z;
   long long r0 = blockIdx.y * rpb, r1 = r0 + rpb; if (r1 > HW) r1 = HW;
-  float s1 = 0.f, s2 = 0.f;
+  float s[2] = {0.f, 0.f};
   if (c < C) {
-    const float mu = mean[c], is = invstd[c];
-    const float ga = gain ? gain[(long long)n * gsn + c] : 1.f;
-    const float bi = bias ? bias[(long long)n * gsn + c] : 0.f;
+    float mu, is, ga, bi;
+    bn_coef<1>(mean, invstd, gain, bias, gsn, n, c, &mu, &is, &ga, &bi);
     const T* xp = x + (long long)n * HW * C + c;
     const T* gp = dy + (long long)n * HW * C + c;
     for (long long r = r0 + ry; r < r1; r += 4) {
-      const float xh = bn_xhat(to_f<T>(xp[r * C]), mu, is);
-      float g = to_f<T>(gp[r * C]);
-      if (relu && !(bn_pre(xh, ga, bi) > 0.f)) g = 0.f;
-      s1 += g; s2 += g * xh;
+      const float xv = to_f<T>(xp[r * C]), gv = to_f<T>(gp[r * C]);
+      bn_bwd_sum_elems<1>(&xv, &gv, &mu, &is, &ga, &bi, relu, &s[0], &s[1]);
     }
   }
-  sm[0][ry][cx] = s1; sm[1][ry][cx] = s2;
-  __syncthreads();
+  bn_col_store(sm, s, ry, cx);
   if (ry == 0 && c < C) {
     float* o = sums + ((long long)n * C + c) * 2;
-    unsafeAtomicAdd(o, sm[0][0][cx] + sm[0][1][cx] + sm[0][2][cx] + sm[0][3][cx]);
-    unsafeAtomicAdd(o + 1, sm[1][0][cx] + sm[1][1][cx] + sm[1][2][cx] + sm[1][3][cx]);
+#pragma unroll
+    for (int k = 0; k < 2; k++) bn_atomic_add(o + k, bn_col_sum<false>(sm[k], cx));
   }
 }
 // Streaming variant of stage 1 (16-byte loads; thread = one channel vector of one sample; LDS combine; float atomics)
@@ -364,75 +445,41 @@ template <typename T> __global__ __launch_bounds__(256) void k_bn_bwd_reduce_str
   constexpr int V = ET<T>::VEC;
   extern __shared__ float smf[];                        // [lanes_p][C][2]
   const int CV = C / V;
-  const int n = blockIdx.y;
-  const int lanes_p = blockDim.x / CV;
-  const int cv = threadIdx.x % CV, pl = threadIdx.x / CV;
+  const BnOwn w = bn_own(0, CV, blockDim.x / CV, V, HW, C, ppb);
   float mu[V], is[V], ga[V], bi[V], s1[V], s2[V];
+  bn_coef<V>(mean, invstd, gain, bias, gsn, blockIdx.y, w.cv * V, mu, is, ga, bi);
 #pragma unroll
-  for (int e = 0; e < V; e++) {
-    const int c = cv * V + e;
-    mu[e] = mean[c]; is[e] = invstd[c];
-    ga[e] = gain ? gain[(long long)n * gsn + c] : 1.f;
-    bi[e] = bias ? bias[(long long)n * gsn + c] : 0.f;
-    s1[e] = 0.f; s2[e] = 0.f;
-  }
-  const long long p0 = (long long)blockIdx.x * ppb;
-  long long p1 = p0 + ppb; if (p1 > HW) p1 = HW;
-  const long long base = (long long)n * HW * C + cv * V;
-  auto one = [&](const u32x4& rx, const u32x4& rg) {
-    float xv[V], gv[V];
-    unpack16<T>(rx, xv);
-    unpack16<T>(rg, gv);
-#pragma unroll
-    for (int e = 0; e < V; e++) {
-      const float xh = bn_xhat(xv[e], mu[e], is[e]);
-      float g = gv[e];
-      if (relu && !(bn_pre(xh, ga[e], bi[e]) > 0.f)) g = 0.f;
-      s1[e] += g; s2[e] += g * xh;
-    }
-  };
-  long long pix = p0 + pl;                                   // same pixel order as before (sums unchanged), eight loads in flight
-  for (; pix + 3ll * lanes_p < p1; pix += 4ll * lanes_p) {
-    u32x4 rx[4], rg[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) { rx[i] = *(const u32x4*)(x + base + (pix + (long long)i * lanes_p) * C); rg[i] = *(const u32x4*)(dy + base + (pix + (long long)i * lanes_p) * C); }
-#pragma unroll
-    for (int i = 0; i < 4; i++) one(rx[i], rg[i]);
-  }
-  for (; pix < p1; pix += lanes_p) one(*(const u32x4*)(x + base + pix * C), *(const u32x4*)(dy + base + pix * C));
-#pragma unroll
-  for (int e = 0; e < V; e++) { smf[((long long)pl * C + cv * V + e) * 2] = s1[e]; smf[((long long)pl * C + cv * V + e) * 2 + 1] = s2[e]; }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
-    float a = 0.f;
-    for (int l = 0; l < lanes_p; l++) a += smf[(long long)l * C * 2 + i];
-    unsafeAtomicAdd(sums + (long long)n * C * 2 + i, a);
-  }
+  for (int e = 0; e < V; e++) { s1[e] = 0.f; s2[e] = 0.f; }
+  bn_walk<4, 2>(w,                                           // eight loads in flight
+    [&](int k, long long pix, bool) { return *(const u32x4*)((k ? dy : x) + w.base + pix * C); },
+    [&](const u32x4* r, long long) {
+      float xv[V], gv[V];
+      unpack16<T>(r[0], xv);
+      unpack16<T>(r[1], gv);
+      bn_bwd_sum_elems<V>(xv, gv, mu, is, ga, bi, relu, s1, s2);
+    });
+  bn_lane_combine<V>(smf, s1, s2, w.pl, w.cv, w.lanes_p, C, sums + (long long)blockIdx.y * C * 2);
 }
 extern "C" int sg_bn_bwd_reduce(int dtype, const void* x, const void* dy, int N, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, int gb_stride_n, int relu, float* sums, sg_stream_t s) {
-  SgProfScope prof((hipStream_t)s, 2.0 * N * (double)HW * C * (dtype == SG_DTYPE_BF16 ? 2.0 : 4.0), 4);
+  SgProfScope prof((hipStream_t)s, 2.0 * N * (double)HW * C * elem_bytes(dtype), 4);
   SG_CHECK(x && dy && mean && invstd && sums, "sg_bn_bwd_reduce: null");
   SG_CHECK(N <= 65535, "sg_bn_bwd_reduce: batch too large for grid.z");
   bool done = false;
   DISPATCH_T(dtype, {
-    constexpr int V = ET<T>::VEC;
-    const int CV = C / V;
-    if (vec_ok<T>(x, dy, C) && CV <= 256 && HW >= 16) {
+    const int CV = C / ET<T>::VEC;
+    if (bn_streams<T>(vec_ok<T>(x, dy, C), N, HW, C)) {
       const int lanes_p = 256 / CV;
-      long long chunks = 2048 / N; if (chunks < 1) chunks = 1;
-      long long ppb = (HW + chunks - 1) / chunks; if (ppb < 8 * lanes_p) ppb = 8 * lanes_p;
-      const int gx = (int)((HW + ppb - 1) / ppb);
-      hipLaunchKernelGGL(k_bn_bwd_reduce_stream<T>, dim3(gx, N), dim3(CV * lanes_p), (size_t)lanes_p * C * 2 * sizeof(float), (hipStream_t)s, (const T*)x, (const T*)dy, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, sums, (int)ppb);
+      int ppb;
+      const int gx = bn_stream_geom(HW, N, lanes_p, 2048, 8, &ppb);
+      hipLaunchKernelGGL(k_bn_bwd_reduce_stream<T>, dim3(gx, N), dim3(CV * lanes_p), (size_t)lanes_p * C * 2 * sizeof(float), (hipStream_t)s, (const T*)x, (const T*)dy, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, sums, ppb);
       bn_path_count(SG_BN_PATH_BWD_REDUCE_STREAM);
       done = true;
     }
   });
   if (done) { SG_LAUNCH_CHECK(); return 0; }
-  int ct = (C + 63) / 64;
-  long long want = 2048 / ((long long)ct * N); if (want < 1) want = 1;
-  long long rpb = (HW + want - 1) / want; if (rpb < 16) rpb = 16;
-  int gy = (int)((HW + rpb - 1) / rpb);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(k_bn_bwd_reduce<T>, dim3(ct, gy, N), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, sums, rpb));
+  long long rpb;
+  const dim3 grid = bn_col_grid(N, HW, C, &rpb);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(k_bn_bwd_reduce<T>, grid, dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, sums, rpb));
   bn_path_count(SG_BN_PATH_BWD_REDUCE_GENERIC);
   SG_LAUNCH_CHECK();
   return 0;
@@ -481,28 +528,13 @@ template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_bn_bwd
   const float invc = (float)(1.0 / count);
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int cv = (int)(i % CV); const long long pix = i / CV; const int n = (int)(pix / HW);
-    const int c0 = cv * V;
-    float xv[V], gv[V];
-    if (VECP) { unpack16<T>(*(const u32x4*)(x + pix * C + c0), xv); unpack16<T>(*(const u32x4*)(dy + pix * C + c0), gv); }
-    else { xv[0] = to_f<T>(x[pix * C + c0]); gv[0] = to_f<T>(dy[pix * C + c0]); }
-#pragma unroll
-    for (int e = 0; e < V; e++) {
-      const int c = c0 + e;
-      const float is = invstd[c];
-      const float xh = bn_xhat(xv[e], mean[c], is);
-      const float ga = gain ? gain[(long long)n * gsn + c] : 1.f;
-      const float bi = bias ? bias[(long long)n * gsn + c] : 0.f;
-      float g = gv[e];
-      if (relu && !(bn_pre(xh, ga, bi) > 0.f)) g = 0.f;
-      xv[e] = bn_dx(g, xh, ga, is, use_batch ? (float)chan[2 * c] : 0.f, use_batch ? (float)chan[2 * c + 1] : 0.f, invc, use_batch);
-    }
-    if (res) {
-      float rv[V];
-      if (VECP) unpack16<T>(*(const u32x4*)(res + pix * C + c0), rv); else rv[0] = to_f<T>(res[pix * C + c0]);
-#pragma unroll
-      for (int e = 0; e < V; e++) xv[e] = bn_add(xv[e], rv[e]);
-    }
-    if (VECP) *(u32x4*)(dx + pix * C + c0) = pack16<T>(xv); else dx[pix * C + c0] = from_f<T>(xv[0]);
+    const long long o = pix * C + cv * V;
+    float xv[V], gv[V], mu[V], is[V], ga[V], bi[V], k0[V], k1[V];
+    load_f<T, V>(x + o, xv);
+    load_f<T, V>(dy + o, gv);
+    bn_coef<V>(mean, invstd, gain, bias, gsn, n, cv * V, mu, is, ga, bi, chan, use_batch, k0, k1);
+    bn_bwd_apply_elems<T, V>(xv, gv, res ? res + o : nullptr, mu, is, ga, bi, k0, k1, invc, relu, use_batch);
+    *(vec_t<T, V>*)(dx + o) = pack_f<T, V>(xv);
   }
 }
 // Streaming variant (same ownership as k_bn_apply_stream): a thread keeps the 6 per-channel coefficients of its 16-byte
@@ -510,69 +542,37 @@ template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_bn_bwd
 template <typename T> __global__ __launch_bounds__(256) void k_bn_bwd_apply_stream(const T* x, const T* dy, T* dx, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, int gsn, int relu, const double* chan, double count, int use_batch, int ppb, const T* res) {
   constexpr int V = ET<T>::VEC;
   const int CV = C / V;
-  const int n = blockIdx.y;
-  const int lanes_p = blockDim.x / CV;
-  const int cv = threadIdx.x % CV, pl = threadIdx.x / CV;
+  const BnOwn w = bn_own(0, CV, blockDim.x / CV, V, HW, C, ppb);
   const float invc = (float)(1.0 / count);
   float mu[V], is[V], ga[V], bi[V], k0[V], k1[V];
-#pragma unroll
-  for (int e = 0; e < V; e++) {
-    const int c = cv * V + e;
-    mu[e] = mean[c]; is[e] = invstd[c];
-    ga[e] = gain ? gain[(long long)n * gsn + c] : 1.f;
-    bi[e] = bias ? bias[(long long)n * gsn + c] : 0.f;
-    k0[e] = use_batch ? (float)chan[2 * c] : 0.f;
-    k1[e] = use_batch ? (float)chan[2 * c + 1] : 0.f;
-  }
-  const long long p0 = (long long)blockIdx.x * ppb;
-  long long p1 = p0 + ppb; if (p1 > HW) p1 = HW;
-  const long long base = (long long)n * HW * C + cv * V;
-  auto one = [&](const u32x4& rx, const u32x4& rg, long long pix) {
-    float xv[V], gv[V];
-    unpack16<T>(rx, xv);
-    unpack16<T>(rg, gv);
-#pragma unroll
-    for (int e = 0; e < V; e++) {
-      const float xh = bn_xhat(xv[e], mu[e], is[e]);
-      float g = gv[e];
-      if (relu && !(bn_pre(xh, ga[e], bi[e]) > 0.f)) g = 0.f;
-      xv[e] = bn_dx(g, xh, ga[e], is[e], k0[e], k1[e], invc, use_batch);     // the same evaluation as k_bn_bwd_apply
-    }
-    if (res) {                                                // the skip path's gradient w.r.t. the same input (see k_bn_bwd_apply)
-      float rv[V];
-      unpack16<T>(*(const u32x4*)(res + base + pix * C), rv);
-#pragma unroll
-      for (int e = 0; e < V; e++) xv[e] = bn_add(xv[e], rv[e]);
-    }
-    *(u32x4*)(dx + base + pix * C) = pack16<T>(xv);
-  };
-  long long pix = p0 + pl;                                   // four pixels = eight loads in flight per lane (see k_bn_apply_stream)
-  for (; pix + 3ll * lanes_p < p1; pix += 4ll * lanes_p) {
-    u32x4 rx[4], rg[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) { rx[i] = *(const u32x4*)(x + base + (pix + (long long)i * lanes_p) * C); rg[i] = *(const u32x4*)(dy + base + (pix + (long long)i * lanes_p) * C); }
-#pragma unroll
-    for (int i = 0; i < 4; i++) one(rx[i], rg[i], pix + (long long)i * lanes_p);
-  }
-  for (; pix < p1; pix += lanes_p) one(*(const u32x4*)(x + base + pix * C), *(const u32x4*)(dy + base + pix * C), pix);
+  bn_coef<V>(mean, invstd, gain, bias, gsn, blockIdx.y, w.cv * V, mu, is, ga, bi, chan, use_batch, k0, k1);
+  bn_walk<4, 2>(w,                                           // four pixels = eight loads in flight per lane
+    [&](int k, long long pix, bool) { return *(const u32x4*)((k ? dy : x) + w.base + pix * C); },
+    [&](const u32x4* r, long long pix) {
+      float xv[V], gv[V];
+      unpack16<T>(r[0], xv);
+      unpack16<T>(r[1], gv);
+      bn_bwd_apply_elems<T, V>(xv, gv, res ? res + w.base + pix * C : nullptr, mu, is, ga, bi, k0, k1, invc, relu, use_batch);
+      *(u32x4*)(dx + w.base + pix * C) = pack16<T>(xv);
+    });
 }
 extern "C" int sg_bn_bwd_apply(int dtype, const void* x, const void* dy, void* dx, int N, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, int gb_stride_n, int relu, const double* chan, double count, int use_batch_stats, sg_stream_t s) {
   return sg_bn_bwd_apply_res(dtype, x, dy, dx, N, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, chan, count, use_batch_stats, nullptr, s);
 }
 extern "C" int sg_bn_bwd_apply_res(int dtype, const void* x, const void* dy, void* dx, int N, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, int gb_stride_n, int relu, const double* chan, double count, int use_batch_stats, const void* res, sg_stream_t s) {
-  SgProfScope prof((hipStream_t)s, (res ? 4.0 : 3.0) * N * (double)HW * C * (dtype == SG_DTYPE_BF16 ? 2.0 : 4.0), 4);
+  SgProfScope prof((hipStream_t)s, (res ? 4.0 : 3.0) * N * (double)HW * C * elem_bytes(dtype), 4);
   SG_CHECK(x && dy && dx && mean && invstd && chan && count > 0, "sg_bn_bwd_apply: bad args");
   SG_CHECK(!res || ((((uintptr_t)res) & 15) == 0), "sg_bn_bwd_apply_res: res must be 16-byte aligned");
   DISPATCH_T(dtype, {
     const int CV = C / ET<T>::VEC;
-    if (vec_ok<T>(x, dy, C) && ((((uintptr_t)dx) & 15) == 0) && CV <= 256 && N <= 65535 && HW >= 16) {
+    const bool vec = vec_ok<T>(x, dy, C) && ((((uintptr_t)dx) & 15) == 0);
+    if (bn_streams<T>(vec, N, HW, C)) {
       const int lanes_p = 256 / CV;
-      long long chunks = 2048 / N; if (chunks < 1) chunks = 1;
-      long long ppb = (HW + chunks - 1) / chunks; if (ppb < 4 * lanes_p) ppb = 4 * lanes_p;
-      const int gx = (int)((HW + ppb - 1) / ppb);
-      hipLaunchKernelGGL(k_bn_bwd_apply_stream<T>, dim3(gx, N), dim3(CV * lanes_p), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (T*)dx, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, chan, count, use_batch_stats, (int)ppb, (const T*)res);
+      int ppb;
+      const int gx = bn_stream_geom(HW, N, lanes_p, 2048, 4, &ppb);
+      hipLaunchKernelGGL(k_bn_bwd_apply_stream<T>, dim3(gx, N), dim3(CV * lanes_p), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (T*)dx, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, chan, count, use_batch_stats, ppb, (const T*)res);
       bn_path_count(SG_BN_PATH_BWD_APPLY_STREAM);
-    } else if (vec_ok<T>(x, dy, C) && ((((uintptr_t)dx) & 15) == 0)) {
+    } else if (vec) {
       hipLaunchKernelGGL((k_bn_bwd_apply<T, true>), dim3(grid_for((long long)N * HW * C / ET<T>::VEC)), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (T*)dx, N, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, chan, count, use_batch_stats, (const T*)res);
       bn_path_count(SG_BN_PATH_BWD_APPLY_VEC);
     } else {
@@ -592,8 +592,9 @@ extern "C" int sg_bn_bwd_apply_res(int dtype, const void* x, const void* dy, voi
 //     dL/dx    = g_c r^2 ( -c (u - ub) - a (g - gb) + xhat (3 a c - m + ub gb) )
 //     dL/dg_c  = r N ( m - ub gb - a c )                       (reference: torch autograd through F.batch_norm's backward,
 //                                                               reached from utils/losses.py:268-275,301-316)
-// stage 1: sums[n][c][5] = {sum u, sum u xhat, sum g, sum g xhat, sum u g}; caller zeroes sums
-template <typename T> __global__ __launch_bounds__(256) void k_bn_bwd2_reduce(const T* x, const T* dy, const T* u, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, int relu, float* sums, long long rpb) {
+// stage 1: sums[n][c][5] = {sum u, sum u xhat, sum g, sum g xhat, sum u g}; caller zeroes sums. Only the mask reads gain / bias, as rows of pitch gsn: the
+// per-channel pass (sg_bn_bwd2_reduce) is pitch 0, the per-sample pass below (sg_cbn_bwd2_reduce) the pitch of its rows
+template <typename T> __global__ __launch_bounds__(256) void k_cbn_bwd2_reduce(const T* x, const T* dy, const T* u, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, int gsn, int relu, float* sums, long long rpb) {
   __shared__ float sm[5][4][64];
   const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + cx;
@@ -601,37 +602,35 @@ template <typename T> __global__ __launch_bounds__(256) void k_bn_bwd2_reduce(co
   long long r0 = blockIdx.y * rpb, r1 = r0 + rpb; if (r1 > HW) r1 = HW;
   float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   if (c < C) {
-    const float mu = mean[c], is = invstd[c];
-    const float ga = gain ? gain[c] : 1.f;
-    const float bi = bias ? bias[c] : 0.f;
+    float mu, is, ga, bi;
+    bn_coef<1>(mean, invstd, gain, bias, gsn, n, c, &mu, &is, &ga, &bi);
     const long long base = (long long)n * HW * C + c;
     for (long long r = r0 + ry; r < r1; r += 4) {
       const float xh = bn_xhat(to_f<T>(x[base + r * C]), mu, is);
       float g = to_f<T>(dy[base + r * C]);
-      if (relu && !(bn_pre(xh, ga, bi) > 0.f)) g = 0.f;
+      if (!bn_gate(relu, xh, ga, bi)) g = 0.f;
       const float uu = to_f<T>(u[base + r * C]);
       s[0] += uu; s[1] += uu * xh; s[2] += g; s[3] += g * xh; s[4] += uu * g;
     }
   }
-#pragma unroll
-  for (int k = 0; k < 5; k++) sm[k][ry][cx] = s[k];
-  __syncthreads();
+  bn_col_store(sm, s, ry, cx);
   if (ry == 0 && c < C) {
     float* o = sums + ((long long)n * C + c) * 5;
 #pragma unroll
-    for (int k = 0; k < 5; k++) unsafeAtomicAdd(o + k, sm[k][0][cx] + sm[k][1][cx] + sm[k][2][cx] + sm[k][3][cx]);
+    for (int k = 0; k < 5; k++) bn_atomic_add(o + k, bn_col_sum<false>(sm[k], cx));
   }
+}
+static int bn_bwd2_reduce_launch(int dtype, const void* x, const void* dy, const void* u, int N, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, int gsn, int relu, float* sums, sg_stream_t s) {
+  long long rpb;
+  const dim3 grid = bn_col_grid(N, HW, C, &rpb);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(k_cbn_bwd2_reduce<T>, grid, dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (const T*)u, HW, C, mean, invstd, gain, bias, gsn, relu, sums, rpb));
+  SG_LAUNCH_CHECK();
+  return 0;
 }
 extern "C" int sg_bn_bwd2_reduce(int dtype, const void* x, const void* dy, const void* u, int N, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, int relu, float* sums, sg_stream_t s) {
   SG_CHECK(x && dy && u && mean && invstd && sums, "sg_bn_bwd2_reduce: null");
   SG_CHECK(N <= 65535, "sg_bn_bwd2_reduce: batch too large for grid.z");
-  int ct = (C + 63) / 64;
-  long long want = 2048 / ((long long)ct * N); if (want < 1) want = 1;
-  long long rpb = (HW + want - 1) / want; if (rpb < 16) rpb = 16;
-  int gy = (int)((HW + rpb - 1) / rpb);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(k_bn_bwd2_reduce<T>, dim3(ct, gy, N), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (const T*)u, HW, C, mean, invstd, gain, bias, relu, sums, rpb));
-  SG_LAUNCH_CHECK();
-  return 0;
+  return bn_bwd2_reduce_launch(dtype, x, dy, u, N, HW, C, mean, invstd, gain, bias, 0, relu, sums, s);
 }
 // stage 2: chan[c][5] (fp64) = sum over n
 __global__ void k_bn_bwd2_finalize(const float* sums, int N, int C, double* chan) {
@@ -671,11 +670,10 @@ template <typename T> __global__ __launch_bounds__(256) void k_bn_bwd2_apply(con
   const float invc = (float)(1.0 / count);
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int c = (int)(i % C);
-    const float is = invstd[c];
-    const float xh = bn_xhat(to_f<T>(x[i]), mean[c], is);
-    const float ga = gain ? gain[c] : 1.f;
-    const float bi = bias ? bias[c] : 0.f;
-    const bool on = !(relu && !(bn_pre(xh, ga, bi) > 0.f));
+    float mu, is, ga, bi;
+    bn_coef<1>(mean, invstd, gain, bias, 0, 0, c, &mu, &is, &ga, &bi);
+    const float xh = bn_xhat(to_f<T>(x[i]), mu, is);
+    const bool on = bn_gate(relu, xh, ga, bi);
     const float g = on ? to_f<T>(dy[i]) : 0.f;
     const float uu = to_f<T>(u[i]);
     float ub = 0.f, a = 0.f, gb = 0.f, cc = 0.f, m = 0.f;
@@ -706,47 +704,12 @@ extern "C" int sg_bn_bwd2_apply(int dtype, const void* x, const void* dy, const 
 //     dL/dx      = s r^2 ( -ch (u - ub) - a (h - hb) + xhat (3 a ch - mh + ub hb) ) + r ( w - s wb - s xhat wx )
 //     dL/dbet_n  = 0                                              (the bias enters through the mask only)
 // With gam_n = g_c for every n and A = B = 0 these are the per-channel formulas above. Same launch structure: reduce -> finalize -> apply (+ gain rows).
-// stage 1: sums[n][c][5] = {sum u, sum u xhat, sum g, sum g xhat, sum u g} (the per-channel pass's five; only the mask reads the rows); caller zeroes sums
-template <typename T> __global__ __launch_bounds__(256) void k_cbn_bwd2_reduce(const T* x, const T* dy, const T* u, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, int gsn, int relu, float* sums, long long rpb) {
-  __shared__ float sm[5][4][64];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cx;
-  const int n = blockIdx.z;
-  long long r0 = blockIdx.y * rpb, r1 = r0 + rpb; if (r1 > HW) r1 = HW;
-  float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-  if (c < C) {
-    const float mu = mean[c], is = invstd[c];
-    const float ga = gain ? gain[(long long)n * gsn + c] : 1.f;
-    const float bi = bias ? bias[(long long)n * gsn + c] : 0.f;
-    const long long base = (long long)n * HW * C + c;
-    for (long long r = r0 + ry; r < r1; r += 4) {
-      const float xh = bn_xhat(to_f<T>(x[base + r * C]), mu, is);
-      float g = to_f<T>(dy[base + r * C]);
-      if (relu && !(bn_pre(xh, ga, bi) > 0.f)) g = 0.f;
-      const float uu = to_f<T>(u[base + r * C]);
-      s[0] += uu; s[1] += uu * xh; s[2] += g; s[3] += g * xh; s[4] += uu * g;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 5; k++) sm[k][ry][cx] = s[k];
-  __syncthreads();
-  if (ry == 0 && c < C) {
-    float* o = sums + ((long long)n * C + c) * 5;
-#pragma unroll
-    for (int k = 0; k < 5; k++) unsafeAtomicAdd(o + k, sm[k][0][cx] + sm[k][1][cx] + sm[k][2][cx] + sm[k][3][cx]);
-  }
-}
+// stage 1: the per-channel pass's five sums per (n, c), by its kernel (k_cbn_bwd2_reduce above) at the pitch of the rows; caller zeroes sums
 extern "C" int sg_cbn_bwd2_reduce(int dtype, const void* x, const void* dy, const void* u, int N, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, int gb_stride_n, int relu, float* sums, sg_stream_t s) {
   SG_CHECK(x && dy && u && mean && invstd && sums && N > 0 && HW > 0 && C > 0, "sg_cbn_bwd2_reduce: bad args");
   SG_CHECK(N <= 65535, "sg_cbn_bwd2_reduce: batch too large for grid.z");
   SG_CHECK((!gain && !bias) || gb_stride_n >= C, "sg_cbn_bwd2_reduce: row pitch below C");
-  int ct = (C + 63) / 64;
-  long long want = 2048 / ((long long)ct * N); if (want < 1) want = 1;
-  long long rpb = (HW + want - 1) / want; if (rpb < 16) rpb = 16;
-  int gy = (int)((HW + rpb - 1) / rpb);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(k_cbn_bwd2_reduce<T>, dim3(ct, gy, N), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (const T*)u, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, sums, rpb));
-  SG_LAUNCH_CHECK();
-  return 0;
+  return bn_bwd2_reduce_launch(dtype, x, dy, u, N, HW, C, mean, invstd, gain, bias, gb_stride_n, relu, sums, s);
 }
 // stage 2: chan[c][7] (fp64) = {sum_n S0, sum_n S1, sum_n gam_n S2, sum_n gam_n S3, sum_n gam_n S4, sum_n A_n S2, sum_n A_n S3}; block = 64 channels x 4 sample
 // groups, combined in a fixed order (deterministic). A (cotangent of the gain rows, pitch gsn as the rows themselves) may be null
@@ -765,12 +728,10 @@ __global__ __launch_bounds__(256) void k_cbn_bwd2_finalize(const float* sums, in
       a[5] += an * sp[2]; a[6] += an * sp[3];
     }
   }
-#pragma unroll
-  for (int k = 0; k < 7; k++) sa[k][grp][cl] = a[k];
-  __syncthreads();
+  bn_col_store(sa, a, grp, cl);
   if (grp == 0 && c < C) {
 #pragma unroll
-    for (int k = 0; k < 7; k++) chan[7 * c + k] = (sa[k][0][cl] + sa[k][1][cl]) + (sa[k][2][cl] + sa[k][3][cl]);
+    for (int k = 0; k < 7; k++) chan[7 * c + k] = bn_col_sum<true>(sa[k], cl);
   }
 }
 extern "C" int sg_cbn_bwd2_finalize(const float* sums, int N, int C, const float* gain, const float* A, int gb_stride_n, double* chan, sg_stream_t s) {
@@ -805,17 +766,13 @@ template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_cbn_bw
   constexpr int V = VECP ? ET<T>::VEC : 1;
   const int CV = C / V;
   const int n = blockIdx.y;
-  const int lanes_p = 256 / cvt;
-  const int pl = threadIdx.x / cvt;
-  const int cv = blockIdx.z * cvt + threadIdx.x % cvt;
-  if (pl >= lanes_p || cv >= CV) return;
+  const BnOwn w = bn_own(blockIdx.z * cvt, cvt, 256 / cvt, V, HW, C, ppb);
+  if (w.pl >= w.lanes_p || w.cv >= CV) return;
   float mu[V], is[V], ga[V], bi[V], P[V], Q[V], R[V], E1[V], E2[V], E3[V], E4[V];
+  bn_coef<V>(mean, invstd, gain, bias, gsn, n, w.cv * V, mu, is, ga, bi);
 #pragma unroll
   for (int e = 0; e < V; e++) {
-    const int c = cv * V + e;
-    mu[e] = mean[c]; is[e] = invstd[c];
-    ga[e] = gain ? gain[(long long)n * gsn + c] : 1.f;
-    bi[e] = bias ? bias[(long long)n * gsn + c] : 0.f;
+    const int c = w.cv * V + e;
     const double r = is[e], gm = ga[e];
     const double an = A ? (double)A[(long long)n * gsn + c] : 0.0, bn = Bc ? (double)Bc[(long long)n * gsn + c] : 0.0;
     double p = gm * r, q = an, rr = bn, e1 = 0.0, e2 = r * an, e3 = 0.0, e4 = 0.0;
@@ -829,25 +786,23 @@ template <typename T, bool VECP> __global__ __launch_bounds__(256) void k_cbn_bw
     }
     P[e] = (float)p; Q[e] = (float)q; R[e] = (float)rr; E1[e] = (float)e1; E2[e] = (float)e2; E3[e] = (float)e3; E4[e] = (float)e4;
   }
-  const long long p0 = (long long)blockIdx.x * ppb;
-  long long p1 = p0 + ppb; if (p1 > HW) p1 = HW;
-  const long long base = (long long)n * HW * C + (long long)cv * V;
 #pragma unroll 2
-  for (long long pix = p0 + pl; pix < p1; pix += lanes_p) {
-    const long long o = base + pix * C;
+  for (long long pix = w.p0 + w.pl; pix < w.p1; pix += w.lanes_p) {
+    const long long o = w.base + pix * C;
     float xv[V], gv[V], uv[V], o1[V], o2[V];
-    if (VECP) { unpack16<T>(*(const u32x4*)(x + o), xv); unpack16<T>(*(const u32x4*)(dy + o), gv); unpack16<T>(*(const u32x4*)(u + o), uv); }
-    else { xv[0] = to_f<T>(x[o]); gv[0] = to_f<T>(dy[o]); uv[0] = to_f<T>(u[o]); }
+    load_f<T, V>(x + o, xv);
+    load_f<T, V>(dy + o, gv);
+    load_f<T, V>(u + o, uv);
 #pragma unroll
     for (int e = 0; e < V; e++) {
       const float xh = bn_xhat(xv[e], mu[e], is[e]);
-      const bool on = !(relu && !(bn_pre(xh, ga[e], bi[e]) > 0.f));
+      const bool on = bn_gate(relu, xh, ga[e], bi[e]);
       const float g = on ? gv[e] : 0.f;
       o1[e] = on ? (P[e] * uv[e] + Q[e] * xh + R[e]) : 0.f;
       o2[e] = E1[e] * uv[e] + E2[e] * g + E3[e] * xh + E4[e];
     }
-    if (VECP) { if (g_dy) *(u32x4*)(g_dy + o) = pack16<T>(o1); if (g_x) *(u32x4*)(g_x + o) = pack16<T>(o2); }
-    else { if (g_dy) g_dy[o] = from_f<T>(o1[0]); if (g_x) g_x[o] = from_f<T>(o2[0]); }
+    if (g_dy) *(vec_t<T, V>*)(g_dy + o) = pack_f<T, V>(o1);
+    if (g_x) *(vec_t<T, V>*)(g_x + o) = pack_f<T, V>(o2);
   }
 }
 extern "C" int sg_cbn_bwd2_apply(int dtype, const void* x, const void* dy, const void* u, void* g_dy, void* g_x, int N, long long HW, int C, const float* mean, const float* invstd, const float* gain, const float* bias, const float* A, const float* B, int gb_stride_n, int relu, const double* chan, double count, int use_batch_stats, sg_stream_t s) {
@@ -859,12 +814,10 @@ extern "C" int sg_cbn_bwd2_apply(int dtype, const void* x, const void* dy, const
     const int CV = vec ? C / ET<T>::VEC : C;
     const int cvt = CV < 256 ? CV : 256;
     const int gz = (CV + cvt - 1) / cvt;
-    const int lanes_p = 256 / cvt;
-    long long chunks = 2048 / ((long long)N * gz); if (chunks < 1) chunks = 1;
-    long long ppb = (HW + chunks - 1) / chunks; if (ppb < 4 * lanes_p) ppb = 4 * lanes_p;
-    const int gx = (int)((HW + ppb - 1) / ppb);
-    if (vec) hipLaunchKernelGGL((k_cbn_bwd2_apply<T, true>), dim3(gx, N, gz), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (const T*)u, (T*)g_dy, (T*)g_x, HW, C, mean, invstd, gain, bias, A, B, gb_stride_n, relu, chan, count, use_batch_stats, (int)ppb, cvt);
-    else hipLaunchKernelGGL((k_cbn_bwd2_apply<T, false>), dim3(gx, N, gz), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (const T*)u, (T*)g_dy, (T*)g_x, HW, C, mean, invstd, gain, bias, A, B, gb_stride_n, relu, chan, count, use_batch_stats, (int)ppb, cvt);
+    int ppb;
+    const int gx = bn_stream_geom(HW, (long long)N * gz, 256 / cvt, 2048, 4, &ppb);
+    if (vec) hipLaunchKernelGGL((k_cbn_bwd2_apply<T, true>), dim3(gx, N, gz), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (const T*)u, (T*)g_dy, (T*)g_x, HW, C, mean, invstd, gain, bias, A, B, gb_stride_n, relu, chan, count, use_batch_stats, ppb, cvt);
+    else hipLaunchKernelGGL((k_cbn_bwd2_apply<T, false>), dim3(gx, N, gz), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (const T*)u, (T*)g_dy, (T*)g_x, HW, C, mean, invstd, gain, bias, A, B, gb_stride_n, relu, chan, count, use_batch_stats, ppb, cvt);
     bn_path_count(vec ? SG_BN_PATH_CBN_BWD2_APPLY_VEC : SG_BN_PATH_CBN_BWD2_APPLY_SCALAR);
   });
   SG_LAUNCH_CHECK();

@@ -14,7 +14,8 @@ Bounds, none of them tuned on the code under test:
                   over the tensor's max-abs), the largest over the cases of the check; 4x that for the atomics' summation order, floor 1e-6; bf16 tensors: 2^-8 |ref| per
                   element plus that bound times max|ref|. Computed again in every process; one run's values are recorded in profiles/bn_bounds.txt (write_bounds).
 Exact checks: the kernels of one entry point write the SAME BYTES on identical logical inputs (streaming variants 0-3, the scalar kernel on a shifted pointer, the
-generic 16-byte kernel), and forward and backward agree on the ReLU mask element for element on inputs planted within a few fp32 ulps of a zero pre-activation.
+generic 16-byte kernel), sg_bn_bwd2_reduce and sg_cbn_bwd2_reduce (one kernel, k_cbn_bwd2_reduce, at row pitch 0 / C / 2 C) on the same values, and forward and
+backward agree on the ReLU mask element for element on inputs planted within a few fp32 ulps of a zero pre-activation.
 
 Not covered: more than one unrolled trip of the BACKWARD streaming kernels (k_bn_bwd_reduce_stream has a floor of two trips per block, k_bn_bwd_apply_stream of one;
 their workgroup target is fixed at 2048, so a longer walk needs tensors above 50 M elements); the RCCL / peer-store statistics paths; sg_bn_stats_from_tiles
@@ -622,6 +623,37 @@ def mask_case(spec, dev, dtype):
     print(f"[mask {DT_ID[dtype]} {spec_id(spec)}] {int(planted.sum())} of {planted.numel()} planted elements pass the ReLU; {len(outs) + 1} backward outputs agree")
 
 
+# ---- second-order stage 1: one kernel for per-channel vectors (row pitch 0) and per-sample rows ------------------------------------------------------------------------
+def bwd2_pitch_case(spec, dev, dtype):
+    """sg_bn_bwd2_reduce on gain[C] / bias[C] and sg_cbn_bwd2_reduce on rows that repeat those values for every sample, at pitch C and at the packed pitch 2 C, write
+    the SAME BYTES into sums[N][C][5]. At these sizes one block adds into each address (HW <= 16: one row group), so the result does not depend on atomic order"""
+    N, HW, C = spec["N"], spec["HW"], spec["C"]
+    assert HW <= 16
+    inp = elem_inputs(dict(spec, layout="chan", relu=1), dtype, backward=True)
+    ga, bi = inp["aff"]["ga"], inp["aff"]["bi"]
+    assert torch.equal(ga, ga[:1].expand(N, C)) and torch.equal(bi, bi[:1].expand(N, C))
+    u = q(torch.randn(N, HW, C, generator=gen(91 + C), dtype=torch.float64), dtype)
+    x, dy, ud = (Buf(dev, t.to(dtype)) for t in (inp["x"], inp["dy"], u))
+    mean, invstd = stat_dev(inp, dev)
+    vec = [ga[0].float().contiguous().to(dev), bi[0].float().contiguous().to(dev)]
+    rows = [ga.float().contiguous().to(dev), bi.float().contiguous().to(dev)]
+    packed = torch.cat([ga, bi], 1).float().contiguous().to(dev)
+
+    def run(name, gp, bp, *pitch):
+        sums = Buf(dev, torch.zeros(N, C, 5, dtype=torch.float32))
+        launch(None, name, _L().dt(dtype), x.ptr(), dy.ptr(), ud.ptr(), N, HW, C, dptr(mean), dptr(invstd), gp, bp, *pitch, 1, sums.ptr())
+        guard(sums, name)
+        return raw(sums), read(sums, torch.float32, (N, C, 5))
+
+    by, got = run("sg_bn_bwd2_reduce", dptr(vec[0]), dptr(vec[1]))
+    xh, g, _, _ = masked(inp, dict(relu=1), torch.float64)
+    assert bool((g == 0).any()) and bool((g != 0).any()), "the ReLU masks nothing or everything: the rows would not matter"
+    assert bool((got[..., 0] != 0).all()) and rel(got[..., 3], (g * xh).sum(1)) < 1e-2, "sums were not written"      # (a sanity line; the check is the bytes)
+    same_bytes(run("sg_cbn_bwd2_reduce", dptr(rows[0]), dptr(rows[1]), C)[0], by, "sg_cbn_bwd2_reduce on repeated rows of pitch C against sg_bn_bwd2_reduce")
+    same_bytes(run("sg_cbn_bwd2_reduce", dptr(packed), dptr(packed) + 4 * C, 2 * C)[0], by, "sg_cbn_bwd2_reduce on repeated packed rows of pitch 2 C against sg_bn_bwd2_reduce")
+    print(f"[bwd2_pitch {DT_ID[dtype]} {spec_id(spec)}] {by.numel()} bytes of sums equal at row pitch 0, C and 2 C; {int((g == 0).sum())} of {g.numel()} elements masked")
+
+
 # ---- end to end against the fp64 oracle ---------------------------------------------------------------------------------------------------------------------------------
 ROWS_SHAPES = [(19, 2, 2, 72), (37, 3, 2, 8), (2, 48, 47, 8)]      # N beyond the first trip of both finalize kernels (16 / 4 sample groups); 4512 rows: the streaming statistics kernel
 CHAN_SHAPES = [(2, 40, 40, 8), (19, 3, 3, 6)]
@@ -827,6 +859,9 @@ def _cases():
     add(bapply_case, dict(N=2, HW=20, C=20, use_batch=1, relu=1, res=1, path={"bf16": "scalar", "fp32": "stream"}))
     for sh in ({"x": 8}, {"dy": 8}, {"dx": 8}, {"dx": -1}):
         add(bapply_case, dict(N=4, HW=36, C=24, use_batch=1, relu=1, res=1, path="scalar", shift=sh))
+    # second-order stage 1: the per-channel entry point is the per-sample kernel at row pitch 0
+    add(bwd2_pitch_case, dict(N=3, HW=15, C=72))                                 # a second channel tile with an 8-wide tail
+    add(bwd2_pitch_case, dict(N=3, HW=15, C=6))
     # the ReLU mask on every path
     add(mask_case, dict(N=4, HW=36, C=24))
     add(mask_case, dict(N=3, HW=15, C=72))

@@ -79,16 +79,17 @@ def measure():
     return res
 
 
-def compare(parent, new):
+def compare(parent, new, shapes=SHAPES):
+    """shapes: {entry point: its shapes}, the keys of the round files (tools/bn_bench.py passes its own)"""
     P, N = [json.load(open(f)) for f in parent], [json.load(open(f)) for f in new]
     assert len(P) >= 3 and len(N) >= 3, "at least three rounds of either build"
     print("shapes:")
-    for name, shapes in SHAPES.items():
-        print(f"  {name:18s} {shapes}")
+    for name, shp in shapes.items():
+        print(f"  {name:18s} {shp}")
     print(f"\nbf16, us per entry point (its shapes summed), {len(P)} rounds of the parent build and {len(N)} of the new one, alternating")
     print(f"{'entry point':18s} {'parent median':>14s} {'new median':>12s} {'parent spread (max - min)':>27s}")
     slow = []
-    for name in SHAPES:
+    for name in shapes:
         p, n = [r[name] for r in P], [r[name] for r in N]
         pm, nm, spread = statistics.median(p), statistics.median(n), max(p) - min(p)
         over = nm > pm + spread
