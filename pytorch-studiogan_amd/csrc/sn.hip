@@ -13,6 +13,7 @@
 
 #define SN_SPLITS 16      // row groups of the W^T u pass (bank.py WeightBank.SN_SPLITS sizes the workspace with the same number)
 
+// ---- what several kernels state, once ----------------------------------------------------------------------
 // element (o, k) of the weight viewed as the [rows][cols] matrix spectral norm works on. Conv2d / Linear / Embedding:
 // natural layout (dim 0 = rows). ConvTranspose2d (torch uses dim=1): weight is [Cin][Cout][R][S], rows = Cout.
 template <class LAYER> __device__ __forceinline__ long long sn_widx(const LAYER& l, int o, int k) {
@@ -20,6 +21,16 @@ template <class LAYER> __device__ __forceinline__ long long sn_widx(const LAYER&
   const int c = k / l.RS, rs = k - c * l.RS;
   return ((long long)c * l.rows + o) * l.RS + rs;
 }
+// pitches (a pad of 0 = none): rows of the forward image = couts of the data-gradient image; channels of the forward image and of the gradient the backward reads
+__host__ __device__ __forceinline__ int sn_rows_out(const sg_sn_layer& l) { return l.rows_pad > l.rows ? l.rows_pad : l.rows; }
+template <class LAYER> __host__ __device__ __forceinline__ int sn_cin_pitch(const LAYER& l) { return l.Cin_pad > l.Cin ? l.Cin_pad : l.Cin; }
+__host__ __device__ __forceinline__ bool sn_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// the master's rows can be read 16 bytes (4 floats) at a time; every vector path adds its own terms to this
+__host__ __device__ __forceinline__ bool sn_rows16(const sg_sn_layer& l) { return !l.trans && (l.cols & 3) == 0 && sn_al16(l.w); }
+// W / sigma on four lanes: the scalar paths' operation (a division, not a multiplication by the reciprocal), so every path writes bit-identical images
+__device__ __forceinline__ f32x4 sn_div4(f32x4 v, float sig) { v[0] = v[0] / sig; v[1] = v[1] / sig; v[2] = v[2] / sig; v[3] = v[3] / sig; return v; }
+// element (c, rs, o) of the data-gradient image [Cin][R][S][rows_out]: taps flipped unless the layer says otherwise
+__device__ __forceinline__ long long sn_dgrad_idx(const sg_sn_layer& l, int c, int rs, int o) { return ((long long)c * l.RS + (l.dgrad_noflip ? rs : (l.RS - 1 - rs))) * sn_rows_out(l) + o; }
 
 // Flat work tables (round 6). The launches below used to be (tiles of the LARGEST layer) x layers: a table that holds [1536 x 13824] convolutions next to [96 x 864] ones, a
 // [24576 x 20] linear layer and a [1000 x 1536] embedding is mostly empty workgroups (and needed two calls to keep the linear layers from inflating the convolutions' grids).
@@ -32,7 +43,13 @@ __device__ __forceinline__ int sn_find(const sn_flat& F, int b) {     // the lay
   while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (b >= F.start[mid]) lo = mid; else hi = mid; }
   return lo;
 }
-__host__ __device__ __forceinline__ bool sn_wtu_skinny(const sg_sn_layer& l) { return !l.trans && (l.cols & 3) == 0 && l.cols <= 64 && ((uintptr_t)l.w & 15) == 0; }
+template <class COUNT> static sn_flat sn_flat_of(const sg_sn_layer* layers_host, int n, COUNT tiles) {      // host: the table of a launch whose layer l has tiles(l) workgroups
+  sn_flat F;
+  F.n = n; F.start[0] = 0;
+  for (int i = 0; i < n; i++) F.start[i + 1] = F.start[i] + tiles(layers_host[i]);
+  return F;
+}
+__host__ __device__ __forceinline__ bool sn_wtu_skinny(const sg_sn_layer& l) { return sn_rows16(l) && l.cols <= 64; }
 
 // flat grid of (col tiles of 1024) x SN_SPLITS per power-iterating layer: partial[split][k] = sum over the split's rows of W[o][k] u[o].
 // A thread owns 4 adjacent columns (one 16-byte load per row, 4 KB contiguous per row and block) and keeps 8 rows in flight (16 measured SLOWER, 129 -> 153 us per launch, session r3n): the
@@ -74,7 +91,7 @@ __global__ __launch_bounds__(256) void k_sn_wtu(const sg_sn_layer* L, float* wor
     }
     return;
   }
-  if (!l.trans && (l.cols & 3) == 0 && ((uintptr_t)l.w & 15) == 0) {
+  if (sn_rows16(l)) {
     const int k = (bx * 256 + threadIdx.x) * 4;
     if (k >= l.cols) return;
     const float* wp = l.w + k;
@@ -113,6 +130,19 @@ __device__ __forceinline__ float block_sum_nt(float v, float* sm /* SN_NT / 64 f
   for (int w = 1; w < SN_NT / 64; w++) t += sm[w];
   return t;
 }
+// The block's walk of a vector: use(i, src[i], i < n) for i = threadIdx.x, + SN_NT, ... in ascending order, the eight loads of a trip issued before the first is used; a
+// slot past the end carries 0.f and `false`, which a sum may add without asking (k_sn_u's norm does: its squares are then rounded before they are added). One
+// load -> use per trip (the vectors may alias as far as the compiler knows) was 54 dependent round trips on a 13824-column layer, most of k_sn_u's 48 us, and 96 on a
+// 24576-row linear layer, most of its 67 us on the generator's linear table (round 6 trace of tools/sn_bench.py).
+template <class USE> __device__ __forceinline__ void sn_walk8(const float* src, int n, USE use) {
+  for (int i0 = threadIdx.x; i0 < n; i0 += SN_NT * 8) {
+    float t[8];
+#pragma unroll
+    for (int e = 0; e < 8; e++) { const int i = i0 + SN_NT * e; t[e] = i < n ? src[i] : 0.f; }
+#pragma unroll
+    for (int e = 0; e < 8; e++) { const int i = i0 + SN_NT * e; use(i, t[e], i < n); }
+  }
+}
 // grid (layers): v = normalize(sum of partials)
 __global__ __launch_bounds__(SN_NT) void k_sn_v(const sg_sn_layer* L, float* work, float eps) {
   __shared__ float sm[SN_NT / 64];
@@ -129,13 +159,7 @@ __global__ __launch_bounds__(SN_NT) void k_sn_v(const sg_sn_layer* L, float* wor
   }
   nn = block_sum_nt(nn, sm);
   const float inv = 1.f / fmaxf(sqrtf(nn), eps);
-  for (int k0 = threadIdx.x; k0 < l.cols; k0 += SN_NT * 8) {
-    float t[8];
-#pragma unroll
-    for (int e = 0; e < 8; e++) { const int k = k0 + SN_NT * e; t[e] = k < l.cols ? part[k] : 0.f; }
-#pragma unroll
-    for (int e = 0; e < 8; e++) { const int k = k0 + SN_NT * e; if (k < l.cols) l.v[k] = t[e] * inv; }
-  }
+  sn_walk8(part, l.cols, [&](int k, float t, bool in) { if (in) l.v[k] = t * inv; });
 }
 // flat grid of (row tiles of 4) per SN layer: one wave per row, t_u[o] = W[o,:] . v
 __global__ __launch_bounds__(256) void k_sn_wv(const sg_sn_layer* L, float* work, const sn_flat F) {
@@ -146,7 +170,7 @@ __global__ __launch_bounds__(256) void k_sn_wv(const sg_sn_layer* L, float* work
   if (o >= l.rows) return;
   const int lane = threadIdx.x & 63;
   float acc = 0.f;
-  if (!l.trans && (l.cols & 3) == 0 && ((uintptr_t)l.w & 15) == 0 && ((uintptr_t)l.v & 15) == 0) {
+  if (sn_rows16(l) && sn_al16(l.v)) {
     // 16 bytes per lane, four loads of the row in flight (round 3: the 4-byte walk moved the 352 MB of D's weights at 2.7 TB/s)
     const float* wr = l.w + (long long)o * l.cols;
     f32x4 a4 = {0.f, 0.f, 0.f, 0.f};
@@ -171,27 +195,13 @@ __global__ __launch_bounds__(SN_NT) void k_sn_u(const sg_sn_layer* L, float* wor
   if (!l.apply_sn) { if (threadIdx.x == 0) l.sigma[0] = 1.f; return; }
   const float* tu = work + l.work_off + (long long)SN_SPLITS * l.cols;
   float sig;
-  if (l.do_power_iter) {
-    // (eight loads in flight per thread: a 24576-row linear layer is 96 trips of this one block; one load per trip was most of the kernel's 67 us on the
-    // generator's linear table -- round 6 trace of tools/sn_bench.py. Same per-thread summation order.)
+  if (l.do_power_iter) {      // (sn_walk8: the per-thread summation order of a one-load-per-trip walk)
     float nn = 0.f;
-    for (int o0 = threadIdx.x; o0 < l.rows; o0 += SN_NT * 8) {
-      float t[8];
-#pragma unroll
-      for (int e = 0; e < 8; e++) { const int o = o0 + SN_NT * e; t[e] = o < l.rows ? tu[o] : 0.f; }
-#pragma unroll
-      for (int e = 0; e < 8; e++) nn += t[e] * t[e];
-    }
+    sn_walk8(tu, l.rows, [&](int, float t, bool) { nn += t * t; });
     nn = block_sum_nt(nn, sm);
     const float inv = 1.f / fmaxf(sqrtf(nn), eps);
     float dot = 0.f;
-    for (int o0 = threadIdx.x; o0 < l.rows; o0 += SN_NT * 8) {
-      float t[8];
-#pragma unroll
-      for (int e = 0; e < 8; e++) { const int o = o0 + SN_NT * e; t[e] = o < l.rows ? tu[o] : 0.f; }
-#pragma unroll
-      for (int e = 0; e < 8; e++) { const int o = o0 + SN_NT * e; if (o < l.rows) { const float un = t[e] * inv; l.u[o] = un; dot += un * t[e]; } }
-    }
+    sn_walk8(tu, l.rows, [&](int o, float t, bool in) { if (in) { const float un = t * inv; l.u[o] = un; dot += un * t; } });
     sig = block_sum_nt(dot, sm);
   } else {
     float dot = 0.f;
@@ -199,31 +209,13 @@ __global__ __launch_bounds__(SN_NT) void k_sn_u(const sg_sn_layer* L, float* wor
     sig = block_sum_nt(dot, sm);
   }
   if (threadIdx.x == 0) l.sigma[0] = sig;
-  if (l.u_snap) {
-    for (int o0 = threadIdx.x; o0 < l.rows; o0 += SN_NT * 8) {
-      float t[8];
-#pragma unroll
-      for (int e = 0; e < 8; e++) { const int o = o0 + SN_NT * e; t[e] = o < l.rows ? l.u[o] : 0.f; }
-#pragma unroll
-      for (int e = 0; e < 8; e++) { const int o = o0 + SN_NT * e; if (o < l.rows) l.u_snap[o] = t[e]; }
-    }
-  }
-  if (l.v_snap) {
-    // eight loads in flight per thread: one load -> store per iteration (the two vectors may alias as far as the compiler knows) was 54
-    // dependent round trips on a 13824-column layer, most of this kernel's 48 us
-    for (int k0 = threadIdx.x; k0 < l.cols; k0 += SN_NT * 8) {
-      float t[8];
-#pragma unroll
-      for (int e = 0; e < 8; e++) { const int k = k0 + SN_NT * e; t[e] = k < l.cols ? l.v[k] : 0.f; }
-#pragma unroll
-      for (int e = 0; e < 8; e++) { const int k = k0 + SN_NT * e; if (k < l.cols) l.v_snap[k] = t[e]; }
-    }
-  }
+  if (l.u_snap) sn_walk8(l.u, l.rows, [&](int o, float t, bool in) { if (in) l.u_snap[o] = t; });
+  if (l.v_snap) sn_walk8(l.v, l.cols, [&](int k, float t, bool in) { if (in) l.v_snap[k] = t; });
 }
-// grid (element tiles, layers): W / sigma -> operand images
+// grid (element tiles, layers): W / sigma -> operand images. The fallback of a table with a row too wide for k_sn_pack_rows' LDS row buffer (scattered 2-byte stores).
 template <typename T> __global__ __launch_bounds__(256) void k_sn_pack(const sg_sn_layer* L) {
   const sg_sn_layer l = L[blockIdx.y];
-  const int rows_out = l.rows_pad > l.rows ? l.rows_pad : l.rows;
+  const int rows_out = sn_rows_out(l), cp = sn_cin_pitch(l);
   const long long total = (long long)rows_out * l.cols;
   const float sig = l.sigma[0];
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -233,9 +225,17 @@ template <typename T> __global__ __launch_bounds__(256) void k_sn_pack(const sg_
     if (o < l.rows) {
       val = l.w[sn_widx(l, o, k)] / sig;
       if (l.w_f32) l.w_f32[i] = val;
-      if (l.w_dgrad) ((T*)l.w_dgrad)[((long long)c * l.RS + (l.dgrad_noflip ? rs : (l.RS - 1 - rs))) * rows_out + o] = from_f<T>(val);
+      if (l.w_dgrad) ((T*)l.w_dgrad)[sn_dgrad_idx(l, c, rs, o)] = from_f<T>(val);
     }
-    if (l.w_fwd) ((T*)l.w_fwd)[((long long)o * l.RS + rs) * (l.Cin_pad > l.Cin ? l.Cin_pad : l.Cin) + c] = from_f<T>(val);
+    if (l.w_fwd) ((T*)l.w_fwd)[((long long)o * l.RS + rs) * cp + c] = from_f<T>(val);
+  }
+  if (l.w_fwd && cp > l.Cin) {      // the padding channels of the forward image: zero, as include/sgamd.h says and k_sn_pack_rows writes them
+    const int pad = cp - l.Cin;
+    const long long ptotal = (long long)rows_out * l.RS * pad;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < ptotal; i += (long long)gridDim.x * 256) {
+      const long long ors = i / pad;
+      ((T*)l.w_fwd)[ors * cp + l.Cin + (int)(i - ors * pad)] = from_f<T>(0.f);
+    }
   }
 }
 
@@ -249,23 +249,19 @@ template <typename T> __global__ __launch_bounds__(256) void k_sn_pack_rows(cons
   const int li = sn_find(F, blockIdx.x);
   const sg_sn_layer l = L[li];
   const int nblk = F.start[li + 1] - F.start[li];          // workgroups of this layer (<= 2048: rows beyond that are walked)
-  const int rows_out = l.rows_pad > l.rows ? l.rows_pad : l.rows;
+  const int rows_out = sn_rows_out(l);
   const float sig = l.sigma[0];
-  const float inv = 1.f / sig;
-  const int cp = l.Cin_pad > l.Cin ? l.Cin_pad : l.Cin, colsp = l.RS * cp;
+  const int cp = sn_cin_pitch(l), colsp = l.RS * cp;
   // fast path (round 2): 16-byte global accesses on both sides and no per-element division -- the read side takes 4 fp32 per lane,
   // the write side 8 outputs of one tap (cp % 8 == 0: eight consecutive image elements share their tap), gathered from the LDS row
-  const bool vec = !l.trans && (l.cols % 4 == 0) && (cp % 8 == 0) && sizeof(T) == 2 && ((reinterpret_cast<uintptr_t>(l.w) & 15) == 0) &&
-                   (!l.w_f32 || (reinterpret_cast<uintptr_t>(l.w_f32) & 15) == 0) && (!l.w_fwd || (reinterpret_cast<uintptr_t>(l.w_fwd) & 15) == 0);
+  const bool vec = sn_rows16(l) && (cp % 8 == 0) && sizeof(T) == 2 && (!l.w_f32 || sn_al16(l.w_f32)) && (!l.w_fwd || sn_al16(l.w_fwd));
   for (int o = blockIdx.x - F.start[li]; o < rows_out; o += nblk) {
     if (vec) {
       const float* src = l.w + (long long)o * l.cols;
       for (int k = threadIdx.x * 4; k < l.cols; k += 1024) {
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (o < l.rows) {
-          v = *(const f32x4*)(src + k);
-          // same operation as the scalar path (a division, not a multiplication by the reciprocal: bit-identical images)
-          v[0] = v[0] / sig; v[1] = v[1] / sig; v[2] = v[2] / sig; v[3] = v[3] / sig;
+          v = sn_div4(*(const f32x4*)(src + k), sig);
           if (l.w_f32) *(f32x4*)(l.w_f32 + (long long)o * l.cols + k) = v;
         }
         u32x2 pk = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
@@ -311,17 +307,29 @@ template <typename T> __global__ __launch_bounds__(256) void k_sn_pack_rows(cons
     }
     __syncthreads();
   }
-  (void)inv;
 }
 // The data-gradient image of a layer whose forward image [o][rs][c] was just written by k_sn_pack_rows is a transposition of THAT image (the same bf16 values, 2 bytes
 // read per element instead of the master's 4, no division): `elem` = bytes per image element.
 __host__ __device__ __forceinline__ bool sn_dgrad_from_image(const sg_sn_layer& l, int elem) {
-  const int rows_out = l.rows_pad > l.rows ? l.rows_pad : l.rows, cp = l.Cin_pad > l.Cin ? l.Cin_pad : l.Cin;
-  return elem == 2 && l.w_fwd && !l.trans && (rows_out % 8 == 0) && (cp % 8 == 0) && ((reinterpret_cast<uintptr_t>(l.w_fwd) & 15) == 0) &&
-         ((reinterpret_cast<uintptr_t>(l.w_dgrad) & 15) == 0);
+  return elem == 2 && l.w_fwd && !l.trans && (sn_rows_out(l) % 8 == 0) && (sn_cin_pitch(l) % 8 == 0) && sn_al16(l.w_fwd) && sn_al16(l.w_dgrad);
 }
 __host__ __device__ __forceinline__ int sn_dgrad_extent(const sg_sn_layer& l, int elem) {      // columns the 128-wide tiles of a layer walk
-  return sn_dgrad_from_image(l, elem) ? l.RS * (l.Cin_pad > l.Cin ? l.Cin_pad : l.Cin) : l.cols;
+  return sn_dgrad_from_image(l, elem) ? l.RS * sn_cin_pitch(l) : l.cols;
+}
+// 16-byte write phase of k_sn_pack_dgrad's bf16 tile at (o0, k0): a thread gathers eight couts of one column from LDS, packs four words, issues one store.
+// split(j, c, rs) takes column j < ncols apart in the order the tile was read in and says whether the column is stored at all.
+template <class SPLIT> __device__ __forceinline__ void sn_dgrad_store8(const sg_sn_layer& l, const bf16_t* tp /* [64][130] */, int o0, int k0, int ncols, SPLIT split) {
+  for (int e = threadIdx.x; e < 8 * 128; e += 256) {
+    const int og = e & 7, jj = e >> 3, o = o0 + og * 8, j = k0 + jj;
+    int c, rs;
+    if (j < ncols && o < sn_rows_out(l) && split(j, c, rs)) {
+      uint32_t w4[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) w4[i] = (uint32_t)tp[(og * 8 + 2 * i) * 130 + jj] | ((uint32_t)tp[(og * 8 + 2 * i + 1) * 130 + jj] << 16);
+      u32x4 v = {w4[0], w4[1], w4[2], w4[3]};
+      *(u32x4*)((bf16_t*)l.w_dgrad + sn_dgrad_idx(l, c, rs, o)) = v;
+    }
+  }
 }
 template <typename T> __global__ __launch_bounds__(256) void k_sn_pack_dgrad(const sg_sn_layer* L, const sn_flat F) {
   __shared__ T tile[64][130];
@@ -332,9 +340,9 @@ template <typename T> __global__ __launch_bounds__(256) void k_sn_pack_dgrad(con
   const int tiles_k = (sn_dgrad_extent(l, (int)sizeof(T)) + 127) >> 7, local = blockIdx.x - F.start[li];
   const int by = local / tiles_k, bx = local - by * tiles_k;
   const int o0 = by * 64, k0 = bx * 128;
-  const int rows_out = l.rows_pad > l.rows ? l.rows_pad : l.rows;    // pitch of the image; columns >= rows stay zero
+  const int rows_out = sn_rows_out(l);    // pitch of the image; columns >= rows stay zero
   if (img) {      // (tiles over rows_out: the zero rows of the forward image's padding become the zero columns of this one)
-    const int cp = l.Cin_pad > l.Cin ? l.Cin_pad : l.Cin, colsp = l.RS * cp;
+    const int cp = sn_cin_pitch(l), colsp = l.RS * cp;
     for (int e = threadIdx.x; e < 64 * 16; e += 256) {
       const int oo = e >> 4, jj = (e & 15) * 8, o = o0 + oo, j = k0 + jj;
       u32x4 v = {0u, 0u, 0u, 0u};
@@ -343,35 +351,18 @@ template <typename T> __global__ __launch_bounds__(256) void k_sn_pack_dgrad(con
       tp[0] = v[0]; tp[1] = v[1]; tp[2] = v[2]; tp[3] = v[3];
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < 8 * 128; e += 256) {
-      const int og = e & 7, jj = e >> 3, o = o0 + og * 8, j = k0 + jj;
-      if (j < colsp && o < rows_out) {
-        const int rs = j / cp, c = j - rs * cp;
-        if (c < l.Cin) {
-          const bf16_t* tp = (const bf16_t*)&tile[0][0];
-          uint32_t w4[4];
-#pragma unroll
-          for (int i = 0; i < 4; i++) w4[i] = (uint32_t)tp[(og * 8 + 2 * i) * 130 + jj] | ((uint32_t)tp[(og * 8 + 2 * i + 1) * 130 + jj] << 16);
-          u32x4 v = {w4[0], w4[1], w4[2], w4[3]};
-          *(u32x4*)((bf16_t*)l.w_dgrad + ((long long)c * l.RS + (l.dgrad_noflip ? rs : (l.RS - 1 - rs))) * rows_out + o) = v;
-        }
-      }
-    }
+    sn_dgrad_store8(l, (const bf16_t*)&tile[0][0], o0, k0, colsp, [&](int j, int& c, int& rs) { rs = j / cp; c = j - rs * cp; return c < l.Cin; });
     return;
   }
   if (o0 >= l.rows || k0 >= l.cols) return;
   const float sig = l.sigma[0];
   // fast path (round 2): 16-byte accesses on both sides -- 4 fp32 per lane in, 8 couts of one (c, tap) row per lane out
-  const bool vec = sizeof(T) == 2 && !l.trans && (l.cols % 4 == 0) && (rows_out % 8 == 0) && ((reinterpret_cast<uintptr_t>(l.w) & 15) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(l.w_dgrad) & 15) == 0);
+  const bool vec = sizeof(T) == 2 && sn_rows16(l) && (rows_out % 8 == 0) && sn_al16(l.w_dgrad);
   if (vec) {
     for (int e = threadIdx.x; e < 64 * 32; e += 256) {
       const int oo = e >> 5, kk = (e & 31) * 4, o = o0 + oo, k = k0 + kk;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (o < l.rows && k < l.cols) {
-        v = *(const f32x4*)(l.w + (long long)o * l.cols + k);
-        v[0] = v[0] / sig; v[1] = v[1] / sig; v[2] = v[2] / sig; v[3] = v[3] / sig;     // the scalar path's operation: bit-identical images
-      }
+      if (o < l.rows && k < l.cols) v = sn_div4(*(const f32x4*)(l.w + (long long)o * l.cols + k), sig);
       bf16_t* tp = (bf16_t*)&tile[oo][kk];
       *(uint32_t*)tp = pack2bf(v[0], v[1]);
       *(uint32_t*)(tp + 2) = pack2bf(v[2], v[3]);
@@ -387,40 +378,24 @@ template <typename T> __global__ __launch_bounds__(256) void k_sn_pack_dgrad(con
   }
   __syncthreads();
   if (vec) {
-    for (int e = threadIdx.x; e < 8 * 128; e += 256) {
-      const int og = e & 7, kk = e >> 3, o = o0 + og * 8, k = k0 + kk;
-      if (k < l.cols && o < rows_out) {
-        const int c = k / l.RS, rs = k - c * l.RS;
-        const bf16_t* tp = (const bf16_t*)&tile[0][0];
-        uint32_t w4[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) w4[i] = (uint32_t)tp[(og * 8 + 2 * i) * 130 + kk] | ((uint32_t)tp[(og * 8 + 2 * i + 1) * 130 + kk] << 16);
-        u32x4 v = {w4[0], w4[1], w4[2], w4[3]};
-        *(u32x4*)((bf16_t*)l.w_dgrad + ((long long)c * l.RS + (l.dgrad_noflip ? rs : (l.RS - 1 - rs))) * rows_out + o) = v;
-      }
-    }
+    sn_dgrad_store8(l, (const bf16_t*)&tile[0][0], o0, k0, l.cols, [&](int k, int& c, int& rs) { c = k / l.RS; rs = k - c * l.RS; return true; });
   } else {
     const int oo = threadIdx.x & 63, o = o0 + oo;
     for (int p = 0; p < 32; p++) {
       const int kk = p * 4 + (threadIdx.x >> 6), k = k0 + kk;
       if (k < l.cols && o < l.rows) {
         const int c = k / l.RS, rs = k - c * l.RS;
-        ((T*)l.w_dgrad)[((long long)c * l.RS + (l.dgrad_noflip ? rs : (l.RS - 1 - rs))) * rows_out + o] = tile[oo][kk];
+        ((T*)l.w_dgrad)[sn_dgrad_idx(l, c, rs, o)] = tile[oo][kk];
       }
     }
   }
 }
-template <typename T> static void sn_pack_launch(const sg_sn_layer* layers_dev, const sg_sn_layer* layers_host, int n, int max_rows_out, int max_rows, int max_cols, long long max_elems, hipStream_t st) {
+template <typename T> static void sn_pack_launch(const sg_sn_layer* layers_dev, const sg_sn_layer* layers_host, int n, int max_cols, long long max_elems, hipStream_t st) {
   if ((size_t)max_cols * sizeof(T) <= 60 * 1024) {
-    sn_flat Fr, Fd;
-    Fr.n = Fd.n = n; Fr.start[0] = Fd.start[0] = 0;
-    for (int i = 0; i < n; i++) {
-      const sg_sn_layer& l = layers_host[i];
-      const int ro = l.rows_pad > l.rows ? l.rows_pad : l.rows;
-      Fr.start[i + 1] = Fr.start[i] + (ro > 2048 ? 2048 : ro);
-      const bool img = sn_dgrad_from_image(l, (int)sizeof(T));
-      Fd.start[i + 1] = Fd.start[i] + (l.w_dgrad ? ((sn_dgrad_extent(l, (int)sizeof(T)) + 127) / 128) * (((img ? ro : l.rows) + 63) / 64) : 0);
-    }
+    const int es = (int)sizeof(T);
+    const sn_flat Fr = sn_flat_of(layers_host, n, [](const sg_sn_layer& l) { return sn_rows_out(l) > 2048 ? 2048 : sn_rows_out(l); });
+    const sn_flat Fd = sn_flat_of(layers_host, n, [es](const sg_sn_layer& l) {
+      return l.w_dgrad ? ((sn_dgrad_extent(l, es) + 127) / 128) * (((sn_dgrad_from_image(l, es) ? sn_rows_out(l) : l.rows) + 63) / 64) : 0; });
     hipLaunchKernelGGL(k_sn_pack_rows<T>, dim3(Fr.start[n]), dim3(256), (size_t)max_cols * sizeof(T), st, layers_dev, Fr);
     if (Fd.start[n] > 0) hipLaunchKernelGGL(k_sn_pack_dgrad<T>, dim3(Fd.start[n]), dim3(256), 0, st, layers_dev, Fd);
   } else {
@@ -431,37 +406,31 @@ template <typename T> static void sn_pack_launch(const sg_sn_layer* layers_dev, 
 
 // layers [i0, i1) of a table: the launch sequence of one forward (power iteration, sigma, operand images)
 template <typename T> static void sn_forward_range(const sg_sn_layer* layers_dev, const sg_sn_layer* layers_host, int n, float eps, float* work, hipStream_t st) {
-  int max_rows = 1, max_cols = 1, max_rows_out = 1; long long max_elems = 1; bool any_sn = false, any_pi = false;
+  int max_cols = 1; long long max_elems = 1; bool any_sn = false, any_pi = false;
   for (int i = 0; i < n; i++) {
     const sg_sn_layer& l = layers_host[i];
     if (l.apply_sn) { any_sn = true; if (l.do_power_iter) any_pi = true; }
-    if (l.rows > max_rows) max_rows = l.rows;
     if (l.cols > max_cols) max_cols = l.cols;
-    const int ro = l.rows_pad > l.rows ? l.rows_pad : l.rows;
-    if (ro > max_rows_out) max_rows_out = ro;
-    const long long e = (long long)ro * l.cols;
+    const long long e = (long long)sn_rows_out(l) * l.cols;
     if (e > max_elems) max_elems = e;
   }
-  sn_flat Fu, Fv;
-  Fu.n = Fv.n = n; Fu.start[0] = Fv.start[0] = 0;
-  for (int i = 0; i < n; i++) {
-    const sg_sn_layer& l = layers_host[i];
-    Fu.start[i + 1] = Fu.start[i] + (l.apply_sn && l.do_power_iter ? ((l.cols + 1023) / 1024) * SN_SPLITS : 0);
-    Fv.start[i + 1] = Fv.start[i] + (l.apply_sn ? (l.rows + 3) / 4 : 0);
-  }
+  const sn_flat Fu = sn_flat_of(layers_host, n, [](const sg_sn_layer& l) { return l.apply_sn && l.do_power_iter ? ((l.cols + 1023) / 1024) * SN_SPLITS : 0; });
+  const sn_flat Fv = sn_flat_of(layers_host, n, [](const sg_sn_layer& l) { return l.apply_sn ? (l.rows + 3) / 4 : 0; });
   if (any_pi) {
     hipLaunchKernelGGL(k_sn_wtu, dim3(Fu.start[n]), dim3(256), 0, st, layers_dev, work, Fu);
     hipLaunchKernelGGL(k_sn_v, dim3(n), dim3(SN_NT), 0, st, layers_dev, work, eps);
   }
   if (any_sn) hipLaunchKernelGGL(k_sn_wv, dim3(Fv.start[n]), dim3(256), 0, st, layers_dev, work, Fv);
   hipLaunchKernelGGL(k_sn_u, dim3(n), dim3(SN_NT), 0, st, layers_dev, work, eps);
-  sn_pack_launch<T>(layers_dev, layers_host, n, max_rows_out, max_rows, max_cols, max_elems, st);
+  sn_pack_launch<T>(layers_dev, layers_host, n, max_cols, max_elems, st);
 }
 // (Round 5, measured and removed: walking the table in runs of layers that fit the 256 MB Infinity Cache, each run through its whole launch sequence, so that the
 // later passes of a run would find its weights on the die -- SLOWER on the D table, forward 430 -> 512 us and backward 588 -> 1177 us: the extra launches cost
-// more than the cache returns. What does pay is keeping layers of very different shapes out of one launch: the grids are sized by the largest layer of the
+// more than the cache returns. What paid THEN was keeping layers of very different shapes out of one launch: the grids were sized by the largest layer of the
 // table, and one [24576 x 20] linear layer next to [1536 x 13824] convolutions turned k_sn_pack_dgrad into 1.7 M workgroups, all but 50 k of them empty
-// (generator forward 869 us): bank.py hands the convolutions and the linear / embedding layers over as separate tables.)
+// (generator forward 869 us), so bank.py handed convolutions and linear / embedding layers over as separate tables. The flat tables above (round 6) ended that:
+// any mix of shapes shares one call, bank.py hands a network over as ONE table. Still sized by a table's largest layer: the LDS row buffer of k_sn_pack_rows
+// (with it the choice of the fallback k_sn_pack) and the (tiles, layers) grids of k_sn_pack and k_snb_apply.)
 extern "C" int sg_sn_forward(int dtype, const sg_sn_layer* layers_dev, const sg_sn_layer* layers_host, int n, float eps, float* work, long long work_floats, sg_stream_t s) {
   SG_CHECK(layers_dev && layers_host && n > 0 && work, "sg_sn_forward: bad args");
   SG_CHECK(dtype == SG_DTYPE_F32 || dtype == SG_DTYPE_BF16, "sg_sn_forward: bad dtype");
@@ -497,7 +466,18 @@ __device__ __forceinline__ long long snb_src_index(const sg_sn_bwd_layer& l, int
   if (l.natural == 1) return (long long)o * l.cols + k;
   const int c = k / l.RS, rs = k - c * l.RS;
   if (l.natural == 2) return ((long long)c * l.RS + rs) * l.rows + o;   // [Cin][R][S][Cout]: weight gradient of a transposed conv
-  return ((long long)o * l.RS + rs) * (l.Cin_pad > l.Cin ? l.Cin_pad : l.Cin) + c;
+  return ((long long)o * l.RS + rs) * sn_cin_pitch(l) + c;
+}
+// <dWt, W> of layer blockIdx.y: the fixed-order sum of its nb block partials, spread over the first wave (every block computes the same value). Called by the whole block.
+__device__ __forceinline__ float snb_coef(const float* work, int nb, float* coef_sm /* one float of LDS */) {
+  if (threadIdx.x < 64) {
+    float t = 0.f;
+    for (int b = threadIdx.x; b < nb; b += 64) t += work[(long long)blockIdx.y * nb + b];
+    t = wave_sum(t);
+    if (threadIdx.x == 0) *coef_sm = t;
+  }
+  __syncthreads();
+  return *coef_sm;
 }
 // ---- tile kernels (round 2) ---------------------------------------------------------------------------------------------------
 // k_snb_dot / k_snb_apply walk a flat element index with a 64-bit division per element and fetch the two layouts of a weight
@@ -521,8 +501,12 @@ __host__ __device__ __forceinline__ bool snb_row_ok(const sg_sn_bwd_layer& l) {
   if (l.trans) return false;
   if (l.natural == 1) return true;
   if (l.natural != 0) return false;
-  const int cp = l.Cin_pad > l.Cin ? l.Cin_pad : l.Cin;
-  return (cp % 4 == 0) && ((reinterpret_cast<uintptr_t>(l.dwt) & 15) == 0) && l.RS <= 16;
+  return (sn_cin_pitch(l) % 4 == 0) && sn_al16(l.dwt) && l.RS <= 16;
+}
+// k_snb_rows' element: g = the gradient of master element i (column k of its row, whose u times coef is uo) -> its term of <dWt, W>, or its dw
+template <bool APPLY> __device__ __forceinline__ void snb_elem(const sg_sn_bwd_layer& l, long long i, int k, float g, float uo, float inv, float& acc) {
+  if (APPLY) l.dw[i] += l.apply_sn ? (g - uo * l.v[k]) * inv : g;
+  else acc += g * l.w[i];
 }
 // grid (SNB_BLOCKS, layers); APPLY = false: block partials of <dWt, W> into work; true: dw += (dWt - coef u v^T) / sigma
 template <bool APPLY> __global__ __launch_bounds__(256) void k_snb_rows(const sg_sn_bwd_layer* L, float* work, int nb) {
@@ -535,14 +519,7 @@ template <bool APPLY> __global__ __launch_bounds__(256) void k_snb_rows(const sg
   float sig = 1.f, coef = 0.f;
   if (APPLY && l.apply_sn) {
     sig = l.sigma[0];
-    if (threadIdx.x < 64) {      // fixed-order sum of the block partials (every block computes the same value)
-      float t = 0.f;
-      for (int b = threadIdx.x; b < nb; b += 64) t += work[(long long)blockIdx.y * nb + b];
-      t = wave_sum(t);
-      if (threadIdx.x == 0) coef_sm = t;
-    }
-    __syncthreads();
-    coef = coef_sm / sig;        // <dWt, W/sigma>
+    coef = snb_coef(work, nb, &coef_sm) / sig;        // <dWt, W/sigma>
   }
   const float inv = 1.f / sig;
   const int RS = l.RS, cols = l.cols;
@@ -555,14 +532,10 @@ template <bool APPLY> __global__ __launch_bounds__(256) void k_snb_rows(const sg
       const int o = it / nch, k0 = (it - o * nch) * 1024;
       const long long base = (long long)o * cols;
       const float uo = (APPLY && l.apply_sn) ? l.u[o] * coef : 0.f;
-      for (int k = k0 + threadIdx.x; k < cols && k < k0 + 1024; k += 256) {
-        const float g = l.dwt[base + k];
-        if (APPLY) l.dw[base + k] += l.apply_sn ? (g - uo * l.v[k]) * inv : g;
-        else acc += g * l.w[base + k];
-      }
+      for (int k = k0 + threadIdx.x; k < cols && k < k0 + 1024; k += 256) snb_elem<APPLY>(l, base + k, k, l.dwt[base + k], uo, inv, acc);
     }
   } else {
-    const int cp = l.Cin_pad > l.Cin ? l.Cin_pad : l.Cin;
+    const int cp = sn_cin_pitch(l);
     const int nch = (l.Cin + SNB_CW - 1) / SNB_CW;               // chunks of real channels (padding channels carry no gradient)
     const int items = l.rows * nch;
     // per-thread walks: master order k' = c RS + rs (k' += 256) and image order j = rs SNB_CW + c (4 floats per step, j += 1024)
@@ -588,9 +561,7 @@ template <bool APPLY> __global__ __launch_bounds__(256) void k_snb_rows(const sg
       const int kn = cwr * RS;
       int c = c_init, rs = rs_init;
       for (int k = threadIdx.x; k < kn; k += 256) {
-        const float g = tile[rs * SNB_ST + c];
-        if (APPLY) l.dw[base + k] += l.apply_sn ? (g - uo * l.v[c0 * RS + k]) * inv : g;
-        else acc += g * l.w[base + k];
+        snb_elem<APPLY>(l, base + k, c0 * RS + k, tile[rs * SNB_ST + c], uo, inv, acc);
         c += dc; rs += drs;
         if (rs >= RS) { rs -= RS; c++; }
       }
@@ -609,8 +580,7 @@ __global__ __launch_bounds__(256) void k_snb_dot(const sg_sn_bwd_layer* L, float
   if (!l.apply_sn || snb_row_ok(l)) return;
   const long long total = (long long)l.rows * l.cols;
   float acc = 0.f;
-  const int cp = l.Cin_pad > l.Cin ? l.Cin_pad : l.Cin;
-  if (l.natural == 0 && cp == l.Cin) {
+  if (l.natural == 0 && sn_cin_pitch(l) == l.Cin) {
     // walk dwt in ITS order ([o][rs][c], contiguous reads of the big scratch) and gather w ([o][c][rs], L2-friendly 9-float strides)
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += nb * 256ll) {
       const int o = (int)(i / l.cols), j = (int)(i % l.cols);
@@ -628,24 +598,14 @@ __global__ __launch_bounds__(256) void k_snb_dot(const sg_sn_bwd_layer* L, float
 }
 // grid (tiles, layers)
 __global__ __launch_bounds__(256) void k_snb_apply(const sg_sn_bwd_layer* L, const float* work, int nb) {
+  __shared__ float coef_sm;
   const sg_sn_bwd_layer l = L[blockIdx.y];
   if (snb_row_ok(l)) return;
   const long long total = (long long)l.rows * l.cols;
   float sig = 1.f, coef = 0.f;
   if (l.apply_sn) {
     sig = l.sigma[0];
-    float d = 0.f;
-    // fixed-order sum of the block partials, spread over the first wave (every block computes the same value)
-    __shared__ float coef_sm;
-    if (threadIdx.x < 64) {
-      float t = 0.f;
-      for (int b = threadIdx.x; b < nb; b += 64) t += work[(long long)blockIdx.y * nb + b];
-      t = wave_sum(t);
-      if (threadIdx.x == 0) coef_sm = t;
-    }
-    __syncthreads();
-    d = coef_sm;
-    coef = d / sig;  // <dWt, W/sigma>
+    coef = snb_coef(work, nb, &coef_sm) / sig;  // <dWt, W/sigma>
   }
   const float inv = 1.f / sig;
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {

@@ -23,6 +23,23 @@ LAYERS = [
     ("conv", 32, 16, 3, {"apply_sn": False}),                # plain layer: images with sigma = 1
     ("conv", 48, 32, 3, {"power_iter": False}),              # eval mode: sigma from the stored u, v, no iteration
     ("conv", 8, 1536, 3, {}),                                # 13824 columns: the k_sn_wtu column tiling and the 8-deep v copy
+    ("conv", 16, 4, 3, {"cin_pad": 8}),                      # cols % 4 == 0, pitch % 8 == 0 and Cin < pitch at once: the zero-filling lanes of k_sn_pack_rows' vector path,
+                                                             # the c < Cin skip of k_sn_pack_dgrad's from-image path, cw != cwr in k_snb_rows
+    ("conv", 12, 3, 5, {"cin_pad": 8}),                      # RS = 25 > 16 with a padded gradient pitch: the second walk of k_snb_dot, snb_src_index's third branch in k_snb_apply
+    ("linear", 2500, 8, 1, {}),                              # rows > 1024: a thread of k_sn_u's row walks (norm, u, u_snap) sums / copies more than one element
+    ("linear", 9000, 4, 1, {}),                              # rows > 8192: a second trip of those walks
+]
+# A table with one layer whose row does not fit k_sn_pack_rows' 60 KB LDS row buffer: the whole TABLE takes the fallback k_sn_pack (the choice is per table, which is why
+# these rows are not part of LAYERS: one wide layer there would take the tiled pack kernels out of that test).
+WIDE_LAYERS = [
+    ("conv", 2, 3416, 3, {}),                                # 30744 columns: 61488 B in bf16 > the 60 KB row buffer in both dtypes; a last column tile of 24
+    ("conv", 3, 8, 3, {"rows_pad": 8}),
+    ("conv", 8, 3, 3, {"cin_pad": 8}),
+    ("conv", 9, 5, 4, {"noflip": True}),
+    ("deconv", 6, 4, 4, {"noflip": True}),
+    ("linear", 10, 20, 1, {}),
+    ("conv", 8, 4, 3, {"apply_sn": False}),
+    ("conv", 8, 4, 3, {"power_iter": False}),
 ]
 
 
@@ -56,13 +73,14 @@ def reference(kind, w64, u64, v64, training, eps=1e-6):
     return m.weight, m
 
 
-def run(dev, dtype, L, call, ptr, stream, seed=0):
-    """-> list of (name, error, bound) rows; L = studiogan_amd._lib"""
+def run(dev, dtype, L, call, ptr, stream, seed=0, layers=LAYERS, tap=None):
+    """the table `layers` through one sg_sn_forward and one sg_sn_backward -> list of (name, error, bound) rows; L = studiogan_amd._lib.
+    tap(stage, recs, work), if given, is called after either call with the per-layer buffers (tools/sn_fold_check.py keeps them)"""
     g = torch.Generator().manual_seed(seed)
     es = 2 if dtype == torch.bfloat16 else 4
-    n = len(LAYERS)
+    n = len(layers)
     recs, work_floats = [], 0
-    for kind, rows, cin, R, opt in LAYERS:
+    for kind, rows, cin, R, opt in layers:
         RS = R * R
         cols = cin * RS
         if kind == "deconv":
@@ -100,6 +118,8 @@ def run(dev, dtype, L, call, ptr, stream, seed=0):
         d.trans, d.dgrad_noflip, d.Cin_pad = int(r["trans"]), int(r["noflip"]), r["cin_pad"]
     tab = torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(dev)
     call("sg_sn_forward", L.dt(dtype), ptr(tab), arr, n, 1e-6, ptr(work), work.numel(), stream())
+    if tap:
+        tap("forward", recs, work)
     rows_out = []
     img_tol = 4e-3 if dtype == torch.bfloat16 else 2e-6          # one bf16 rounding of W / sigma (2^-9 relative) resp. fp32 rounding
 
@@ -162,13 +182,15 @@ def run(dev, dtype, L, call, ptr, stream, seed=0):
     call("sg_sn_backward", ptr(btab), barr, n, ptr(work), work.numel(), stream())
     if dev.type == "cuda":
         torch.cuda.synchronize()
+    if tap:
+        tap("backward", recs, work)
     for i, r in enumerate(recs):
         tag = f"{i}:{r['kind']} {r['rows']}x{r['cin']}x{r['RS']}" + "".join(f" {k}" for k in r["opt"])
         rows_out.append((tag + " dW_orig", rel(r["dw_d"], r["gref"]), 1e-5))
     return rows_out
 
 
-def forward_table(dev, dtype, L, call, ptr, stream, shapes, seed, split_at=None):
+def forward_table(dev, dtype, L, call, ptr, stream, shapes, seed, split_at=None, tap=None):
     """sg_sn_forward on a table of plain convolution layers `shapes` = [(rows, cin, R)]; split_at = None: ONE call; an index: two calls ([0, split_at), [split_at, n)) on the
     same table. -> per layer (u, v, sigma, forward image, data-gradient image) as CPU tensors."""
     g = torch.Generator().manual_seed(seed)
@@ -192,4 +214,6 @@ def forward_table(dev, dtype, L, call, ptr, stream, shapes, seed, split_at=None)
     esz = ctypes.sizeof(L.SnLayer)
     for first, count in ([(0, n)] if split_at is None else [(0, split_at), (split_at, n - split_at)]):
         call("sg_sn_forward", L.dt(dtype), tab.data_ptr() + first * esz, ctypes.cast(ctypes.addressof(arr) + first * esz, ctypes.POINTER(L.SnLayer)), count, 1e-6, ptr(work), work.numel(), stream())
+        if tap:
+            tap(f"forward [{first}, {first + count})", recs, work)
     return [tuple(r[k].detach().float().cpu().clone() for k in ("u", "v", "sigma", "fwd", "dg")) for r in recs]

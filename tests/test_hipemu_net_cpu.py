@@ -386,6 +386,18 @@ def test_emulated_sn_kernels_against_torch_spectral_norm(dtype):
     assert not bad, bad
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_emulated_sn_table_with_a_row_wider_than_the_lds_row_buffer(dtype):
+    """tests/test_sn_gpu.py's WIDE_LAYERS table (one row wider than the 60 KB row buffer: the whole table goes through the fallback k_sn_pack) on the interpreter"""
+    import fullemu
+    import sn_checks as SC
+    with fullemu.Installed(dma_late=1, greedy=1, seed=2) as E:
+        L = E.L
+        rows = SC.run(torch.device("cpu"), dtype, L, L.call, L.ptr, L.stream, layers=SC.WIDE_LAYERS)
+    bad = [(n, e, t) for n, e, t in rows if not e <= t]
+    assert not bad, bad
+
+
 def test_emulated_sn_forward_table_longer_than_one_flat_tile_table():
     """tests/test_sn_gpu.py's 70-layer table (csrc/sn.hip walks it in runs of SN_MAXL = 64) on the interpreter: one call = two calls on the halves, bit for bit"""
     import fullemu

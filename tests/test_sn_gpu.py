@@ -20,6 +20,18 @@ def test_sn_forward_backward_against_torch_spectral_norm(sg, dtype):
     assert not bad, bad
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_sn_table_with_a_row_wider_than_the_lds_row_buffer(sg, dtype):
+    """SC.WIDE_LAYERS: one 30744-column layer sends the whole table to the fallback pack kernel k_sn_pack -- the same checks, the zero-filled padding of the forward
+    image among them (the image buffers are pre-filled with 3.0)"""
+    from studiogan_amd import _lib as L
+    rows = SC.run(torch.device("cuda:0"), dtype, L, L.call, L.ptr, L.stream, layers=SC.WIDE_LAYERS)
+    bad = [(n, e, t) for n, e, t in rows if not e <= t]
+    for n, e, t in rows:
+        print(f"{n:60s} err {e:.3e} (tol {t:.0e})")
+    assert not bad, bad
+
+
 def test_sn_forward_table_longer_than_one_flat_tile_table(sg):
     """csrc/sn.hip walks a table in runs of SN_MAXL = 64 layers (one flat tile table per run): 70 layers in ONE call = the same table handed over as [0, 37) + [37, 70), bit for bit."""
     from studiogan_amd import _lib as L
